@@ -2,7 +2,12 @@
 """
 bench.py -- one embedding-construction iteration per step on synthetic k-sampled tensors.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets the inputs up, runs W untimed and K timed steps, writes
+the outputs of the last timed step when --dump-outputs is given and prints the result line.  Everything else the script measures or
+checks -- the oracle checks (parity_*), the CPU baseline, the extra shard / full-config passes, the vcor fit -- runs only with
+--full, after the timed steps, and is never part of `value`.
 
 N > 1 without a torch.distributed environment: this process starts N ranks itself (torch.distributed.run as a
 child process, one rank per GPU over RCCL) BEFORE it touches the GPU, waits, and exits with the child's code.
@@ -13,26 +18,27 @@ UHF, 56 valence orbitals -> nemb = 256.  A step = diag (432 Hermitian 200x200) +
 k->R fold + Schmidt bath (43144 x 56 SVD per spin) + C_ao_emb + density-fitted ERI transform of this
 rank's share of the irreducible momentum transfers kL + embedding Hamiltonian.
 
-  --scaling strong (default): every timed step IS the full config -- all 112 irreducible kL / 12 152 DF blocks of C5 -- sharded
-                  over the N ranks by the reference's assign_workload rule: the config the metric is quoted on, at every N
-                  (N = 1: ~52 s per step; N = 8: 14 kL per GPU).  --steps K / --warmup W are honoured EXACTLY whenever the whole
-                  run (W + K steps, then the checks, the fit and the CPU baseline) fits --max-total-s (default 1500 s: at
-                  N = 1, 52 s per step, that is up to 19 + 5); only otherwise the timed steps are cut to
-                  min(K, max(3, floor(--max-timed-s / step seconds))) = 6 after two warm-up steps (the decision is taken on the second:
-                  the first also pays the one-off allocations), which keeps the run near ten minutes with the GPU busy 70 % of it;
-                  --max-total-s 1800 runs all 20 + 5 (25 minutes).  The line reports
-                  the counts that were run ("steps", "warmup"), the ones asked for and why they differ ("steps_requested",
-                  "warmup_requested", "steps_note": top level AND inside "config").  One extra pass over a 14-kL shard per GPU
+  --scaling weak (default): every GPU transforms --kl-per-gpu irreducible kL per step (14 = 112 / 8, so N = 8 is exactly the full
+                  C5 iteration; N = 1: ~6.7 s per step, so that a run with the step counts it is given -- they are always the
+                  counts that are run, "steps" / "warmup" of the line -- stays short enough to be repeated for every change);
+                  with --full ONE pass over the full config after the timed region is reported under "full_config".
+  --scaling strong: every timed step IS the full config -- all 112 irreducible kL / 12 152 DF blocks of C5 -- sharded
+                  over the N ranks by the reference's assign_workload rule (N = 1: ~52 s per step; N = 8: 14 kL per GPU): the
+                  configuration the figures of DESIGN.md are quoted on.  With --full one extra pass over a 14-kL shard per GPU
                   (the 8-GPU share) is reported under "shard_pass" as a secondary rate.
-  --scaling weak: every GPU transforms --kl-per-gpu irreducible kL per step (14 = 112 / 8, so N = 8 is exactly the full C5
-                  iteration); after the timed region ONE pass over the full config is reported under "full_config".
+
+--dump-outputs DIR writes what the last timed step handed back -- the arrays a caller of pipeline.iteration receives -- as
+DIR/<name>.npy (float64; complex arrays with a trailing (re, im) axis): ew, occ, mu, sigma, rho_R, basis, C_ao_emb, eri and the
+embedding Hamiltonian (H1, JK_core, rdm1_emb, veff, fock_emb).  An array of more than 2^20 numbers is written as a fixed sample:
+2^20 flat positions drawn from a constant seed, for the ERI whole pair rows drawn the same way (at most 64 MB in all); the line
+lists shapes and what was sampled under "dump_outputs".  Inputs are seeded: the same arguments give the same arrays.
 
 The DF blocks of the timed kL shard are RESIDENT in HBM when they fit (--df auto: C3, C4 -- 85 GB; loaded once before the timed
 region, what a DMET run does with a DF tensor that fits) and otherwise regenerated on the device (Philox) inside every step,
 standing in for the reference's HDF5 reads (C5: 6.2 TB).  All other inputs are resident in HBM before the clock starts; the line
 says which under "input".
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0); full_config, shard_pass, parity_*, vcor_fit and cpu_baseline only with --full:
   value            = ALGORITHMIC FP64 flop of the ERI transform (8 flop per complex
                      multiply-add, full npair^2 contraction) of all ranks / wall-clock of the whole step (max over ranks)
   roofline         = the dominant kernel family: flop ISSUED to the f64 matrix pipe (counted by the library at launch:
@@ -80,25 +86,27 @@ def parse():
                                                             "lattices C1 / C2, whose step is 0.1 - 0.2 ms)")
     p.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 1 / 30)")
     p.add_argument("--workload", default="C5")
-    p.add_argument("--scaling", choices=("weak", "strong"), default="strong")
-    p.add_argument("--max-timed-s", type=float, default=330.0,
-                   help="cap of the timed region when the requested counts do not fit --max-total-s: timed steps = "
-                        "min(--steps, max(3, floor(this / seconds of one step)))")
-    p.add_argument("--max-total-s", type=float, default=1500.0,
-                   help="wall-clock this whole process may take (the driver's window is 1800 s): --steps / --warmup are honoured "
-                        "EXACTLY whenever warm-up + timed steps + the checks after them fit it")
+    p.add_argument("--scaling", choices=("weak", "strong"), default="weak",
+                   help="timed step: --kl-per-gpu irreducible kL per GPU (weak) or the whole config sharded over the GPUs (strong: 52 s "
+                        "per step at C5 on one GPU)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything that is not needed for the headline figure: the oracle checks "
+                        "(parity_*), the CPU baseline, the extra shard / full-config pass and the vcor fit (each can be switched "
+                        "off by its --no-* option); a plain run skips them all")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step returned as DIR/<name>.npy (float64; large ones as a fixed seeded sample)")
     p.add_argument("--parity-seed", type=int, default=-1, help="seed of the sampled embedding orbitals (-1: from the clock)")
     p.add_argument("--df", choices=("auto", "resident", "regenerate"), default="auto",
                    help="AO DF blocks of the timed kL shard: resident in HBM (loaded once before the timed region, read in place "
                         "by every step: what a DMET run does when the DF tensor fits -- C4: 85 GB) or regenerated by the device "
                         "generator inside every step (C5: 6.2 TB does not fit); auto = resident when the shard fits in 45 %% of "
                         "the free device memory")
-    p.add_argument("--no-shard-pass", action="store_true", help="strong scaling: skip the extra 14-kL-per-GPU pass")
+    p.add_argument("--no-shard-pass", action="store_true", help="--full: strong scaling: skip the extra 14-kL-per-GPU pass")
     p.add_argument("--kl-per-gpu", type=int, default=14, help="weak scaling: irreducible kL transformed per GPU per step")
     p.add_argument("--max-blocks-per-kl", type=int, default=0, help="debug: truncate the i-loop (0 = all)")
-    p.add_argument("--no-full-config", action="store_true", help="skip the pass over the whole config after the timed steps")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-parity", action="store_true", help="skip every oracle check")
+    p.add_argument("--no-full-config", action="store_true", help="--full: skip the pass over the whole config after the timed steps")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    p.add_argument("--no-parity", action="store_true", help="--full: skip every oracle check")
     p.add_argument("--parity-budget-s", type=float, default=260.0,
                    help="host-time budget of the ERI oracle; the full-config check is dropped first, then the timed check is cut "
                         "to an UN-timed re-run of the first kL of every shard -- the line says which")
@@ -106,7 +114,13 @@ def parse():
     p.add_argument("--fit-iters", type=int, default=300,
                    help="MaxIter of the vcor fit measured after the timed steps (reference default 300, "
                         "routine/slater.py:909; 0 = skip); reported under \"vcor_fit\", never part of `value`")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps is not None and a.steps < 1:
+        p.error("--steps must be at least 1")
+    if not a.full:
+        a.no_parity = a.no_cpu_baseline = a.no_shard_pass = a.no_full_config = True
+        a.fit_iters = 0
+    return a
 
 
 def spawn_ranks(n):
@@ -277,8 +291,62 @@ def fetch_rows(eri_dev, spin_pair, npair, idx, table=None):
     return dist.gather_rows_numpy(eri_dev, spin_pair, npair, idx, table)[:, :, idx]
 
 
+DUMP_SEED = 20240229             # the sample of --dump-outputs: a constant, so that two builds write the same positions
+DUMP_MAX_NUMBERS = 1 << 20       # per array (8 MB of float64); the ERI: whole pair rows, at most twice that
+
+
+def dump_outputs(dirname, out, sysm, rank):
+    """--dump-outputs: the arrays of `out` (what pipeline.iteration returned) as <dirname>/<name>.npy, float64, complex ones with a
+    trailing (re, im) axis.  Arrays above DUMP_MAX_NUMBERS are written as the flat positions a generator seeded with DUMP_SEED
+    draws; the ERI as whole pair rows drawn the same way (row-sharded ERI: assembled from the owners, so every rank must call).
+    Rank 0 writes.  Returns {name: {"shape", "full_shape", "sample"}} for the result line."""
+    rng = np.random.default_rng(DUMP_SEED)
+    if rank == 0:
+        os.makedirs(dirname, exist_ok=True)
+    info = {}
+
+    def put(name, x, full_shape=None, sample=None):
+        x = np.asarray(x)
+        if np.iscomplexobj(x):
+            x = np.stack([x.real, x.imag], axis=-1)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if full_shape is None:
+            full_shape = x.shape
+            if x.size > DUMP_MAX_NUMBERS:
+                pos = np.sort(rng.integers(0, x.size, DUMP_MAX_NUMBERS))
+                x, sample = x.reshape(-1)[pos], "%d flat positions, rng(%d).integers, sorted" % (DUMP_MAX_NUMBERS, DUMP_SEED)
+        if rank == 0:
+            np.save(os.path.join(dirname, name + ".npy"), x)
+        info[name] = {"shape": list(x.shape), "full_shape": list(full_shape), "sample": sample}
+
+    n, nk, spin, nemb = sysm.nlo, sysm.nk, sysm.spin, out["nemb"]
+    put("ew", out["ew"].get().reshape(spin, nk, n))
+    put("occ", out["occ"].get().reshape(spin, nk, n))
+    put("mu", np.atleast_1d(np.asarray(out["mu"], dtype=np.float64)))
+    put("sigma", np.concatenate([np.ravel(x) for x in out["sigma"]]) if isinstance(out["sigma"], (list, tuple)) else out["sigma"])
+    put("rho_R", out["rho_R"].get().reshape(spin, nk, n, n))
+    put("basis", out["basis"].get().reshape(spin, nk, n, nemb))
+    if "eri" in out:
+        put("C_ao_emb", out["C_ao_emb"].get().reshape(spin, nk, sysm.nao, nemb))
+        npair, spin_pair = nemb * (nemb + 1) // 2, spin * (spin + 1) // 2
+        nrows = max(1, min(npair, 2 * DUMP_MAX_NUMBERS // (spin_pair * npair)))
+        rows = np.arange(npair) if nrows == npair else np.sort(rng.choice(npair, size=nrows, replace=False))
+        table = out.get("eri_rows")
+        if table is None:
+            eri = np.stack([np.stack([out["eri"].offset((b * npair + int(r)) * npair, (npair,)).get() for r in rows])
+                            for b in range(spin_pair)])
+        else:
+            from libdmet_preview_amd.parallel import dist
+            eri = dist.gather_rows_numpy(out["eri"], spin_pair, npair, rows, table)
+        put("eri", eri, full_shape=(spin_pair, npair, npair),
+            sample=None if nrows == npair else "pair rows %s of every spin block, rng(%d)" % ([int(r) for r in rows], DUMP_SEED))
+        for k, v in sorted(out.get("emb_ham", {}).items()):
+            if isinstance(v, np.ndarray):
+                put(k, v)
+    return info
+
+
 def main():
-    t_process_start = time.perf_counter()
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus))
@@ -427,46 +495,17 @@ def main():
             yref = dist.all_reduce_sum_numpy(yref)
         return float(np.abs(y - yref).max()), float(np.abs(yref).max())
 
-    # ---- warm-up and the number of timed steps -------------------------------------------------------------------------
-    nsteps, nwarm = a.steps, a.warmup
-    if a.warmup > 0:
-        fence()
-        tw0 = time.perf_counter()
+    # ---- warm-up, then exactly --steps timed steps ---------------------------------------------------------------------------
+    out = None
+    for _ in range(a.warmup):
         out = step({}, kl_mine)
-        fence()
-        t_w = max_over_ranks(time.perf_counter() - tw0)
-        warm_done = 1
-        if not model and a.warmup >= 2:
-            # the first step also pays the one-off allocations (ERI workspace, plane stack): the decision below is taken on the
-            # SECOND warm-up step, which costs what a timed step costs
-            fence()
-            tw0 = time.perf_counter()
-            out = step({}, kl_mine)
-            fence()
-            t_w = max_over_ranks(time.perf_counter() - tw0)
-            warm_done = 2
-        if not model:
-            # A whole-config step at N = 1 takes ~52 s.  The counts asked for are honoured EXACTLY whenever the rest of the
-            # warm-up, the timed steps and what follows them (shard pass, oracle checks within --parity-budget-s, fit, CPU
-            # baseline) fit --max-total-s; only otherwise are they cut to what fits --max-timed-s (never below 3 + 1)
-            after = 0.0 if a.no_parity else min(a.parity_budget_s, 110.0) + 20.0
-            after += (0.0 if a.no_cpu_baseline else a.cpu_seconds + 5.0) + (10.0 if a.fit_iters > 0 else 0.0) + 0.2 * t_w + 30.0
-            left = a.max_total_s - (time.perf_counter() - t_process_start) - after
-            if (a.steps + a.warmup - warm_done) * t_w * 1.03 > left:
-                nsteps = min(a.steps, max(3, int(a.max_timed_s // max(t_w, 1e-6))))
-                nwarm = max(warm_done, min(a.warmup, max(1, int(0.3 * a.max_timed_s // max(t_w, 1e-6)))))
-            if distributed:          # every rank must run the same counts
-                c = dist.all_reduce_sum_numpy(np.array([float(nsteps), float(nwarm)]) * (1.0 if rank == 0 else 0.0))
-                nsteps, nwarm = int(round(c[0])), int(round(c[1]))
-        for _ in range(nwarm - warm_done):
-            out = step({}, kl_mine)
     fence()
     ctx.profile(True)
     ctx.profile_read(reset=True)
     ctx.profile_read_flops(reset=True)
     timers = {}
     t0 = time.perf_counter()
-    for _ in range(nsteps):
+    for _ in range(a.steps):
         out = step(timers, kl_mine)
     fence()
     t1 = time.perf_counter()
@@ -477,18 +516,19 @@ def main():
     nemb = out["nemb"]
     npair = nemb * (nemb + 1) // 2
 
+    # what the timed path handed back in its last step, before any later pass reuses the buffers
+    dumped = dump_outputs(a.dump_outputs, out, sysm, rank) if a.dump_outputs else None
+
     if model:
-        model_line(a, ctx, sysm, out, fam, timers, elapsed, world, rank, distributed)
+        model_line(a, ctx, sysm, out, fam, timers, elapsed, world, rank, distributed, dumped)
         return
-    a.steps_requested, a.warmup_requested = a.steps, a.warmup
-    a.steps, a.warmup = nsteps, nwarm                        # from here on: the counts that were run
 
     # ---- per-rank view of the timed region (N > 1): stage seconds, DF blocks and bytes put on the wire per step ------------
     per_rank = None
     if distributed:
         keys = sorted(timers)
         sl = np.zeros((world, len(keys) + 2))
-        sl[rank, :len(keys)] = [timers[k] / nsteps for k in keys]
+        sl[rank, :len(keys)] = [timers[k] / a.steps for k in keys]
         sl[rank, len(keys)] = out["nblocks"]
         n_, nk_, sp_ = sysm.nlo, sysm.nk, sysm.spin
         sent = sp_ * nk_ * n_ * n_ * 8 + sp_ * nk_ * n_ * 8 + 3 * sp_ * nemb * nemb * 8        # rho_R, eigenvalue table, J / K partials
@@ -513,12 +553,13 @@ def main():
     timed_is_full = (a.scaling == "strong") or (len(kl_mine) * world >= n_irr and maxblk is None)
 
     # sampled rows of the TIMED ERI and its Freivalds residual, taken before the buffer is reused by a later pass
-    A = parity_sample(nemb, pseed)
-    from oracle import eri_sample as ES                      # checker only
-    pidx = np.asarray([p[2] for p in ES.sample_pairs(A)])
     got_timed = None
     frv_timed = frv_full = None
+    if not a.no_parity or not a.no_cpu_baseline:
+        from oracle import eri_sample as ES                      # checker / baseline only
     if not a.no_parity:
+        A = parity_sample(nemb, pseed)
+        pidx = np.asarray([p[2] for p in ES.sample_pairs(A)])
         got_timed = fetch_rows(eri_dev, spin_pair, npair, pidx, out.get("eri_rows"))
         frv_timed = freivalds(out)
 
@@ -758,21 +799,17 @@ def main():
                 hbm["fold"]["k2R_algorithmic_GB_per_launch"] = round((16.0 + 8.0) * spin * nk * n * n / 1e9, 3)
         roofline["hbm_stages"] = hbm
         n_mine = len(kl_mine)
-        steps_note = "as requested" if (a.steps, a.warmup) == (a.steps_requested, a.warmup_requested) else \
-            "cut: %.0f s/step x (%d + %d) does not fit --max-total-s %g" % (elapsed / a.steps, a.steps_requested,
-                                                                            a.warmup_requested, a.max_total_s)
         res = {
             "metric": "DMET embedding-construction iteration (diag+bath+ERI-transform): ERI-transform algorithmic TFLOP/s over the whole step",
             "value": round(flops_all / elapsed / 1e12, 3),
             "unit": "TFLOP/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "steps_requested": a.steps_requested, "warmup_requested": a.warmup_requested,
-            "steps_note": steps_note, "input": input_note,
+            "input": input_note,
             "df_mode": "regenerate" if df_resident_bytes == 0 else "resident", "df_resident_GB_per_gpu": round(df_resident_bytes / 1e9, 2),
             "ms_per_step": round(elapsed / a.steps * 1e3, 2),
             "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
             "vs_baseline_note": "null by contract: the reference publishes no number for this metric (BASELINE.md section 1); "
-                                "the measured CPU path is under cpu_baseline, its ratio under vs_cpu_baseline",
+                                "the measured CPU path is under cpu_baseline, its ratio under vs_cpu_baseline (--full)",
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": "%s: mesh %s nao %d naux %d nemb %d spin %d; timed step = %d irreducible kL per GPU "
                                    "(%d of %d in total over %d GPUs), %d DF blocks per GPU per step, %s%s"
@@ -784,7 +821,6 @@ def main():
                                       ("; the timed step IS the whole config" if timed_is_full else "")),
                        "scaling_note": "strong: every timed step is the WHOLE config sharded over the ranks" if a.scaling == "strong"
                                        else "weak: --kl-per-gpu irreducible kL per GPU per step",
-                       "steps_requested": a.steps_requested, "warmup_requested": a.warmup_requested, "steps_note": steps_note,
                        "input": input_note,
                        "parallelism": "kL-sharded x%d, k-sharded diag, all-reduce(ew) + all-reduce(rho_R); ERI: K-stacked contraction finished "
                                       "band by band, every finished band of rows reduced to its owner underneath the remaining GEMMs "
@@ -803,6 +839,8 @@ def main():
                 rc = 3
         elif timed_is_full:
             res["full_config_iteration_wall_s"] = round(elapsed / a.steps, 4)
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if shard is not None:
             res["shard_pass"] = shard
         if per_rank is not None:
@@ -858,7 +896,7 @@ def main():
         sys.exit(rc)
 
 
-def model_line(a, ctx, sysm, out, fam, timers, elapsed, world, rank, distributed):
+def model_line(a, ctx, sysm, out, fam, timers, elapsed, world, rank, distributed, dumped=None):
     """Model lattices (BASELINE configs 1-2: Hubbard): no DF tensor, the step is diag + occupations + density + fold + bath.
     HBM-bound stages: every family is reported as algorithmic bytes / HIP-event time against the 8 TB/s roof."""
     from libdmet_preview_amd.parallel import dist
@@ -905,6 +943,8 @@ def model_line(a, ctx, sysm, out, fam, timers, elapsed, world, rank, distributed
                             "frac": d["frac_of_hbm_peak"], "traffic": None, "stages": stages,
                             "note": "launch/latency bound at this size (SURVEY.md section 8d): %d matrices of %dx%d, bath %d x %d"
                                     % (spin * nk, n, n, len(sysm.env_idx), sysm.nval)}}
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if stage_parity is not None:
             res.update(stage_parity)
         if not a.no_cpu_baseline:

@@ -1160,7 +1160,7 @@ def main():
     shim.install()
     shim.quiet()
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G13", "G14", "G15", "G16", "G17", "G18", "G19", "G20", "G21", "G22", "G23", "G24", "G25", "G26", "G27", "G28", "G29", "G30", "G31", "G32", "G33", "G34", "G35", "G36", "G37", "G38"]
+    which = sys.argv[1:] or ["G1", "G2", "G3", "G4", "G5", "G6", "G7", "G8", "G9", "G10", "G11", "G12", "G13", "G14", "G15", "G16", "G17", "G18", "G19", "G20", "G21", "G22", "G23", "G24", "G25", "G26", "G27", "G28", "G29", "G30", "G31", "G32", "G33", "G34", "G35", "G36", "G37", "G38", "G39", "G40"]
     for g in which:
         globals()["gen_" + g]()
 
@@ -2340,6 +2340,77 @@ def gen_G38():
                 out["%s/upd%d_fock_k" % (name, spin)] = np.asarray(L.fock_lo_k)
     np.savez_compressed(os.path.join(GOLD, "G38_model_lattices.npz"), **out)
     print("G38 done", len(out), "arrays")
+
+
+def gen_G39():
+    """Host containers against the reference's own classes (tests/test_host_containers.py): routine/vcor.py:19-103 Vcor.assign /
+    get on a two-parameter local potential, system/integral.py get_eri_format and the Integral pair lists, utils/misc.py max_abs /
+    mdot / add_spin_dim / get_spin_dim -- seeded inputs and what the reference returns for them."""
+    from libdmet.routine import vcor as rvcor
+    from libdmet.system import integral as rint
+    from libdmet.utils import misc as rmisc
+    rng = np.random.default_rng(0)
+    grad = np.zeros((2, 1, 2, 2))
+    grad[0, 0, 0, 0] = grad[0, 0, 1, 1] = 1.0
+    grad[1, 0, 0, 1] = grad[1, 0, 1, 0] = 1.0
+
+    class RLocal(rvcor.Vcor):
+        def __init__(self):
+            rvcor.Vcor.__init__(self)
+            self.grad = grad
+
+        def evaluate(self):
+            return np.tensordot(self.param, self.grad, axes=(0, 0))
+
+        def gradient(self):
+            return self.grad
+
+        def length(self):
+            return 2
+    out = {"vcor/grad": grad}
+    v0 = rng.standard_normal((1, 2, 2))
+    r = RLocal()
+    r.assign(v0)
+    out["vcor/v0"], out["vcor/param"], out["vcor/get"] = v0, np.asarray(r.param), np.asarray(r.get())
+    out["vcor/get_cell1_R"] = np.asarray(r.get(1, kspace=False))
+    n = 4
+    npair = n * (n + 1) // 2
+    shapes = [(1, n, n, n, n), (3, n, n, n, n), (n, n, n, n), (3, npair, npair), (npair, npair), (1, npair * (npair + 1) // 2),
+              (npair * (npair + 1) // 2,)]
+    fmts = [rint.get_eri_format(np.zeros(sh), n) for sh in shapes]
+    out["eri_format/norb"] = np.asarray(n)
+    for i, (sh, f) in enumerate(zip(shapes, fmts)):
+        out["eri_format/shape%d" % i] = np.asarray(sh)
+    out["eri_format/format"] = np.asarray([f[0] for f in fmts])
+    out["eri_format/spin_dim"] = np.asarray([f[1] for f in fmts])
+    Ir = rint.Integral(n, True, False, 0.0, np.zeros((1, n, n)), np.zeros((1, npair, npair)))
+    out["integral/pairNoSymm"], out["integral/pairSymm"] = np.asarray(Ir.pairNoSymm()), np.asarray(Ir.pairSymm())
+    out["integral/pairAntiSymm"] = np.asarray(Ir.pairAntiSymm())
+    x = rng.standard_normal((3, 5)) + 1j * rng.standard_normal((3, 5))
+    out["misc/x"], out["misc/max_abs_x"], out["misc/max_abs_x_real"] = x, np.asarray(rmisc.max_abs(x)), np.asarray(rmisc.max_abs(x.real))
+    mats = np.asarray([rng.standard_normal((3, 3)) for _ in range(4)])
+    out["misc/mats"], out["misc/mdot"] = mats, np.asarray(rmisc.mdot(*mats))
+    H = rng.standard_normal((5, 2, 2))
+    out["misc/H"], out["misc/add_spin_dim_2"] = H, np.asarray(rmisc.add_spin_dim(H, 2))
+    out["misc/get_spin_dim"] = np.asarray(rmisc.get_spin_dim([H, H[None]]))
+    np.savez_compressed(os.path.join(GOLD, "G39_host_containers.npz"), **out)
+    print("G39 done", len(out), "arrays")
+
+
+def gen_G40():
+    """Names only: the callables (dunder names left out) of every reference module the rebinding plan of libdmet_preview_amd.patch touches, and of
+    system.lattice.Lattice (tests/test_host_patch.py checks the plan against this list)."""
+    import importlib
+    import json
+    from libdmet_preview_amd import patch
+    mods = sorted({ref for _, ref, _ in patch.binding_table()} | {"system.lattice"})
+    public = lambda obj: sorted(k for k in dir(obj) if not k.startswith("__") and callable(getattr(obj, k)))
+    out = {"modules": {m: public(importlib.import_module("libdmet." + m)) for m in mods},
+           "Lattice": public(importlib.import_module("libdmet.system.lattice").Lattice)}
+    with open(os.path.join(GOLD, "G40_reference_names.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("G40 done", len(mods), "modules")
 
 
 if __name__ == "__main__":

@@ -11,9 +11,8 @@ patch rebinds.  Shared by tests/test_host_df_object.py (CPU: resolution logic) a
                      fed identity coefficients.
   fake_h5py          a module object for sys.modules["h5py"] whose File(path, mode) returns the mapping registered for `path`
                      and records open / close: proves the path-string branch without h5py on the box.
-  patched_reference  context manager: libdmet_preview_amd.patch.install() on the reference's module tree -- the real one under
-                     oracle/shim.py where /root/reference exists (this container), a placeholder tree with the reference's
-                     module names on the GPU box -- yielding the module `libdmet.routine.slater`.
+  patched_reference  context manager: libdmet_preview_amd.patch.install() on a placeholder tree with the reference's module
+                     names, yielding the module `libdmet.routine.slater`.
 """
 import contextlib
 import importlib
@@ -68,28 +67,25 @@ def fake_h5py(registry):
 
 @contextlib.contextmanager
 def patched_reference(**install_kwargs):
-    """Yield `libdmet.routine.slater` with libdmet_preview_amd.patch installed (real reference tree under the import shim when
-    it exists, placeholder tree otherwise); everything is undone on exit."""
+    """Yield `libdmet.routine.slater` with libdmet_preview_amd.patch installed on a placeholder tree with the reference's module
+    names (the plan itself is checked against the reference's recorded names by tests/test_host_patch.py, golden G40); everything
+    is undone on exit."""
     from libdmet_preview_amd import patch
-    from oracle import shim
     made = []
-    if shim.available():
-        shim.install()
-        shim.quiet()
-    else:
-        def mk(name):
-            if name not in sys.modules:
-                sys.modules[name] = types.ModuleType(name)
-                made.append(name)
-            return sys.modules[name]
-        mk("libdmet")
-        for ours, ref, name in patch.binding_table():
-            parts = ref.split(".")
-            for i in range(1, len(parts) + 1):
-                mk("libdmet." + ".".join(parts[:i]))
-            setattr(sys.modules["libdmet." + ref], name, ("placeholder", ref, name))
-        lat = mk("libdmet.system.lattice")
-        lat.Lattice = type("Lattice", (), {n: ("placeholder", n) for n in patch._LATTICE_METHODS})
+
+    def mk(name):
+        if name not in sys.modules:
+            sys.modules[name] = types.ModuleType(name)
+            made.append(name)
+        return sys.modules[name]
+    mk("libdmet")
+    for ours, ref, name in patch.binding_table():
+        parts = ref.split(".")
+        for i in range(1, len(parts) + 1):
+            mk("libdmet." + ".".join(parts[:i]))
+        setattr(sys.modules["libdmet." + ref], name, ("placeholder", ref, name))
+    lat = mk("libdmet.system.lattice")
+    lat.Lattice = type("Lattice", (), {n: ("placeholder", n) for n in patch._LATTICE_METHODS})
     handle = patch.install(**install_kwargs)
     try:
         yield importlib.import_module("libdmet.routine.slater")

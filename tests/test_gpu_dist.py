@@ -280,7 +280,7 @@ def test_two_ranks_over_rccl_match_single_process():
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_script_two_ranks_gloo_one_gpu(scaling):
-    """bench.py ITSELF with two ranks (torch.distributed.run, gloo exchanges, both ranks on GPU 0): shards, k-sharded mean
+    """bench.py --full ITSELF with two ranks (torch.distributed.run, gloo exchanges, both ranks on GPU 0): shards, k-sharded mean
     field with the device-side eigenvalue exchange, kL-sharded ERI, the full-config pass after the timed steps (weak) or
     the full config as the timed step (strong), the rank-summed oracle samples and the per-stage oracle check.  The JSON
     line must carry the contract keys, every parity flag must be green and the exit status 0.  Workload C4-shaped but
@@ -295,7 +295,7 @@ def test_bench_script_two_ranks_gloo_one_gpu(scaling):
     env.update({"DMK_BENCH_BACKEND": "gloo", "DMK_BENCH_ONE_GPU": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0",
                 "DMK_BENCH_OVERRIDE": json.dumps({"mesh": [3, 2, 2], "nlo": 24, "naux": 16, "nval": 8, "spin": 2})})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--workload", "C3", "--kl-per-gpu", "1", "--scaling", scaling, "--fit-iters", "0", "--cpu-seconds", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

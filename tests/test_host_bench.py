@@ -55,3 +55,17 @@ def test_bench_rank_uses_world_size_from_env():
     """Inside a torch.distributed.run launch (WORLD_SIZE set) bench.py must NOT spawn again."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'if a.gpus > 1 and "WORLD_SIZE" not in os.environ:' in src
+
+
+def test_plain_run_leaves_everything_else_to_full(monkeypatch):
+    """Without --full the parsed options switch off the oracle checks, the CPU baseline, the extra passes and the fit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (4, 2, False, None)
+    assert a.no_parity and a.no_cpu_baseline and a.no_shard_pass and a.no_full_config and a.fit_iters == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "somewhere"
+    assert not (a.no_parity or a.no_cpu_baseline or a.no_shard_pass or a.no_full_config) and a.fit_iters == 300

@@ -1,12 +1,10 @@
 """
 Host containers at the exit / entry of the path: routine.vcor.Vcor, system.integral.Integral / get_eri_format and the
 utils.misc helpers.  Their bodies are this package's own; the CONTRACT is the reference's (routine/vcor.py:19-103,
-system/integral.py:60-128, 883-927, utils/misc.py:34-86).  Stand-alone semantic checks, and -- when the reference tree is
-present in this container (never on the GPU box) -- a side-by-side run against the reference's own classes under the import
-shim on the same inputs.
+system/integral.py:60-128, 883-927, utils/misc.py:34-86).  Stand-alone semantic checks, and a comparison with what the
+reference's own classes return on the same inputs (golden G39, captured under the import shim).
 """
 import itertools as it
-import os
 
 import numpy as np
 import pytest
@@ -14,8 +12,6 @@ import pytest
 from libdmet_preview_amd.routine import vcor as avcor
 from libdmet_preview_amd.system import integral as aint
 from libdmet_preview_amd.utils import misc as amisc
-
-HAVE_REF = os.path.isdir("/root/reference/libdmet")
 
 
 class _Local(avcor.Vcor):
@@ -98,43 +94,34 @@ def test_misc_helpers():
     assert amisc.add_spin_dim(np.zeros((1, 3, 2, 2)), 2).shape == (2, 3, 2, 2)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present (GPU box)")
-def test_against_the_reference_classes():
-    from oracle import shim
-    shim.install()
-    shim.quiet()
-    from libdmet.routine import vcor as rvcor
-    from libdmet.system import integral as rint
-    from libdmet.utils import misc as rmisc
-    rng = np.random.default_rng(0)
+def test_against_the_reference_classes(golden):
+    """Golden G39: what the reference's own Vcor / Integral / get_eri_format / misc helpers return on seeded inputs, captured under
+    the import shim (oracle/gen_golden.py gen_G39); the same inputs through this package's classes."""
+    g = golden("G39_host_containers.npz")
     # Vcor.assign on the same parametrisation
-    class RLocal(rvcor.Vcor):
-        def __init__(self):
-            rvcor.Vcor.__init__(self)
-            self.grad = _Local().grad
-        evaluate, gradient, length = _Local.evaluate, _Local.gradient, _Local.length
-    v0 = rng.standard_normal((1, 2, 2))
-    a, r = _Local(), RLocal()
-    a.assign(v0)
-    r.assign(v0)
-    assert np.allclose(a.param, r.param, atol=1e-15) and np.allclose(a.get(), r.get(), atol=1e-15)
-    assert np.array_equal(a.get(1, kspace=False), r.get(1, kspace=False))
+    assert np.array_equal(g["vcor/grad"], _Local().grad)
+    a = _Local()
+    a.assign(g["vcor/v0"])
+    assert np.allclose(a.param, g["vcor/param"], atol=1e-15) and np.allclose(a.get(), g["vcor/get"], atol=1e-15)
+    assert np.array_equal(a.get(1, kspace=False), g["vcor/get_cell1_R"])
     # get_eri_format / Integral pair lists / misc helpers on random shapes
-    n = 4
+    n = int(g["eri_format/norb"])
     npair = n * (n + 1) // 2
-    for shape in [(1, n, n, n, n), (3, n, n, n, n), (n, n, n, n), (3, npair, npair), (npair, npair), (1, npair * (npair + 1) // 2),
-                  (npair * (npair + 1) // 2,)]:
-        assert aint.get_eri_format(np.zeros(shape), n) == rint.get_eri_format(np.zeros(shape), n)
+    assert len(g["eri_format/format"]) == 7
+    for i, (fmt, sd) in enumerate(zip(g["eri_format/format"], g["eri_format/spin_dim"])):
+        shape = tuple(int(x) for x in g["eri_format/shape%d" % i])
+        assert aint.get_eri_format(np.zeros(shape), n) == (str(fmt), int(sd)), shape
     Ia = aint.Integral(n, True, False, 0.0, np.zeros((1, n, n)), np.zeros((1, npair, npair)))
-    Ir = rint.Integral(n, True, False, 0.0, np.zeros((1, n, n)), np.zeros((1, npair, npair)))
-    assert Ia.pairNoSymm() == Ir.pairNoSymm() and Ia.pairSymm() == Ir.pairSymm() and Ia.pairAntiSymm() == Ir.pairAntiSymm()
-    x = rng.standard_normal((3, 5)) + 1j * rng.standard_normal((3, 5))
-    assert amisc.max_abs(x) == pytest.approx(rmisc.max_abs(x)) and amisc.max_abs(x.real) == pytest.approx(rmisc.max_abs(x.real))
-    mats = [rng.standard_normal((3, 3)) for _ in range(4)]
-    assert np.allclose(amisc.mdot(*mats), rmisc.mdot(*mats))
-    H = rng.standard_normal((5, 2, 2))
-    assert np.array_equal(amisc.add_spin_dim(H, 2), rmisc.add_spin_dim(H, 2))
-    assert amisc.get_spin_dim([H, H[None]]) == rmisc.get_spin_dim([H, H[None]])
+    as_lists = lambda arr: [tuple(int(x) for x in row) for row in arr]
+    assert Ia.pairNoSymm() == as_lists(g["integral/pairNoSymm"]) and Ia.pairSymm() == as_lists(g["integral/pairSymm"])
+    assert Ia.pairAntiSymm() == as_lists(g["integral/pairAntiSymm"])
+    x = g["misc/x"]
+    assert amisc.max_abs(x) == pytest.approx(float(g["misc/max_abs_x"]))
+    assert amisc.max_abs(x.real) == pytest.approx(float(g["misc/max_abs_x_real"]))
+    assert np.allclose(amisc.mdot(*g["misc/mats"]), g["misc/mdot"])
+    H = g["misc/H"]
+    assert np.array_equal(amisc.add_spin_dim(H, 2), g["misc/add_spin_dim_2"])
+    assert amisc.get_spin_dim([H, H[None]]) == int(g["misc/get_spin_dim"])
 
 
 def test_orthonormal_completion_of_null_bath_columns():

@@ -1,10 +1,11 @@
 """
 Host logic of libdmet_preview_amd.patch (the rebinding of SURVEY.md section 8b): every entry of the binding table
-exists on our side; install / uninstall rebind every holder of a name and restore it; when the reference tree is
-present in this container (never on the GPU box) the table is checked against the reference's real module tree
-under oracle/shim.py.  No compute is called.
+exists on our side; install / uninstall rebind every holder of a name and restore it; the table is checked against
+the names of the reference's real module tree (golden G40, read off it under oracle/shim.py).  No compute is called.
 """
 import importlib
+import json
+import os
 import sys
 import types
 
@@ -75,24 +76,47 @@ def test_install_rebinds_every_holder_and_uninstall_restores():
             sys.modules.pop(k, None)
 
 
+def _recorded_reference(root):
+    """A module tree named like the reference's, holding a placeholder for every callable that golden G40 records
+    (oracle/gen_golden.py gen_G40: names read off the reference's real module tree under the import shim)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "G40_reference_names.json")) as f:
+        rec = json.load(f)
+    mods = {}
+
+    def mk(name):
+        if name not in mods:
+            mods[name] = sys.modules[name] = types.ModuleType(name)
+        return mods[name]
+    mk(root)
+    for ref, names in rec["modules"].items():
+        parts = ref.split(".")
+        for i in range(1, len(parts) + 1):
+            mk(root + "." + ".".join(parts[:i]))
+        for name in names:
+            setattr(mods[root + "." + ref], name, ("placeholder", ref, name))
+    mods[root + ".system.lattice"].Lattice = type("Lattice", (), {n: ("placeholder", n) for n in rec["Lattice"]})
+    return rec, mods
+
+
 def test_binding_table_matches_the_reference_tree():
-    from oracle import shim
-    if not shim.available():
-        pytest.skip("reference tree not present (GPU box)")
-    shim.install()
-    shim.quiet()
-    for ours, ref, name in patch.binding_table():
-        mod = importlib.import_module("libdmet." + ref)
-        assert hasattr(mod, name), (ref, name)
-    lat = importlib.import_module("libdmet.system.lattice")
-    for name in patch._LATTICE_METHODS:
-        assert hasattr(lat.Lattice, name), name
-    handle = patch.install()
+    root = "recorded_libdmet_for_patch_test"
+    rec, mods = _recorded_reference(root)
     try:
-        import libdmet.routine.slater as rs
+        for ours, ref, name in patch.binding_table():
+            assert ref in rec["modules"] and name in rec["modules"][ref], (ref, name)
+            assert hasattr(importlib.import_module(root + "." + ref), name), (ref, name)
+        lat = importlib.import_module(root + ".system.lattice")
+        for name in patch._LATTICE_METHODS:
+            assert name in rec["Lattice"] and hasattr(lat.Lattice, name), name
         from libdmet_preview_amd.basis_transform import eri_transform as aet
-        assert rs.get_emb_eri is aet.get_emb_eri
+        handle = patch.install(reference_package=root)
+        try:
+            rs = importlib.import_module(root + ".routine.slater")
+            assert rs.get_emb_eri is aet.get_emb_eri
+        finally:
+            patch.uninstall(handle)
+        rs = importlib.import_module(root + ".routine.slater")
+        assert rs.get_emb_eri is not aet.get_emb_eri
     finally:
-        patch.uninstall(handle)
-    import libdmet.routine.slater as rs
-    assert rs.get_emb_eri is not aet.get_emb_eri
+        for k in list(mods):
+            sys.modules.pop(k, None)

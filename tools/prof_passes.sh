@@ -8,8 +8,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 for WL in C5 C4; do
-  if [ $WL = C5 ]; then EXTRA="--scaling weak --kl-per-gpu 14 --no-full-config"; else EXTRA="--workload C4"; fi
-  B="python3 $R/bench.py $EXTRA --no-cpu-baseline --no-parity --steps 1 --warmup 0 --fit-iters 0"
+  if [ $WL = C5 ]; then EXTRA="--scaling weak --kl-per-gpu 14 --no-full-config"; else EXTRA="--scaling strong --workload C4"; fi
+  B="python3 $R/bench.py --full $EXTRA --no-cpu-baseline --no-parity --steps 1 --warmup 0 --fit-iters 0"
   rocprofv3 --kernel-trace --stats -d $O/${WL}_trace -- $B > $O/${WL}_trace.json 2> $O/${WL}_trace.err
   rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/${WL}_fetch -- $B > /dev/null 2> $O/${WL}_fetch.err
   rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/${WL}_write -- $B > /dev/null 2> $O/${WL}_write.err

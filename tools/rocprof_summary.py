@@ -104,7 +104,7 @@ def traffic_json(dbs, out, workload="C5", how=None, steps_profiled=1):
         commit = None
     acc["_collected"] = {"kernel_source_sha": kernel_source_sha(), "commit": commit, "workload": workload,
                          "how": how or ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two passes) -- python3 bench.py "
-                                        "--workload %s ... --steps 1 --warmup 0 --no-parity; tools/rocprof_summary.py --traffic-json"
+                                        "--full --workload %s ... --steps 1 --warmup 0 --no-parity; tools/rocprof_summary.py --traffic-json"
                                         % workload)}
     doc = {"workloads": {}}
     if os.path.exists(out):
