@@ -179,6 +179,21 @@ int dmk_eigh_batched_real(dmk_ctx *ctx, int n, int batch, const double *A, doubl
  * 0 when the refinement was accepted.  DMK_ERR_NOCONV for NaN / Inf input. */
 int dmk_eigh_jacobi_real(dmk_ctx *ctx, int n, int batch, const double *A, const double *V0, double *w, double *Vt,
                          int *sweeps_out);
+/* Large real symmetric matrices, ONE matrix spread over the whole GPU (csrc/eigh_large.hip): Householder tridiagonalisation with
+ * one kernel boundary per dependency, bisection for every eigenvalue, inverse iteration + cluster re-orthogonalisation for the
+ * SELECTED eigenvectors only, compact-WY back-transformation on the matrix cores.  Replaces scipy.linalg.eigh of the env-env block
+ * (routine/slater.py:278, routine/spinless.py:166-275) and of the full lattice (bath_opt, routine/spinless.py:274-349) where the
+ * dimension exceeds what one workgroup holds; dmk_eigh_batched_real routes n > 2000 here (all vectors, one matrix after another).
+ * Any n >= 2.  Results are bit-reproducible (no atomics).  The handle owns the working copy (8 n^2 bytes); when the device cannot
+ * hold the workspace the calls return DMK_ERR_INVALID with the bytes needed in the message.  NaN / Inf input, or an eigenvector that
+ * still fails |T z - lam z| <= 64 n eps |T| or the orthogonality test of its cluster after the repair pass: DMK_ERR_NOCONV. */
+typedef struct dmk_eighl dmk_eighl;
+/* tridiagonalise a copy of A (device, n x n, leading dimension lda, lower triangle referenced; A is not modified)
+ * and compute ALL n eigenvalues, ascending, into w (device, n).  Synchronises. */
+int dmk_eighl_factor(dmk_ctx *ctx, int n, const double *A, int64_t lda, double *w, dmk_eighl **out);
+/* eigenvectors of the eigenvalues w[idx[0..m)] (host int32, strictly ascending): Vt device m x n, ROW j = eigenvector of w[idx[j]] */
+int dmk_eighl_vectors(dmk_eighl *h, int m, const int32_t *idx_host, double *Vt);
+int dmk_eighl_free(dmk_eighl *h);
 int dmk_occ_density(dmk_ctx *ctx, int n, int batch, const void *Vt, const double *occ,
                     void *rho /* c128 batch x n x n */);
 /* a4: chemical potential and occupation numbers of `n` levels `ew` (device, any order; all spins and k-points of one
@@ -217,6 +232,12 @@ int dmk_bath_svd(dmk_ctx *ctx, const int mesh[3], int nlo, const double *rdm1,
  * rdm1 + b * rdm1_stride; sigma batch x nb; U batch x nenv x nb): one chain of launches for all of them. */
 int dmk_bath_svd_batched(dmk_ctx *ctx, const int mesh[3], int nlo, int batch, const double *rdm1, int64_t rdm1_stride,
                          const int32_t *env_idx, int nenv, const int32_t *bath_col, int nb, double *sigma, double *U);
+/* A block of the expanded density without expanding it: out[a][b] = stripe[R(row_a) - R(col_b)][p(row_a)][p(col_b)] for global site
+ * indices row_idx (nrow) / col_idx (ncol) (device int32; site = cell * nlo + orbital), stripe: ncells x nlo x nlo f64 (device), out:
+ * nrow x ncol f64.  Cell subtraction as dmk_cell_add_table(sign = -1), done on the device.  Replaces
+ * lattice.expand(rdm1)[rows][:, cols] (system/lattice.py expand, routine/slater.py:262-266). */
+int dmk_stripe_gather(dmk_ctx *ctx, const int mesh[3], int nlo, const double *stripe, int nrow, const int32_t *row_idx, int ncol,
+                      const int32_t *col_idx, double *out);
 /* B = U[:, :nbath]; if orth: B[virt_mask] = 0; B = B (B^T B)^{-1/2} (eigenvalues
  * <= 1e-14 dropped); then basis[imp_idx, :nimp] = I and
  * basis[env_idx, nimp:nimp+nbath] = B, basis: (ncells*nlo) x ncol_basis f64 (zeroed here). */

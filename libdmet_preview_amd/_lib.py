@@ -58,6 +58,10 @@ PROTOTYPES = {
     "dmk_fold_k2R_complex": (c_int, [c_vp, _int3, c_i64, c_int, c_vp, c_vp]),
     "dmk_eigh_batched": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "dmk_eigh_batched_real": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    "dmk_eighl_factor": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, P(c_vp)]),
+    "dmk_eighl_vectors": (c_int, [c_vp, c_int, c_vp, c_vp]),
+    "dmk_eighl_free": (c_int, [c_vp]),
+    "dmk_stripe_gather": (c_int, [c_vp, _int3, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
     "dmk_eigh_jacobi_real": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, P(c_int)]),
     "dmk_occ_density": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     "dmk_assign_occ": (c_int, [c_vp, c_i64, c_vp, c_dbl, c_dbl, c_dbl, c_int, c_dbl, c_dbl, c_vp, P(c_dbl)]),

@@ -886,6 +886,21 @@ int dmk_bath_svd_batched(dmk_ctx *ctx, const int mesh[3], int nlo, int batch, co
     return DMK_OK;
 }
 
+int dmk_stripe_gather(dmk_ctx *ctx, const int mesh[3], int nlo, const double *stripe, int nrow, const int32_t *row_idx, int ncol,
+                      const int32_t *col_idx, double *out) {
+    if (!ctx) return DMK_ERR_INVALID;
+    if (!mesh || mesh[0] <= 0 || mesh[1] <= 0 || mesh[2] <= 0 || nlo <= 0 || nrow < 0 || ncol < 0 || !stripe || !row_idx || !col_idx || !out)
+        return dmk_fail(ctx, DMK_ERR_INVALID, "stripe_gather: bad arguments");
+    if (nrow == 0 || ncol == 0) return DMK_OK;
+    FamScope fs(ctx, DMK_FAM_BATH);
+    const long long total = (long long)nrow * ncol;
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(gather_env_imp_kernel, dim3(blocks), dim3(256), 0, ctx->stream, mesh[0], mesh[1], mesh[2], nlo, stripe, row_idx,
+                       nrow, col_idx, ncol, out, 0LL, 0LL);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
 int dmk_bath_svd(dmk_ctx *ctx, const int mesh[3], int nlo, const double *rdm1, const int32_t *env_idx, int nenv,
                  const int32_t *bath_col, int nb, double *sigma, double *U) {
     if (!ctx) return DMK_ERR_INVALID;

@@ -19,6 +19,7 @@
 // Bound: latency / L2: algorithmic HBM traffic is
 // 2*16*n^2 + 8*n bytes per matrix.
 #include "common.h"
+#include "tridiag_bisect.h"
 
 namespace {
 
@@ -456,39 +457,8 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
                 continue;
             }
             const double tn = bnorm[j];
-            // ---- (b) bisection: Gershgorin interval, count(x) = number of eigenvalues below x
-            double emax2 = 0.0, lo = dl[s0], hi = dl[s0];
-            for (int i = s0; i < t0; ++i) {
-                const double rad = (i > s0 ? fabs(el[i - 1]) : 0.0) + (i + 1 < t0 ? fabs(el[i]) : 0.0);
-                lo = fmin(lo, dl[i] - rad);
-                hi = fmax(hi, dl[i] + rad);
-                if (i + 1 < t0) emax2 = fmax(emax2, el[i] * el[i]);
-            }
-            const double pivmin = 2.2250738585072014e-308 * fmax(1.0, emax2);
-            lo -= 2.0 * eps * tn * m + 2.0 * pivmin;
-            hi += 2.0 * eps * tn * m + 2.0 * pivmin;
-            for (int it = 0; it < 200; ++it) {
-                const double mid = 0.5 * (lo + hi);
-                if (!(mid > lo && mid < hi)) break;
-                int cnt = 0;
-                double q = dl[s0] - mid;
-                if (fabs(q) < pivmin) q = -pivmin;
-                cnt += q < 0.0 ? 1 : 0;
-#pragma unroll 4
-                for (int i = s0 + 1; i < t0; ++i) {
-                    // 1 / q from v_rcp_f64 and two Newton steps (the count only needs the SIGN of the pivots to be right
-                    // up to perturbations of a few ulp of |T|, which is the accuracy bisection delivers anyway)
-                    double r = __builtin_amdgcn_rcp(q);
-                    r = r * (2.0 - q * r);
-                    r = r * (2.0 - q * r);
-                    q = (dl[i] - mid) - e2[i - 1] * r;
-                    if (fabs(q) < pivmin) q = -pivmin;
-                    cnt += q < 0.0 ? 1 : 0;
-                }
-                if (cnt > kk) hi = mid; else lo = mid;
-                if (hi - lo <= eps * (fabs(lo) + fabs(hi)) + 2.0 * pivmin) break;
-            }
-            const double lm = 0.5 * (lo + hi);
+            // ---- (b) bisection on the Sturm count over the block's Gershgorin interval (tridiag_bisect.h)
+            const double lm = dmk_bisect_eigenvalue(dl, el, e2, s0, t0, kk, tn);
             lam[j] = lm;
             inv_factor(j, lm);
             inv_seed(j, 0ull);
@@ -727,13 +697,23 @@ int launch_backtransform(dmk_ctx *ctx, int n, int batch, const double *Zt, const
                          void *Tws);
 int launch_tri_eigpairs(dmk_ctx *ctx, int n, int batch, const double *d, const double *e, double *Zt, double *w, int *rank_out,
                         int *flags, int inject);
+int launch_eigh_large_all(dmk_ctx *ctx, int n, const double *A, double *w, double *Vt);      // eigh_large.hip
 namespace {
 
 int launch_eigh(dmk_ctx *ctx, int n, int batch, const void *A, int a_real, const double *add, int add_group, double *w,
                 void *Vt, int v_real) {
     if (n <= 0 || batch <= 0) return DMK_OK;
-    // one workgroup per matrix: the LDS carve (80 n bytes) and the per-lane column slices (64 R columns) bound n
-    if (n > 2000) return dmk_fail(ctx, DMK_ERR_INVALID, "eigh: n = %d exceeds the supported maximum of 2000", n);
+    // one workgroup per matrix: the LDS carve (80 n bytes) and the per-lane column slices (64 R columns) bound n; larger real
+    // matrices go one after another through the many-workgroup solver (eigh_large.hip)
+    if (n > 2000 && a_real && v_real && !add) {
+        for (int b = 0; b < batch; ++b) {
+            const int rc = launch_eigh_large_all(ctx, n, reinterpret_cast<const double *>(A) + (size_t)b * n * n, w + (size_t)b * n,
+                                                 reinterpret_cast<double *>(Vt) + (size_t)b * n * n);
+            if (rc) return rc;
+        }
+        return DMK_OK;
+    }
+    if (n > 2000) return dmk_fail(ctx, DMK_ERR_INVALID, "eigh: complex n = %d exceeds the supported maximum of 2000", n);
     const size_t nn = (size_t)n * n;
     const size_t per = nn * (16 + 16 + 8 + 56) + (size_t)n * (8 + 8 + 16 + 8);
     const size_t total = per * batch + 256 + (size_t)batch * sizeof(int) + 256;

@@ -131,6 +131,37 @@ def bath_assemble_dev(ctx, d_U, nenv, nb, nbath, d_virt, orth, d_env, d_imp, nim
     return d_basis
 
 
+# environment / lattice dimension above which the eigenvalue-flavoured baths use the many-workgroup eigensolver
+# (csrc/eigh_large.hip); up to it, one workgroup per matrix (csrc/eigh.hip, whose limit this is)
+EIGH_LARGE_MIN = 2000
+
+
+def stripe_gather_dev(ctx, kmesh, nlo, d_stripe, d_rows, d_cols, d_out):
+    """d_out (nrow, ncol) = expand(stripe)[rows][:, cols] by index arithmetic on the device (dmk_stripe_gather)."""
+    ctx.check(lib.dmk_stripe_gather(ctx.h, mesh3(kmesh), int(nlo), d_stripe.ptr, int(d_rows.size), d_rows.ptr, int(d_cols.size),
+                                    d_cols.ptr, d_out.ptr))
+    return d_out
+
+
+def eigh_large_selected(ctx, d_A, n, select):
+    """Selected eigenpairs of the real symmetric device matrix d_A (n x n, lower triangle referenced, left unchanged): every
+    eigenvalue `ew` (host, ascending), then the eigenvectors of the indices `select(ew)` returns (ascending) as the ROWS of a device
+    array (max(m, 1), n).  The host applies its comparisons to the very doubles the device computed -- the reference's
+    `abs(e) > tol and abs(1 - e) > tol` (slater.py:283-287) or `ev[:, -nemb:]` (spinless.py:306) -- and the device computes
+    exactly those vectors.  Returns (ew, idx, d_Vt)."""
+    h = C.c_void_p()
+    d_w = ctx.empty((n,), np.float64)
+    ctx.check(lib.dmk_eighl_factor(ctx.h, int(n), d_A.ptr, int(n), d_w.ptr, C.byref(h)))
+    try:
+        ew = d_w.get()
+        idx = np.ascontiguousarray(select(ew), dtype=np.int32)
+        d_Vt = ctx.empty((max(len(idx), 1), n), np.float64)
+        ctx.check(lib.dmk_eighl_vectors(h, int(len(idx)), idx.ctypes.data_as(C.c_void_p), d_Vt.ptr))
+    finally:
+        lib.dmk_eighl_free(h)
+    return ew, idx, d_Vt
+
+
 def _get_emb_basis_svd(lattice, rdm1, **kwargs):
     imp_idx = kwargs.get("imp_idx", lattice.imp_idx)
     val_idx = kwargs.get("val_idx", lattice.val_idx)
@@ -189,8 +220,9 @@ def _get_emb_basis_svd(lattice, rdm1, **kwargs):
 
 
 def _get_emb_basis_eig(lattice, rdm1, **kwargs):
-    """Eigen-decomposition of the env-env block (slater.py:224-318); model-size systems
-    (needs the expanded (ncells*nlo)^2 matrix like the reference)."""
+    """Eigen-decomposition of the env-env block (slater.py:224-318).  Up to EIGH_LARGE_MIN environment orbitals the block is cut
+    from the expanded matrix on the host and goes through the one-workgroup solver; above, it is gathered on the device from
+    the stripe (dmk_stripe_gather) and only the eigenvectors the reference's comparison keeps are computed (eigh_large_selected)."""
     imp_idx = kwargs.get("imp_idx", lattice.imp_idx)
     val_idx = kwargs.get("val_idx", lattice.val_idx)
     valence_bath = kwargs.get("valence_bath", True)
@@ -204,19 +236,27 @@ def _get_emb_basis_eig(lattice, rdm1, **kwargs):
     if rdm1.ndim == 3:
         rdm1 = rdm1[np.newaxis]
     spin = rdm1.shape[0]
-    if nenv > 2000:
-        raise NotImplementedError("eig bath: env dimension %d exceeds the eigensolver limit of 2000 (one workgroup per matrix); "
-                                  "use the SVD flavour (kind='svd', the reference's default), which has no limit" % nenv)
-    env_env = lattice.expand(rdm1)[:, env_idx][:, :, env_idx]
     ctx = get_ctx()
-    d_A = ctx.to_device(env_env, np.float64)
-    d_w = ctx.empty((spin, nenv), np.float64)
-    d_Vt = ctx.empty((spin, nenv, nenv), np.float64)
-    ctx.check(lib.dmk_eigh_batched_real(ctx.h, nenv, spin, d_A.ptr, d_w.ptr, d_Vt.ptr))
-    ew, Vt = d_w.get(), d_Vt.get()
-    keep = [[i for i, e in enumerate(ew[s]) if abs(e) > tol_bath and abs(1 - e) > tol_bath] for s in range(spin)]
-    nb = len(keep[0])
-    if any(len(k) != nb for k in keep):
+    select = lambda ew: [i for i, e in enumerate(ew) if abs(e) > tol_bath and abs(1 - e) > tol_bath]       # noqa: E731
+    if nenv > EIGH_LARGE_MIN:
+        d_rdm1 = ctx.to_device(rdm1, np.float64)
+        d_env = ctx.to_device(env_idx, np.int32)
+        d_A = ctx.empty((nenv, nenv), np.float64)
+        kept = []
+        for s in range(spin):
+            stripe_gather_dev(ctx, lattice.kmesh, nlo, d_rdm1.offset(s * ncells * nlo * nlo, (ncells, nlo, nlo)), d_env, d_env, d_A)
+            _, idx, d_sel = eigh_large_selected(ctx, d_A, nenv, select)
+            kept.append(d_sel.get()[:len(idx)])
+    else:
+        env_env = lattice.expand(rdm1)[:, env_idx][:, :, env_idx]
+        d_A = ctx.to_device(env_env, np.float64)
+        d_w = ctx.empty((spin, nenv), np.float64)
+        d_Vt = ctx.empty((spin, nenv, nenv), np.float64)
+        ctx.check(lib.dmk_eigh_batched_real(ctx.h, nenv, spin, d_A.ptr, d_w.ptr, d_Vt.ptr))
+        ew, Vt = d_w.get(), d_Vt.get()
+        kept = [Vt[s][select(ew[s])] for s in range(spin)]
+    nb = len(kept[0])
+    if any(len(k) != nb for k in kept):
         raise ValueError("eig bath: spin sectors give different numbers of bath orbitals")
     nsites = ncells * nlo
     basis = np.zeros((spin, nsites, nimp + nb))
@@ -227,7 +267,7 @@ def _get_emb_basis_eig(lattice, rdm1, **kwargs):
         if nb == 0:
             basis[s, imp_idx, :nimp] = np.eye(nimp)
             continue
-        U = np.ascontiguousarray(Vt[s][keep[s]].T)          # (nenv, nb) columns = kept eigenvectors
+        U = np.ascontiguousarray(kept[s].T)                 # (nenv, nb) columns = kept eigenvectors
         d_U = ctx.to_device(U, np.float64)
         d_basis = ctx.empty((nsites, nimp + nb), np.float64)
         bath_assemble_dev(ctx, d_U, nenv, nb, nb, d_virt, orth, d_env, d_imp, nimp, nsites, nimp + nb, d_basis)

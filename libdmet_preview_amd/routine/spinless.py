@@ -10,8 +10,11 @@ The GSO ERI twin is basis_transform.eri_transform.get_emb_eri_gso.
 import numpy as np
 
 from libdmet_preview_amd._lib import lib, get_ctx
-from libdmet_preview_amd.routine.slater import bath_svd_dev, bath_assemble_dev
+from libdmet_preview_amd.routine.slater import bath_svd_dev, bath_assemble_dev, stripe_gather_dev, eigh_large_selected
 from libdmet_preview_amd.utils import logger as log
+
+# dimension above which the eig bath and bath_opt use the many-workgroup eigensolver (csrc/eigh_large.hip); see routine/slater.py
+EIGH_LARGE_MIN = 2000
 
 
 def separate_basis(basis, copy=False):
@@ -43,17 +46,21 @@ def get_emb_basis_opt(latt, rdm1_R, basis, keep_imp_identity=False, tol=1e-6):
     of the top nemb eigenvectors of  B B^T - mu D  (D = the full-lattice density matrix) with mu from a bracketed root search
     on [-1, 0] / [0, 1] -- scipy's brentq with the reference's tolerances, as there, so the iterates are the reference's.
     Every evaluation is device work: the shifted matrix (two axpys), ONE real symmetric eigenproblem of the full lattice
-    dimension (dmk_eigh_batched_real, one workgroup; ncells * nso <= 2000) and the electron count  tr(E D E^T)  (two GEMMs);
-    the host only sees the scalar."""
+    dimension and the electron count  tr(E D E^T)  (two GEMMs); the host only sees the scalar.  Up to EIGH_LARGE_MIN lattice
+    orbitals the eigenproblem is dmk_eigh_batched_real (one workgroup, all vectors); above, D is gathered on the device from the
+    stripe and every evaluation factors the shifted matrix with the many-workgroup solver and takes the top nemb vectors only."""
     from scipy import optimize as opt
     rdm1_R = np.ascontiguousarray(np.asarray(rdm1_R).real, dtype=np.float64)
     basis = np.ascontiguousarray(basis, dtype=np.float64)
     ncells, nso, nemb = basis.shape
     N = ncells * nso
-    if N > 2000:
-        raise NotImplementedError("bath_opt: the lattice dimension %d exceeds the eigensolver limit of 2000 (one workgroup per matrix)" % N)
+    large = N > EIGH_LARGE_MIN
     ctx = get_ctx()
-    d_D = ctx.to_device(latt.expand(rdm1_R), np.float64)
+    if large:
+        d_all = ctx.to_device(np.arange(N, dtype=np.int32))
+        d_D = stripe_gather_dev(ctx, latt.kmesh, nso, ctx.to_device(rdm1_R), d_all, d_all, ctx.empty((N, N), np.float64))
+    else:
+        d_D = ctx.to_device(latt.expand(rdm1_R), np.float64)
     d_Bt = ctx.to_device(np.ascontiguousarray(basis.reshape(N, nemb).T), np.float64)     # rows = basis vectors
     d_G, d_n = ctx.empty((nemb, N), np.float64), ctx.empty((1,), np.float64)
 
@@ -72,13 +79,17 @@ def get_emb_basis_opt(latt, rdm1_R, basis, keep_imp_identity=False, tol=1e-6):
 
     d_P = ctx.empty((N, N), np.float64)
     ctx.check(lib.dmk_dgemm_batched(ctx.h, 1, 0, N, N, nemb, 1, 1.0, d_Bt.ptr, N, 0, d_Bt.ptr, N, 0, 0.0, d_P.ptr, N, 0))
-    d_M, d_w, d_Vt = ctx.empty((N, N), np.float64), ctx.empty((1, N), np.float64), ctx.empty((1, N, N), np.float64)
+    d_M = ctx.empty((N, N), np.float64)
+    if not large:
+        d_w, d_Vt = ctx.empty((1, N), np.float64), ctx.empty((1, N, N), np.float64)
 
     def top(mu):
         """rows N - nemb .. N of Vt: the eigenvectors of the nemb largest eigenvalues, ascending (ev[:, -nemb:], :306)."""
         d_M.zero_()
         ctx.check(lib.dmk_axpy_f64(ctx.h, N * N, 1.0, d_P.ptr, d_M.ptr))
         ctx.check(lib.dmk_axpy_f64(ctx.h, N * N, -float(mu), d_D.ptr, d_M.ptr))
+        if large:
+            return eigh_large_selected(ctx, d_M, N, lambda ew: np.arange(N - nemb, N))[2]
         ctx.check(lib.dmk_eigh_batched_real(ctx.h, N, 1, d_M.ptr, d_w.ptr, d_Vt.ptr))
         return d_Vt.offset((N - nemb) * N, (nemb, N))
 
@@ -163,8 +174,9 @@ def _order_by_particle_character(ctx, d_basis, ncells, nso, nlo, nimp, nbath):
 def _get_emb_basis_eig(lattice, rdm1, **kwargs):
     """GSO bath from the eigenvectors of the env-env block of the generalised density matrix whose eigenvalues are neither 0
     nor 1 (routine/spinless.py:166-275): one real symmetric eigenproblem of the environment dimension on the device
-    (dmk_eigh_batched_real: model sizes, one workgroup per matrix), then the virtual projection + Loewdin + scatter of the SVD
-    flavour (dmk_bath_assemble) and the particle-character ordering."""
+    (up to EIGH_LARGE_MIN environment orbitals dmk_eigh_batched_real, one workgroup, on the block cut from the expanded matrix;
+    above, the block is gathered on the device and only the kept eigenvectors are computed, eigh_large_selected), then the
+    virtual projection + Loewdin + scatter of the SVD flavour (dmk_bath_assemble) and the particle-character ordering."""
     valence_bath = kwargs.get("valence_bath", True)
     tol_bath = kwargs.get("tol_bath", 1e-9)
     if not kwargs.get("orth", True):
@@ -176,16 +188,21 @@ def _get_emb_basis_eig(lattice, rdm1, **kwargs):
     nimp, nenv = len(imp_idx), len(env_idx)
     rdm1 = np.ascontiguousarray(rdm1, dtype=np.float64)
     assert rdm1.shape == (ncells, nso, nso)
-    if nenv > 2000:
-        raise NotImplementedError("eig bath: env dimension %d exceeds the eigensolver limit of 2000 (one workgroup per matrix); "
-                                  "use kind='svd' (the reference's default), which has no limit" % nenv)
-    env_env = lattice.expand(rdm1)[env_idx][:, env_idx]
     ctx = get_ctx()
-    d_w, d_Vt = ctx.empty((1, nenv), np.float64), ctx.empty((1, nenv, nenv), np.float64)
-    d_A = ctx.to_device(env_env, np.float64)                # (named: alive until the read-back below)
-    ctx.check(lib.dmk_eigh_batched_real(ctx.h, nenv, 1, d_A.ptr, d_w.ptr, d_Vt.ptr))
-    ew, Vt = d_w.get().reshape(nenv), d_Vt.get().reshape(nenv, nenv)
-    keep = [i for i, e in enumerate(ew) if abs(e) > tol_bath and abs(1 - e) > tol_bath]
+    select = lambda ew: [i for i, e in enumerate(ew) if abs(e) > tol_bath and abs(1 - e) > tol_bath]       # noqa: E731
+    if nenv > EIGH_LARGE_MIN:
+        d_envA = ctx.to_device(env_idx)
+        d_A = stripe_gather_dev(ctx, lattice.kmesh, nso, ctx.to_device(rdm1), d_envA, d_envA, ctx.empty((nenv, nenv), np.float64))
+        ew, keep, d_sel = eigh_large_selected(ctx, d_A, nenv, select)
+        kept = d_sel.get()[:len(keep)]
+    else:
+        env_env = lattice.expand(rdm1)[env_idx][:, env_idx]
+        d_w, d_Vt = ctx.empty((1, nenv), np.float64), ctx.empty((1, nenv, nenv), np.float64)
+        d_A = ctx.to_device(env_env, np.float64)                # (named: alive until the read-back below)
+        ctx.check(lib.dmk_eigh_batched_real(ctx.h, nenv, 1, d_A.ptr, d_w.ptr, d_Vt.ptr))
+        ew, Vt = d_w.get().reshape(nenv), d_Vt.get().reshape(nenv, nenv)
+        keep = select(ew)
+        kept = Vt[keep]
     log.debug(0, "dm eigenvalues:\n%s", ew[keep])
     nbath = len(keep)
     log.eassert(nbath % 2 == 0, "nbath (%s) should be even in GSO.", nbath)
@@ -193,7 +210,7 @@ def _get_emb_basis_eig(lattice, rdm1, **kwargs):
     d_env, d_virt = ctx.to_device(env_idx), ctx.to_device(virt_mask)
     d_imp = ctx.to_device(np.asarray(imp_idx, dtype=np.int32))
     d_basis = ctx.empty((ncells * nso, ncol), np.float64)
-    d_U = ctx.to_device(np.ascontiguousarray(Vt[keep].T) if nbath else np.zeros((nenv, 1)), np.float64)
+    d_U = ctx.to_device(np.ascontiguousarray(kept.T) if nbath else np.zeros((nenv, 1)), np.float64)
     bath_assemble_dev(ctx, d_U, nenv, max(nbath, 1), nbath, d_virt, True, d_env, d_imp, nimp, ncells * nso, ncol, d_basis)
     if loc_method is not None:
         _localize_assembled(ctx, lattice, d_basis, env_idx, nimp, nbath, loc_method)
