@@ -348,6 +348,31 @@ int dmk_eri_stack(dmk_eri *h, int nslots_wanted, int *nslots_granted);
  * (eri_transform.py:453-455), so its blocks run a real-part-only step 2, 2/3 of the matrix work; dmk_eri_end_kL must then be given
  * the same weight.  After such a kL the Im half of what dmk_eri_planes returns is zero.  DMK_ERI_RE_ONLY=0 switches it off.) */
 int dmk_eri_begin_kL_weighted(dmk_eri *h, int kL, int weight);
+/* Iteration-invariant step-2 planes.  The embedding basis is [impurity | bath], so the leading columns of C_ao_emb do not change
+ * over a DMET run, and neither does the DF tensor: every plane entry S[L][a][b] whose pair the nemb = 256 step-2 kernel gives to
+ * its workgroup types 0 and 2 (all with a < 192: the prefix [0, 8256) of the packed pair index and, for a in [128,192), the 128
+ * entries from a (a + 1) / 2) comes out the same in every call.  A dmk_eri_cache, owned by the caller and outliving the
+ * pipelines, keeps that region of the finished planes per kL; a later pipeline copies it back and launches the other two
+ * workgroup types only -- half of step 2's block products.
+ *   dmk_eri_cache_create : `budget_bytes` is additionally capped at a quarter of the free device memory; the cache never evicts.
+ *   dmk_eri_attach_cache : accepted (*attached = 1) only for the grouped nemb = 256 path with time reversal, without the
+ *       imaginary-part accumulator and without sub-plane copies; otherwise *attached = 0 and the pipeline behaves as without a
+ *       cache.  Columns [0,192) of the pipeline's C_ao_emb are compared BITWISE on the device with the copy the entries were built
+ *       from, and the shape (mesh, nao, naux, nemb, spin) likewise: any difference drops every entry and stores the new columns.
+ *       Call it before the first kL, after dmk_eri_begin.
+ *   dmk_eri_begin_kL_cached : dmk_eri_begin_kL_weighted plus `key64`, the caller's fingerprint of everything else the planes of
+ *       this kL depend on (the DF tensor, the blocks it is about to push and their order).  An entry for (kL, key64, Re-only
+ *       flag) makes the kL warm; without one it runs as before and dmk_eri_end_kL stores its region if the budget holds it.
+ *       Without an attached cache it is dmk_eri_begin_kL_weighted.
+ *   dmk_eri_cache_stats  : hits, misses, entries, bytes held, entries dropped.
+ *   dmk_eri_cache_drop   : forget every entry and the stored columns.   dmk_eri_cache_destroy frees everything. */
+typedef struct dmk_eri_cache dmk_eri_cache;
+int dmk_eri_cache_create(dmk_ctx *ctx, int64_t budget_bytes, dmk_eri_cache **out);
+int dmk_eri_cache_destroy(dmk_eri_cache *cache);
+int dmk_eri_cache_drop(dmk_eri_cache *cache);
+int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]);
+int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached);
+int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64);
 /* Contract what is resident, restricted to the band [band_lo, band_hi) of 128-row tiles of the pair index (-1, -1: all;
  * dmk_eri_bands gives their number).  Bands must be issued in increasing order; after band b the ROWS of band b of every
  * spin block are complete, so a kL-sharded job can reduce them over its ranks while later bands are still being computed

@@ -22,6 +22,8 @@ path of an HDF5 file, or an open container) and no provider methods -- is adapte
 eri_transform.py:260-261.
 """
 import ctypes as C
+import hashlib
+import itertools
 import os
 import numpy as np
 
@@ -42,7 +44,9 @@ ERI_SLICE = 2000
 # ---------------------------------------------------------------------------------------------
 
 class GDFMemory(object):
-    """In-memory DF tensor: blocks[(i, j)] / blocks[i, j] / blocks(i, j) -> (naux, nao, nao) complex."""
+    """In-memory DF tensor: blocks[(i, j)] / blocks[i, j] / blocks(i, j) -> (naux, nao, nao) complex.
+    The host arrays (or the callable) may change between calls, so it has no `df_token`: transforms fed from it never use the
+    invariant-plane cache (EriInvariantCache) and always run the dense step 2."""
     def __init__(self, kpts, blocks, naux=None, cell=None):
         self.kpts = np.asarray(kpts)
         self.blocks = blocks
@@ -110,7 +114,9 @@ class CderiProvider(object):
     _load3c, :1312-1396 transform_gdf_to_lo): "j3c-kptij" (npairs, 2, 3) absolute k-point pairs (only i >= j stored),
     "j3c/<pair>/<segment>" with shape (naux_seg, nao*nao), or (naux_seg, nao*(nao+1)/2) lower-triangular packed when
     ki == kj (real at Gamma).  A pair stored as (kj, ki) is served conjugate-transposed.  An open h5py.File works as
-    is; on a box without h5py the same layout in a dict (or np.load of an .npz with "/"-joined keys) does."""
+    is; on a box without h5py the same layout in a dict (or np.load of an .npz with "/"-joined keys) does.
+    The container can be rewritten behind the provider's back, so it has no `df_token` (no invariant-plane caching,
+    EriInvariantCache); wrapped in a GDFResident its blocks are fixed in device memory and the wrapper's token applies."""
 
     def __init__(self, feri, kpts, nao, cell=None, tol=KPT_DIFF_TOL):
         self.feri, self.kpts, self.nao, self.cell = feri, np.asarray(kpts), int(nao), cell
@@ -304,6 +310,11 @@ class GDFPhilox(object):
         self.cell = cell
         self._cderi = "philox"
 
+    def df_token(self):
+        """What the generated tensor is a function of: the blocks behind equal tokens are bit-identical (EriInvariantCache key)."""
+        kh = hashlib.blake2b(np.ascontiguousarray(self.kpts, dtype=np.float64).tobytes(), digest_size=8).hexdigest()
+        return ("philox", self.seed, self.naux, self.nao, kh)
+
     def load_block(self, ctx, i, j, out_dev):
         ctx.check(lib.dmk_df_block_philox(ctx.h, C.c_uint64(self.seed), int(i), int(j), self.naux, self.nao,
                                           out_dev.ptr))
@@ -374,6 +385,9 @@ def convert_eri_to_gdf(eri, norb, fname=None, tol=1e-8):
     return fname
 
 
+_resident_uid = itertools.count(1)
+
+
 class GDFResident(object):
     """The AO DF blocks a kL shard reads, RESIDENT in device memory in the order the pipeline consumes them (one contiguous
     array: kL by kL, records in plan order).  The reference reads every (ki, kj) block from the cderi file once per get_emb_eri
@@ -388,6 +402,7 @@ class GDFResident(object):
         """`max_bytes`: hold only the leading kL of the shard that fit (PARTIAL residency: the rest is still read from `provider`
         on every transform -- for a host-fed tensor larger than HBM every resident block is one PCIe transfer less per iteration)."""
         self.ctx, self.provider = ctx, provider
+        self._uid, self._freed = next(_resident_uid), 0
         self.kpts = getattr(provider, "kpts", None)
         self.nao, self.naux = int(nao), int(naux)
         weights, records = eri_plan(list(kmesh), bool(t_reversal_symm)) if plan is None else plan
@@ -468,22 +483,32 @@ class GDFResident(object):
     def get_naoaux(self):
         return self.naux
 
+    def df_token(self):
+        """The source's token when it has one, else an id unique to this object (the blocks held here do not change whatever
+        happens to the source), plus a counter that `free()` bumps."""
+        src = getattr(self.provider, "df_token", None)
+        return ("resident", src() if src is not None else ("object", self._uid), self._freed)
+
     def load_block(self, ctx, ki, kj, out):                 # (the ring path of a caller that does not know about group_ptr)
         return self.provider.load_block(ctx, ki, kj, out)
 
     def __getattr__(self, name):
         # everything else a driver may ask of a DF provider (get_block, blockdim, max_memory, cell, ...) is the source's
         prov = self.__dict__.get("provider")
-        if prov is None or name.startswith("__") or name in ("load_block_host", "load_blocks_on", "load_block_on", "close"):
+        if prov is None or name.startswith("__") or name in ("load_block_host", "load_blocks_on", "load_block_on", "close", "df_token"):
             raise AttributeError(name)
         return getattr(prov, name)
 
     def free(self):
+        self._freed += 1
         self.buf.free()
 
     def close(self):
         """Give the device memory back and close what make_df_resident opened."""
         self.free()
+        inv = self.__dict__.pop("inv_cache", None)      # invariant planes kept next to the resident blocks (get_emb_eri_fast_gdf)
+        if inv is not None:
+            inv.close()
         opened = getattr(self, "_opened", None)
         if opened is not None and hasattr(opened, "close"):
             opened.close()
@@ -886,13 +911,71 @@ def eri_restore(eri, symmetry, nemb):
 # device-resident driver
 # ---------------------------------------------------------------------------------------------
 
+def inv_key64(df_token, kL, weight, records):
+    """64-bit fingerprint of the work of one kL for the invariant-plane cache: the DF token, kL, its weight and the ordered
+    records about to be pushed.  blake2b of a canonical text form: stable across processes and Python versions."""
+    recs = tuple(tuple(int(x) for x in r) for r in records)
+    text = repr((_canon(df_token), int(kL), int(weight), recs)).encode()
+    return int.from_bytes(hashlib.blake2b(text, digest_size=8).digest(), "little")
+
+
+def _canon(t):
+    if isinstance(t, (tuple, list)):
+        return tuple(_canon(x) for x in t)
+    if isinstance(t, (bool, np.bool_)):
+        return int(t)
+    if isinstance(t, (int, np.integer)):
+        return int(t)
+    return str(t)
+
+
+class EriInvariantCache(object):
+    """Iteration-invariant step-2 planes kept across transforms (dmk_eri_cache): the embedding basis is
+    [impurity | bath], so the leading columns of C_ao_emb and the DF tensor stay the same over a DMET run, and with them the
+    plane entries of every pair the nemb = 256 step-2 kernel gives to its impurity-only workgroups (a < 192).  Pass it to
+    `EriEngine(..., inv_cache=)`: a kL whose entry exists copies that region back and runs half of step 2.  A hit is only ever
+    made legal by the library's bitwise compare of columns [0,192) of C_ao_emb on the device plus the key of the kL (`inv_key64`).
+    `budget_gb`: default DMK_ERI_INV_GB (64), capped by the library at a quarter of the free device memory; never evicts."""
+
+    def __init__(self, ctx, budget_gb=None):
+        if budget_gb is None:
+            budget_gb = float(os.environ.get("DMK_ERI_INV_GB", "64"))
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx.check(lib.dmk_eri_cache_create(ctx.h, int(float(budget_gb) * (1 << 30)), C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        v = (C.c_int64 * 5)()
+        self.ctx.check(lib.dmk_eri_cache_stats(self.h, v))
+        return {"hits": int(v[0]), "misses": int(v[1]), "entries": int(v[2]), "bytes": int(v[3]), "drops": int(v[4])}
+
+    def drop(self):
+        """Forget every entry (and the stored columns)."""
+        self.ctx.check(lib.dmk_eri_cache_drop(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.dmk_eri_cache_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class EriEngine(object):
     """Owns a dmk_eri pipeline: plan -> (begin_kL, push_block*, end_kL)* on one GPU."""
 
     def __init__(self, ctx, kmesh, nao, naux, nemb, spin, C_ao_emb_dev, eri_dev, t_reversal_symm=True, gso=False, plan=None,
-                 track_imag=False, rows_only=False):
+                 track_imag=False, rows_only=False, inv_cache=None):
         """`plan` = (weights, records) of `general_plan` for k lists that are not the np.fft-ordered Gamma-centred mesh
         (then `kmesh` only carries the number of k-points, [nk, 1, 1]); default: the integer-mesh plan of libdmetk.
+        `inv_cache`: an EriInvariantCache; the library attaches it only where the invariant region exists (the grouped
+        nemb = 256 path, time reversal, no GSO, no `track_imag`), `self.inv_attached` tells; kL fed by a provider without a
+        `df_token` run dense all the same.
         `rows_only`: a pipeline WITHOUT an ERI of its own (`eri_dev` may be None): its planes are only ever taken slab-wise
         with `contract_rows_into`; every path that would contract into an internal ERI refuses instead (dmk_eri_begin flag 4).
         `track_imag`: without time reversal also accumulate the imaginary part of the contraction for the reference's
@@ -925,6 +1008,13 @@ class EriEngine(object):
         self.by_kL = {}
         for r in self.records:
             self.by_kL.setdefault(int(r[0]), []).append(r)
+        self.inv_cache, self.inv_attached = None, False
+        if inv_cache is not None and not self.gso and self.tr and not self.track_imag:
+            att = C.c_int(0)
+            ctx.check(lib.dmk_eri_attach_cache(self.h, inv_cache.h, C.byref(att)))
+            self.inv_attached = bool(att.value)
+            if self.inv_attached:
+                self.inv_cache = inv_cache                # (kept alive while the pipeline holds its address)
 
     def irreducible_kL(self):
         return [kL for kL in range(len(self.weights)) if self.weights[kL] > 0]
@@ -998,7 +1088,16 @@ class EriEngine(object):
 
     def run_kL(self, kL, provider, user_of_mesh=None, max_blocks=None):
         ctx = self.ctx
-        if self.nslots > 1 or self.tr:
+        token = getattr(provider, "df_token", None) if self.inv_attached else None
+        if token is not None:
+            # invariant planes: the key covers the DF tensor and exactly the blocks about to be pushed, in order, as the pipeline
+            # (mesh indices) and the provider (its own k indices) will see them
+            cut = self.by_kL[kL] if max_blocks is None else self.by_kL[kL][:int(max_blocks)]
+            key = inv_key64(token(), kL, self.weights[kL],
+                            [(r[1], r[2], r[1] if user_of_mesh is None else user_of_mesh[int(r[1])],
+                              r[2] if user_of_mesh is None else user_of_mesh[int(r[2])], r[4]) for r in cut])
+            ctx.check(lib.dmk_eri_begin_kL_cached(self.h, int(kL), int(self.weights[kL]), C.c_uint64(key)))
+        elif self.nslots > 1 or self.tr:
             # the weight is known here: a kL that is its own time-reversal partner (weight 1) runs the real-part-only step 2
             ctx.check(lib.dmk_eri_begin_kL_weighted(self.h, int(kL), int(self.weights[kL])))
         else:
@@ -1276,6 +1375,9 @@ def get_emb_eri_fast_gdf(cell, mydf, C_ao_lo=None, basis=None, feri=None, kscale
 # k-mesh centre) read them in place.  The copy lives as long as the DF object (weak reference) or until drop_resident().
 RESIDENT_DF = os.environ.get("DMK_DF_RESIDENT", "0") == "1"
 RESIDENT_DF_FRACTION = float(os.environ.get("DMK_DF_RESIDENT_FRACTION", "0.5"))
+# INVARIANT_PLANES (patch.install(invariant_planes=True); off by default): with RESIDENT_DF, an EriInvariantCache is kept next to
+# the cached resident tensor (`res.inv_cache`) and handed to every transform that reads it; drop_resident() frees both.
+INVARIANT_PLANES = False
 _resident_cache = {}
 
 
@@ -1380,8 +1482,14 @@ def _emb_eri_fast_gdf(cell, mydf, C_ao_lo, basis, kscaled_center, symmetry, C_ao
         return _emb_eri_outcore(ctx, cell, mydf, kmesh, plan, C_dev, nao, naux, nemb, spin, fout, use_mpi)
 
     eri_dev = ctx.zeros((spin_pair, npair, npair), np.float64)
+    inv = None
+    if (INVARIANT_PLANES and nemb == 256 and t_reversal_symm and any(r is mydf for _, r in _resident_cache.values())
+            and os.environ.get("DMK_ERI_INV", "1") != "0"):
+        if getattr(mydf, "inv_cache", None) is None:
+            mydf.inv_cache = EriInvariantCache(ctx)
+        inv = mydf.inv_cache
     eng = EriEngine(ctx, kmesh, nao, naux, nemb, spin, C_dev, eri_dev, t_reversal_symm, plan=plan,
-                    track_imag=not t_reversal_symm)
+                    track_imag=not t_reversal_symm, inv_cache=inv)
     try:
         kL_list = None
         dist = None

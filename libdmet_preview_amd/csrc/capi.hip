@@ -719,6 +719,61 @@ int dmk_df_block_philox_on(dmk_ctx *ctx, void *stream, uint64_t seed, int ki, in
 // a11 - a14 : ERI pipeline
 // =============================================================================================
 
+// ---- iteration-invariant step-2 planes (dmk_eri_cache) -----------------------------------------------------------------------
+// The nemb = 256 step-2 kernel (zhot.hip) gives the pairs (a, b) with a < 192 that its workgroup types 0 and 2 own to workgroups of
+// their own: the prefix [0, 8256) of the packed pair index (triangle [0,128)^2) and, for a in [128,192), the 128 entries from
+// a (a + 1) / 2 (rows [128,192) x cols [0,128)).  They are a function of columns [0,192) of C_ao_emb, the DF blocks and the visiting
+// plan alone; a cache entry holds that region of one kL's finished planes, INV_ROW doubles per auxiliary row and plane.
+constexpr int INV_COLS = 192, INV_PREFIX = 8256, INV_ROW = INV_PREFIX + 64 * 128;
+
+struct dmk_eri_cache {
+    dmk_ctx *ctx;
+    size_t budget = 0, held = 0;
+    // what the entries were built from: the shape and columns [0, INV_COLS) of C_ao_emb ([spin nk nao][INV_COLS] c128)
+    bool have_cols = false;
+    int shape[7] = {0, 0, 0, 0, 0, 0, 0};       // mesh, nao, naux, nemb, spin
+    double2 *cols = nullptr;
+    size_t cols_rows = 0;
+    int *flag = nullptr;                         // device: mismatch flag of the column compare
+    struct Entry { int kL; uint64_t key; int re_only; double *buf; size_t bytes; };
+    std::vector<Entry> entries;
+    long long hits = 0, misses = 0, drops = 0;
+    explicit dmk_eri_cache(dmk_ctx *c) : ctx(c) {}
+};
+
+namespace {
+// flag = 1 if any of the 128-bit patterns of columns [0, INV_COLS) of C ([rows][nemb]) differs from cols ([rows][INV_COLS])
+__global__ void inv_cols_compare_kernel(long long n, int nemb, const ulonglong2 *__restrict__ Cm, const ulonglong2 *__restrict__ cols,
+                                        int *__restrict__ flag) {
+    bool diff = false;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const long long row = t / INV_COLS;
+        const int col = (int)(t - row * INV_COLS);
+        const ulonglong2 x = Cm[row * nemb + col], y = cols[t];
+        diff = diff || x.x != y.x || x.y != y.y;
+    }
+    if (diff) *flag = 1;
+}
+
+// The invariant region of the planes of one kL <-> a cache entry.  grid (chunks of INV_ROW, auxiliary row L, spin x plane);
+// entry: [spin][plane][naux][INV_ROW], planes: (ri * pr + L) * pl + a (a + 1) / 2 + b per spin.
+template <bool TO_PLANES>
+__global__ void inv_region_copy_kernel(double *__restrict__ planes, double *__restrict__ entry, long long planes_spin_stride,
+                                       long long pr, long long pl, int naux, int nplanes) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= INV_ROW) return;
+    const int L = blockIdx.y, s = blockIdx.z / nplanes, ri = blockIdx.z - s * nplanes;
+    long long pair = e;
+    if (e >= INV_PREFIX) {
+        const int a = 128 + ((e - INV_PREFIX) >> 7), b = (e - INV_PREFIX) & 127;
+        pair = (long long)a * (a + 1) / 2 + b;
+    }
+    double *p = planes + (long long)s * planes_spin_stride + ((long long)ri * pr + L) * pl + pair;
+    double *q = entry + (((long long)s * nplanes + ri) * naux + L) * INV_ROW + e;
+    if (TO_PLANES) *p = *q; else *q = *p;
+}
+}  // namespace
+
 struct dmk_eri {
     dmk_ctx *ctx;
     Mesh mesh;
@@ -796,6 +851,11 @@ struct dmk_eri {
     const double *probe_x = nullptr;
     double *probe_y = nullptr;
     bool probe_pending = false;      // planes entered the stack since the probe last ran over it
+    // iteration-invariant planes (dmk_eri_attach_cache): inv_warm -- the region of the current kL came from the cache and step 2
+    // runs the two-type grid; inv_save -- a cold kL begun with a key, whose region goes into a new entry when it ends
+    dmk_eri_cache *cache = nullptr;
+    bool inv_warm = false, inv_save = false;
+    uint64_t inv_key = 0;
     dmk_eri(dmk_ctx *c, const int m[3]) : ctx(c), mesh(m) {}
 };
 
@@ -956,6 +1016,61 @@ static int eri_begin_kL_impl(dmk_eri *h, int kL, int weight) {
     h->sub_used = 1;
     h->cur_kL = kL;
     h->slot_reserved = -1;
+    h->inv_warm = h->inv_save = false;
+    return DMK_OK;
+}
+
+static int inv_region_copy(dmk_eri *h, double *entry, bool to_planes) {
+    dmk_ctx *ctx = h->ctx;
+    const int nplanes = h->re_only ? 1 : 2;
+    const dim3 grid((INV_ROW + 255) / 256, (unsigned)h->naux, (unsigned)(h->spin * nplanes));
+    const long long spin_stride = (long long)h->nslots * 2LL * h->pr * h->pl;
+    FamScope fs(ctx, DMK_FAM_MISC);
+    if (to_planes)
+        hipLaunchKernelGGL(inv_region_copy_kernel<true>, grid, dim3(256), 0, ctx->stream, h->slot_planes(h->cur_slot, 0), entry, spin_stride,
+                           (long long)h->pr, (long long)h->pl, h->naux, nplanes);
+    else
+        hipLaunchKernelGGL(inv_region_copy_kernel<false>, grid, dim3(256), 0, ctx->stream, h->slot_planes(h->cur_slot, 0), entry, spin_stride,
+                           (long long)h->pr, (long long)h->pl, h->naux, nplanes);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64) {
+    if (!h) return DMK_ERR_INVALID;
+    int rc = eri_begin_kL_impl(h, kL, weight);
+    if (rc || !h->cache) return rc;
+    dmk_eri_cache *c = h->cache;
+    for (const auto &e : c->entries)
+        if (e.kL == kL && e.key == key64 && e.re_only == (h->re_only ? 1 : 0)) {
+            rc = inv_region_copy(h, e.buf, true);
+            if (rc) return rc;
+            h->inv_warm = true;
+            c->hits += 1;
+            return DMK_OK;
+        }
+    c->misses += 1;
+    h->inv_save = true;
+    h->inv_key = key64;
+    return DMK_OK;
+}
+
+// end of a cold kL begun with a key: its finished region becomes a cache entry when the budget holds it (else the kL stays dense)
+static int inv_save_entry(dmk_eri *h) {
+    dmk_eri_cache *c = h->cache;
+    h->inv_save = false;
+    if (!c) return DMK_OK;
+    const size_t bytes = (size_t)h->spin * (h->re_only ? 1 : 2) * h->naux * INV_ROW * sizeof(double);
+    if (c->held + bytes > c->budget) return DMK_OK;
+    double *buf = nullptr;
+    if (dmk_dev_alloc(h->ctx, reinterpret_cast<void **>(&buf), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return DMK_OK;
+    }
+    int rc = inv_region_copy(h, buf, false);
+    if (rc) { (void)hipFree(buf); return rc; }
+    c->entries.push_back({h->cur_kL, h->inv_key, h->re_only ? 1 : 0, buf, bytes});
+    c->held += bytes;
     return DMK_OK;
 }
 
@@ -973,6 +1088,103 @@ int dmk_eri_begin_kL(dmk_eri *h, int kL) {
 int dmk_eri_begin_kL_weighted(dmk_eri *h, int kL, int weight) {
     if (!h) return DMK_ERR_INVALID;
     return eri_begin_kL_impl(h, kL, weight);
+}
+
+int dmk_eri_cache_create(dmk_ctx *ctx, int64_t budget_bytes, dmk_eri_cache **out) {
+    if (!ctx || !out) return DMK_ERR_INVALID;
+    *out = nullptr;
+    size_t free_b = 0, total_b = 0;
+    DMK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    dmk_eri_cache *c = new dmk_eri_cache(ctx);
+    c->budget = std::min<size_t>(budget_bytes > 0 ? (size_t)budget_bytes : 0, free_b / 4);
+    if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&c->flag), sizeof(int)) != hipSuccess) {
+        delete c;
+        return dmk_fail(ctx, DMK_ERR_NOMEM, "eri_cache_create: allocation failed");
+    }
+    *out = c;
+    return DMK_OK;
+}
+
+// forget every entry (and, with `cols`, the columns they were built from)
+static void inv_cache_clear(dmk_eri_cache *c, bool cols) {
+    if (!c->entries.empty() || (cols && c->cols)) (void)hipStreamSynchronize(c->ctx->stream);
+    for (auto &e : c->entries) (void)hipFree(e.buf);
+    c->drops += (long long)c->entries.size();
+    c->entries.clear();
+    c->held = 0;
+    if (cols) {
+        if (c->cols) (void)hipFree(c->cols);
+        c->cols = nullptr;
+        c->cols_rows = 0;
+        c->have_cols = false;
+    }
+}
+
+int dmk_eri_cache_drop(dmk_eri_cache *cache) {
+    if (!cache) return DMK_ERR_INVALID;
+    inv_cache_clear(cache, true);
+    return DMK_OK;
+}
+
+int dmk_eri_cache_destroy(dmk_eri_cache *cache) {
+    if (!cache) return DMK_OK;
+    inv_cache_clear(cache, true);
+    if (cache->flag) (void)hipFree(cache->flag);
+    delete cache;
+    return DMK_OK;
+}
+
+int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]) {
+    if (!cache || !stats) return DMK_ERR_INVALID;
+    stats[0] = cache->hits; stats[1] = cache->misses; stats[2] = (int64_t)cache->entries.size();
+    stats[3] = (int64_t)cache->held; stats[4] = cache->drops;
+    return DMK_OK;
+}
+
+int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached) {
+    if (!h || !cache) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (attached) *attached = 0;
+    if (cache->ctx != ctx) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_attach_cache: the cache belongs to another context");
+    if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_attach_cache: a kL is in progress");
+    // only the grouped nemb = 256 path has the workgroup types the region is made of; the partner term and Re-only planes need time reversal
+    if (!h->hot256 || h->group <= 1 || !h->tr || h->imag || h->sub_planes || h->nemb != 256) return DMK_OK;
+    const int shape[7] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin};
+    const size_t rows = (size_t)h->spin * h->mesh.nk * h->nao;
+    bool same = cache->have_cols && cache->cols_rows == rows;
+    for (int i = 0; i < 7 && same; ++i) same = cache->shape[i] == shape[i];
+    if (same) {
+        // bit patterns of columns [0, 192) of every (spin, k, AO row), reduced to one flag on the device and read back once
+        const long long n = (long long)rows * INV_COLS;
+        DMK_HIP(ctx, hipMemsetAsync(cache->flag, 0, sizeof(int), ctx->stream));
+        {
+            FamScope fs(ctx, DMK_FAM_MISC);
+            const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, n, h->nemb,
+                               reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(cache->cols), cache->flag);
+            DMK_CHECK_LAUNCH(ctx);
+        }
+        int diff = 1;
+        DMK_HIP(ctx, hipMemcpyAsync(&diff, cache->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        same = diff == 0;
+    }
+    if (!same) {
+        inv_cache_clear(cache, true);
+        if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&cache->cols), rows * INV_COLS * sizeof(double2)) != hipSuccess) {
+            (void)hipGetLastError();
+            cache->cols = nullptr;
+            return DMK_OK;                          // no room for the columns: the pipeline stays dense
+        }
+        DMK_HIP(ctx, hipMemcpy2DAsync(cache->cols, (size_t)INV_COLS * sizeof(double2), h->C, (size_t)h->nemb * sizeof(double2),
+                                      (size_t)INV_COLS * sizeof(double2), rows, hipMemcpyDeviceToDevice, ctx->stream));
+        for (int i = 0; i < 7; ++i) cache->shape[i] = shape[i];
+        cache->cols_rows = rows;
+        cache->have_cols = true;
+    }
+    h->cache = cache;
+    if (attached) *attached = 1;
+    return DMK_OK;
 }
 
 static int eri_ring_step1(dmk_eri *h) {
@@ -1016,7 +1228,9 @@ static int eri_flush(dmk_eri *h) {
     if (h->hot256) {
         rc = launch_half2_hot(ctx, h->Ut, (long long)slot_elems, h->pending, cj, h->pend_sym, h->slot_planes(h->cur_slot, 0), h->pr, h->pl,
                               naux, nao, nemb, h->spin, (long long)h->group * (long long)slot_elems, (long long)h->mesh.nk * h->kdim * nemb,
-                              (long long)h->nslots * 2LL * h->pr * h->pl, h->kdim, h->re_only ? 1 : 0);
+                              (long long)h->nslots * 2LL * h->pr * h->pl, h->kdim, h->re_only ? 1 : 0, h->inv_warm ? 1 : 0);
+        if (rc == 0 && h->inv_warm)
+            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the nemb = 256 step-2 kernel declined a kL whose invariant planes came from the cache");
     } else {
         const int nsub = h->sub_planes ? half2_tab_subgroups(ctx, naux, nao, nemb, h->spin, h->pending, h->nsub_max) : 1;
         rc = launch_half2_tab(ctx, h->Ut, (long long)slot_elems, h->pending, cj, h->pend_sym, h->slot_planes(h->cur_slot, 0), h->pr, h->pl,
@@ -1172,6 +1386,10 @@ int dmk_eri_end_kL(dmk_eri *h, int weight) {
         if (rcf) return rcf;
         rcf = eri_fold_subplanes(h);
         if (rcf) return rcf;
+        if (h->inv_save) {
+            rcf = inv_save_entry(h);
+            if (rcf) return rcf;
+        }
     }
     int K, Kalg;                        // rows of the planes that enter (padding rows are zero) / rows that count as work
     double alpha;

@@ -244,6 +244,9 @@ struct H2Args {
     // completed as P + P^T in the epilogue (S_rr = U_r^T C_r + C_r^T U_r, and the second product is the transpose of the
     // first): 256 instead of 272 block products per L, and triangle waves issue 16 per K step like the square ones
     int fold_diag;
+    // the caller has already put the iteration-invariant part of the planes in place (types 0 and 2: every pair with a < 192 that
+    // those two workgroups own, capi.hip dmk_eri_cache): only types 1 and 3 run, two workgroups per (L, spin)
+    int skip_invariant;
 };
 
 // Kernel-argument arrays must only be indexed with compile-time constants, and the argument struct must
@@ -264,7 +267,9 @@ __global__ __launch_bounds__(HNT, 2) void half2_kernel(const H2Args g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar LDS-DMA addressing
     const int frag_k = lane >> 4, frag_x = lane & 15;
     const unsigned lid = xcd_remap(blockIdx.x, g.nblocks);
-    const int Lall = (int)(lid >> 2), type = (int)(lid & 3);
+    // (blockIdx and kernel arguments only: wave-uniform either way)
+    const int Lall = g.skip_invariant ? (int)(lid >> 1) : (int)(lid >> 2);
+    const int type = g.skip_invariant ? 1 + 2 * (int)(lid & 1) : (int)(lid & 3);
     const int sp = Lall >= g.nL ? 1 : 0;     // nspin <= 2
     const int L = Lall - sp * g.nL;
     const long long nemb = H2_N;
@@ -598,7 +603,7 @@ int launch_half1_hot_multi(dmk_ctx *ctx, const void *Lpq, long long a_slot_strid
 
 int launch_half2_hot(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj,
                      const int *sym, double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
-                     long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int kdim, int re_only) {
+                     long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int kdim, int re_only, int skip_invariant) {
     if (kdim == 0) kdim = nao;
     if (!hot_enabled() || nemb != H2_N || kdim < nao || (kdim % H2_BK) != 0 || nao < 3 * H2_BK || nslot < 1 || nslot > H2_MAXSLOT ||
         nspin < 1 || nspin > 2)
@@ -617,13 +622,18 @@ int launch_half2_hot(dmk_ctx *ctx, const void *Ut, long long slot_stride, int ns
     a.nL = nL; a.nao = nao; a.nslot = nslot; a.kdim = kdim;
     a.nspin = nspin;
     a.ut_spin_stride = ut_spin_stride; a.cj_spin_stride = cj_spin_stride; a.planes_spin_stride = planes_spin_stride;
-    a.nblocks = (unsigned)(4 * nL * nspin);
+    a.skip_invariant = skip_invariant ? 1 : 0;
+    a.nblocks = (unsigned)((skip_invariant ? 2 : 4) * nL * nspin);
     a.fold_diag = (a.symmask == (nslot >= 32 ? 0xffffffffu : ((1u << nslot) - 1u))) ? 1 : 0;
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
     {   // 136 of the 256 16 x 16 blocks per L and spin; a block with the time-reversal partner term runs a second segment
         // (without the 16 diagonal blocks when the whole group is symmetrised: they are folded in the epilogue)
+        // skip_invariant: types 1 and 3 only -- 32 + 36 = 68 blocks, the partner term without the 8 diagonal blocks of type 3 when folded
         double blocks = 0.0;
-        for (int i = 0; i < nslot; ++i) blocks += 136.0 + (sym[i] ? (a.fold_diag ? 120.0 : 136.0) : 0.0);
+        for (int i = 0; i < nslot; ++i) {
+            if (skip_invariant) blocks += 68.0 + (sym[i] ? (a.fold_diag ? 60.0 : 68.0) : 0.0);
+            else blocks += 136.0 + (sym[i] ? (a.fold_diag ? 120.0 : 136.0) : 0.0);
+        }
         fs.mfma_flops((re_only ? 4.0 : 6.0) * blocks * 256.0 * (double)kdim * (double)nL * (double)nspin);
     }
     if (re_only) hipLaunchKernelGGL((half2_kernel<0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);

@@ -119,10 +119,12 @@ def binding_table():
     return out
 
 
-def install(reference_package="libdmet", replace_hf=True, strict=True, resident_df=None):
+def install(reference_package="libdmet", replace_hf=True, strict=True, resident_df=None, invariant_planes=None):
     """Rebind the reference's hot-path entry points to the HIP implementations; returns the undo handle.
     `resident_df=True`: the DF tensor behind `lattice.df` is loaded into HBM by the first get_emb_eri of a run and read in place by
-    every later one (eri_transform.RESIDENT_DF; as many kL as fit, the rest streamed as before) -- no change to the DMET script."""
+    every later one (eri_transform.RESIDENT_DF; as many kL as fit, the rest streamed as before) -- no change to the DMET script.
+    `invariant_planes=True` (with `resident_df`): the impurity-only part of the step-2 planes is kept next to the resident tensor and
+    reused by every later transform whose leading C_ao_emb columns are bit-identical (eri_transform.INVARIANT_PLANES, nemb = 256)."""
     from libdmet_preview_amd import _lib          # noqa: F401 -- loading libdmetk.so fails loudly here if it is missing
     undo = []
 
@@ -147,6 +149,10 @@ def install(reference_package="libdmet", replace_hf=True, strict=True, resident_
         from libdmet_preview_amd.basis_transform import eri_transform as my_et
         undo.append((my_et, "RESIDENT_DF", my_et.RESIDENT_DF))
         my_et.RESIDENT_DF = bool(resident_df)
+    if invariant_planes is not None:
+        from libdmet_preview_amd.basis_transform import eri_transform as my_et
+        undo.append((my_et, "INVARIANT_PLANES", my_et.INVARIANT_PLANES))
+        my_et.INVARIANT_PLANES = bool(invariant_planes)
     return undo
 
 

@@ -57,6 +57,7 @@ class SyntheticSystem(object):
         self.kpts = self.cell.get_abs_kpts(ks)
         self.df = et.GDFPhilox(self.kpts, naux, nlo, seed=seed + 2) if naux > 0 else None
         self.df_resident = None                 # et.GDFResident of a kL shard (make_df_resident): the blocks kept in HBM
+        self.eri_inv_cache = None               # et.EriInvariantCache of eri_stage: invariant step-2 planes kept across iterations
         # orbital index sets: impurity = cell 0, valence = first nval orbitals (ncore = 0)
         self.imp_idx = list(range(nlo))
         self.val_idx = list(range(nval))
@@ -412,7 +413,15 @@ def eri_stage(ctx, sysm, d_C, nemb, eri_dev, kL_list=None, timers=None, max_bloc
     contraction, dist.reduce_eri_bands).  `probe` = (d_x, d_yref): Freivalds probe of the contraction (EriEngine.set_probe).  Returns (nblocks, flops_half, flops_contract, ownership table or None)."""
     timers = {} if timers is None else timers
     t = time.perf_counter()
-    eng = et.EriEngine(ctx, sysm.mesh, sysm.nao, sysm.naux, nemb, sysm.spin, d_C, eri_dev, True)
+    # iteration-invariant step-2 planes: the impurity columns of C_ao_emb come first and do not change between iterations.  The
+    # tests below only avoid a cache that could never hit; what makes a hit legal is the library's bitwise compare of the columns
+    # (DMK_ERI_INV=0: the dense step 2 of every call, the A/B switch)
+    inv = None
+    if os.environ.get("DMK_ERI_INV", "1") != "0":
+        inv = getattr(sysm, "eri_inv_cache", None)
+        if inv is None and nemb == 256 and len(sysm.imp_idx) >= 192:
+            inv = sysm.eri_inv_cache = et.EriInvariantCache(ctx)
+    eng = et.EriEngine(ctx, sysm.mesh, sysm.nao, sysm.naux, nemb, sysm.spin, d_C, eri_dev, True, inv_cache=inv)
     rows = None
     try:
         todo = eng.irreducible_kL() if kL_list is None else list(kL_list)

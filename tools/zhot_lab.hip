@@ -134,7 +134,7 @@ int main() {
     h.slot_stride = (long long)ut; h.planes = planes; h.naux = nL; h.npair = npair;
     h.nL = nL; h.nao = nao; h.kdim = nao; h.nslot = nslot; h.nspin = nspin;
     h.ut_spin_stride = (long long)nslot * ut; h.cj_spin_stride = (long long)nk * nao * nemb; h.planes_spin_stride = 2LL * nL * npair;
-    h.nblocks = (unsigned)(4 * nL * nspin); h.fold_diag = 1;
+    h.nblocks = (unsigned)(4 * nL * nspin); h.fold_diag = 1; h.skip_invariant = 0;
     const double f2 = 6.0 * (double)nslot * (136.0 + 120.0) * 256.0 * nao * nL * nspin;
     printf("step 2 (half2_kernel): %u workgroups, %.1f GFLOP issued per launch\n", h.nblocks, f2 * 1e-9);
 #define RUN2(LABV)                                                                                                            \
