@@ -1022,7 +1022,7 @@ class EriEngine(object):
     # ---- plane stack: deferred, K-stacked contraction (dmk_eri_stack) ---------------------------------------------------
     def slot_bytes(self):
         """Bytes of one plane slot (all spins, Re and Im) in the library's plane geometry: naux rounded up to 8 rows, the pair
-        index to an even row length (capi.hip dmk_eri: pr, pl)."""
+        index to an even row length (eri_engine.hip dmk_eri: pr, pl)."""
         npair = self.nemb * (self.nemb + 1) // 2
         return self.spin * 2 * ((self.naux + 7) // 8 * 8) * (npair + (npair & 1)) * 8
 

@@ -245,7 +245,7 @@ struct H2Args {
     // first): 256 instead of 272 block products per L, and triangle waves issue 16 per K step like the square ones
     int fold_diag;
     // the caller has already put the iteration-invariant part of the planes in place (types 0 and 2: every pair with a < 192 that
-    // those two workgroups own, capi.hip dmk_eri_cache): only types 1 and 3 run, two workgroups per (L, spin)
+    // those two workgroups own, eri_engine.hip dmk_eri_cache): only types 1 and 3 run, two workgroups per (L, spin)
     int skip_invariant;
 };
 
@@ -524,7 +524,7 @@ int half1_hot_usable(int nL, int nao, int nemb) {
 
 // Auxiliary rows one step-1 launch may cover: the per-lane part of an LDS-DMA source address is a 32-bit byte offset from the
 // block's base, so a launch spans < 4 GiB of its AO block; blocks beyond that (naux nao^2 >= 2^28) are transformed in several
-// launches over ranges of L (capi.hip).  DMK_ERI_HOT_LCHUNK caps it (tests: the cut on small shapes).
+// launches over ranges of L (eri_engine.hip). DMK_ERI_HOT_LCHUNK caps it (tests: the cut on small shapes).
 int half1_hot_max_rows(int nao) {
     long long rows = ((1LL << 32) - 1) / ((long long)nao * nao * 16);
     if (const char *e = getenv("DMK_ERI_HOT_LCHUNK")) { const int v = atoi(e); if (v > 0 && v < rows) rows = v; }

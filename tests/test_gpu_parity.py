@@ -915,6 +915,86 @@ def test_tab_half_transform_planes(ctx, nao, naux, nemb, spin, env, monkeypatch)
             eng.close()
 
 
+def test_planes_in_the_middle_of_a_kL_with_subgroup_copies(ctx, monkeypatch):
+    """dmk_eri_planes while a kL is in progress and the table-driven step 2 runs in two sub-group runs (DMK_ERI_TAB_SUB=2): the
+    second run's plane copy is added to the kL's planes and zeroed again, so neither a second look nor the end of the kL adds
+    it twice.  Planes after 5 and after 11 pushes against the oracle's r_e2 restatement, then the two-spin contraction of the
+    finished kL against numpy.  naux 27 and npair 561 are off the plane tile (8 rows, even length): the padded geometry."""
+    from libdmet_preview_amd.basis_transform import eri_transform as et
+    from libdmet_preview_amd._lib import lib
+    monkeypatch.setenv("DMK_ERI_TAB_SUB", "2")
+    mesh, nao, naux, nemb, spin = (2, 2, 1), 24, 27, 33, 2
+    npair = nemb * (nemb + 1) // 2
+    rng = np.random.default_rng(2733)
+    Cemb = (rng.standard_normal((spin, 4, nao, nemb)) + 1j * rng.standard_normal((spin, 4, nao, nemb))) / np.sqrt(nao)
+    eri_dev = ctx.zeros((3, npair, npair), np.float64)
+    eng = et.EriEngine(ctx, mesh, nao, naux, nemb, spin, ctx.to_device(Cemb), eri_dev, True)
+    assert eng.ring_slots == 16                                  # the grouped table-driven path
+    ctx.check(lib.dmk_eri_begin_kL(eng.h, 1))
+    pushes = [(1, 0, 1), (3, 2, 0), (0, 1, 1), (2, 3, 1), (0, 0, 0), (1, 1, 1), (2, 0, 0), (3, 1, 1), (0, 2, 1), (1, 3, 0), (2, 2, 1)]
+    ref = np.zeros((spin, naux, npair), dtype=np.complex128)
+    keep = []
+    for n, (i, j, sym) in enumerate(pushes):
+        blk = R.df_block_philox(5, i, j, naux, nao)
+        keep.append(ctx.to_device(blk))                          # must outlive the call: the pipeline reads it asynchronously
+        ctx.check(lib.dmk_eri_push_block(eng.h, i, j, sym, keep[-1].ptr))
+        Lij = R.transform_ao_to_emb(blk.reshape(naux, -1), Cemb, i, j)
+        ref += R.pack_tril(Lij + Lij.transpose(0, 1, 3, 2) if sym else Lij)
+        if n in (4, 10):
+            for look in range(2):                                # the second look flushes nothing and must change nothing
+                planes = eng.planes().get()
+                got = planes[:, 0] + 1j * planes[:, 1]
+                err = np.abs(got - ref).max()
+                assert err < 1e-11 * max(1.0, np.abs(ref).max()), (n, look, err)
+    ctx.check(lib.dmk_eri_end_kL(eng.h, 2))
+    ctx.sync()
+    got = eri_dev.get()
+    eng.close()
+    X = np.concatenate([ref.real, ref.imag], axis=1)             # (spin, 2 naux, npair)
+    want = 2.0 * np.stack([np.einsum("Lp,Lq->pq", X[a], X[b]) for a, b in ((0, 0), (0, 1), (1, 1))])
+    err = np.abs(got - want).max()
+    assert err < 1e-11 * np.abs(want).max(), err
+
+
+def test_end_kL_without_time_reversal_two_spins_real_and_imaginary_part(ctx):
+    """dmk_eri_end_kL with the imaginary-part accumulator (dmk_eri_begin flag 2, no time reversal) and two spins, on the generic
+    kernels: all three spin blocks of Re (L_a^H L_b) in the ERI and of Im (L_a^H L_b) = Re_a^T Im_b - Im_a^T Re_b in the
+    accumulator, summed over two kL, element by element against numpy on the oracle's half-transformed blocks.  naux 11 and
+    npair 15 are off the plane tile."""
+    from libdmet_preview_amd.basis_transform import eri_transform as et
+    from libdmet_preview_amd._lib import lib
+    mesh, nao, naux, nemb, spin = (2, 2, 1), 24, 11, 5, 2
+    npair = nemb * (nemb + 1) // 2
+    rng = np.random.default_rng(1105)
+    Cemb = (rng.standard_normal((spin, 4, nao, nemb)) + 1j * rng.standard_normal((spin, 4, nao, nemb))) / np.sqrt(nao)
+    eri_dev = ctx.zeros((3, npair, npair), np.float64)
+    eng = et.EriEngine(ctx, mesh, nao, naux, nemb, spin, ctx.to_device(Cemb), eri_dev, False, track_imag=True)
+    assert eng.ring_slots == 0                                   # generic kernels
+    want_re, want_im = np.zeros((3, npair, npair)), np.zeros((3, npair, npair))
+    keep = []
+    for kL, pushes in ((1, [(1, 0), (3, 2), (0, 1)]), (2, [(2, 0), (3, 1)])):
+        ctx.check(lib.dmk_eri_begin_kL(eng.h, kL))
+        L = np.zeros((spin, naux, npair), dtype=np.complex128)
+        for (i, j) in pushes:
+            blk = R.df_block_philox(8, i, j, naux, nao)
+            keep.append(ctx.to_device(blk))
+            ctx.check(lib.dmk_eri_push_block(eng.h, i, j, 0, keep[-1].ptr))
+            L += R.pack_tril(R.transform_ao_to_emb(blk.reshape(naux, -1), Cemb, i, j))
+        ctx.check(lib.dmk_eri_end_kL(eng.h, 1))
+        for b, (s0, s1) in enumerate(((0, 0), (0, 1), (1, 1))):
+            LL = np.einsum("Lp,Lq->pq", L[s0].conj(), L[s1])
+            want_re[b] += LL.real
+            want_im[b] += LL.imag
+    ctx.sync()
+    got_re, got_im, norm = eri_dev.get(), eng.imag_buffer().get(), eng.imag_norm()
+    eng.close()
+    scale = np.abs(want_re).max()
+    assert np.abs(want_im).max() > 1e-3 * scale                  # a real test of the imaginary part
+    assert np.abs(got_re - want_re).max() < 1e-11 * scale, np.abs(got_re - want_re).max()
+    assert np.abs(got_im - want_im).max() < 1e-11 * scale, np.abs(got_im - want_im).max()
+    assert abs(norm - np.abs(want_im).max()) < 1e-11 * scale
+
+
 @pytest.mark.parametrize("nao,naux,nemb,spin", [(40, 24, 256, 2), (10, 7, 12, 1), (24, 16, 40, 2)])
 def test_host_block_feed_matches_device_feed(ctx, nao, naux, nemb, spin):
     """dmk_eri_push_block_host (two pinned buffers, copy stream overlapped with the transform) against
