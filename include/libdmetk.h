@@ -360,6 +360,17 @@ int dmk_eri_begin_kL_weighted(dmk_eri *h, int kL, int weight);
  *       cache.  Columns [0,192) of the pipeline's C_ao_emb are compared BITWISE on the device with the copy the entries were built
  *       from, and the shape (mesh, nao, naux, nemb, spin) likewise: any difference drops every entry and stores the new columns.
  *       Call it before the first kL, after dmk_eri_begin.
+ *   dmk_eri_attach_cache_cols : the same with `ninv`, the caller's claim of how many leading columns of C_ao_emb are invariant
+ *       (the number of impurity orbitals), for ANY embedding dimension.  *cols_used tells how many columns are stored and compared.
+ *       - a pipeline on the nemb = 256 kernel: as dmk_eri_attach_cache when ninv >= 192 (*cols_used = 192), else *attached = 0;
+ *       - a pipeline on the table-driven kernel (every other nemb >= 32, and nemb = 256 under DMK_ERI_TAB256=1), grouped, with
+ *         time reversal, without the imaginary-part accumulator and without sub-plane copies: A = 16 floor(min(ninv, nemb) / 16);
+ *         A < 16 gives *attached = 0.  The region is the pairs b <= a < A -- the 16 x 16 blocks of block rows below A / 16, the
+ *         prefix [0, A (A + 1) / 2) of every plane row; an entry holds it as [spin][plane][naux][A (A + 1) / 2].  A warm kL copies
+ *         it back and launches the block table without those block rows (dmk_half2_tab_table with first_row_block = A / 16).
+ *         Columns [0, A) are compared bitwise; a difference in the shape, in A or in one bit drops every entry.
+ *       `ninv` is a hint: claiming too much only costs the hits (the compare fails), it never serves a stale plane.  Step 1 and
+ *       the contraction stay dense on both paths.
  *   dmk_eri_begin_kL_cached : dmk_eri_begin_kL_weighted plus `key64`, the caller's fingerprint of everything else the planes of
  *       this kL depend on (the DF tensor, the blocks it is about to push and their order).  An entry for (kL, key64, Re-only
  *       flag) makes the kL warm; without one it runs as before and dmk_eri_end_kL stores its region if the budget holds it.
@@ -372,7 +383,23 @@ int dmk_eri_cache_destroy(dmk_eri_cache *cache);
 int dmk_eri_cache_drop(dmk_eri_cache *cache);
 int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]);
 int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached);
+int dmk_eri_attach_cache_cols(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *attached, int *cols_used);
 int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64);
+/* The block-ownership table of the table-driven step-2 kernel, built on the host (no context, no GPU): the lower triangle of the
+ * nb x nb grid of 16 x 16 blocks (nb = ceil(nemb / 16)) without the block rows below `first_row_block`, dealt out to workgroups
+ * ("items") of four waves.  `occ` is the occupancy point, 2 (lists of up to 8 blocks per wave) or 3 (up to 5).  *nitems items of
+ * DMK_TAB_ITEM_INTS ints each are written to `table` (NULL: only *nitems and `stats` are set; else cap_ints must hold them):
+ *   [0]     kind: 0 diagonal triangle, 1 off-diagonal rectangle, 2 wide (whole matrix width, nb <= 12)
+ *   [1] [2] R0, C0: block row / column of the item's panel origin (kind 0: R0 == C0; kind 2: 0, 0)
+ *   [3..6]  number of blocks of wave 0..3
+ *   [7]     byte w: how many blocks at the END of wave w's list are diagonal ones (global row == column; at most 2) -- they skip
+ *           the partner segment and are folded when every queued AO block is symmetrised
+ *   [8 + w * maxblk + i]  block i of wave w: (local block row << 8) | local block column, global = (R0 + row, C0 + column);
+ *           maxblk = 8 (occ 2) or 5 (occ 3)
+ * stats: useful blocks, occupied block slots (4 waves x longest list, summed over the items), folded diagonal blocks.
+ * first_row_block = 0 is the dense table; first_row_block >= nb gives no item. */
+#define DMK_TAB_ITEM_INTS 48
+int dmk_half2_tab_table(int nemb, int occ, int first_row_block, int *table, int cap_ints, int *nitems, double stats[3]);
 /* Contract what is resident, restricted to the band [band_lo, band_hi) of 128-row tiles of the pair index (-1, -1: all;
  * dmk_eri_bands gives their number).  Bands must be issued in increasing order; after band b the ROWS of band b of every
  * spin block are complete, so a kL-sharded job can reduce them over its ranks while later bands are still being computed

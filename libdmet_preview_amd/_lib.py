@@ -92,7 +92,9 @@ PROTOTYPES = {
     "dmk_eri_cache_drop": (c_int, [c_vp]),
     "dmk_eri_cache_stats": (c_int, [c_vp, P(c_i64)]),
     "dmk_eri_attach_cache": (c_int, [c_vp, c_vp, P(c_int)]),
+    "dmk_eri_attach_cache_cols": (c_int, [c_vp, c_vp, c_int, P(c_int), P(c_int)]),
     "dmk_eri_begin_kL_cached": (c_int, [c_vp, c_int, c_int, C.c_uint64]),
+    "dmk_half2_tab_table": (c_int, [c_int, c_int, c_int, P(c_int), c_int, P(c_int), P(C.c_double)]),
     "dmk_eri_contract": (c_int, [c_vp, c_int, c_int, c_int]),
     "dmk_eri_probe": (c_int, [c_vp, c_vp, c_vp]),
     "dmk_eri_bands": (c_int, [c_vp, P(c_int), P(c_int)]),

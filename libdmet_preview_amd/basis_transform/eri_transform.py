@@ -932,9 +932,14 @@ def _canon(t):
 class EriInvariantCache(object):
     """Iteration-invariant step-2 planes kept across transforms (dmk_eri_cache): the embedding basis is
     [impurity | bath], so the leading columns of C_ao_emb and the DF tensor stay the same over a DMET run, and with them the
-    plane entries of every pair the nemb = 256 step-2 kernel gives to its impurity-only workgroups (a < 192).  Pass it to
-    `EriEngine(..., inv_cache=)`: a kL whose entry exists copies that region back and runs half of step 2.  A hit is only ever
-    made legal by the library's bitwise compare of columns [0,192) of C_ao_emb on the device plus the key of the kL (`inv_key64`).
+    plane entries of an impurity-only region of pairs (a, b).  Two regions, by the step-2 kernel of the pipeline:
+      * nemb = 256 kernel: the pairs its impurity-only workgroups own (a < 192, b < 128) -- needs 192 invariant columns;
+      * table-driven kernel (every other nemb >= 32): with `inv_cols` invariant columns and A = 16 floor(inv_cols / 16), the pairs
+        b <= a < A, the prefix of every plane row -- needs A >= 16 (`EriEngine(..., inv_cols=)`).
+    Pass it to `EriEngine(..., inv_cache=)`: a kL whose entry exists copies that region back and step 2 leaves its blocks out
+    (half of the block products at nemb = 256, 40 - 50 % at nemb 136 - 272 with a typical impurity).  A hit is only ever
+    made legal by the library's bitwise compare of columns [0,192) / [0,A) of C_ao_emb on the device plus the key of the kL
+    (`inv_key64`).
     `budget_gb`: default DMK_ERI_INV_GB (64), capped by the library at a quarter of the free device memory; never evicts."""
 
     def __init__(self, ctx, budget_gb=None):
@@ -970,12 +975,15 @@ class EriEngine(object):
     """Owns a dmk_eri pipeline: plan -> (begin_kL, push_block*, end_kL)* on one GPU."""
 
     def __init__(self, ctx, kmesh, nao, naux, nemb, spin, C_ao_emb_dev, eri_dev, t_reversal_symm=True, gso=False, plan=None,
-                 track_imag=False, rows_only=False, inv_cache=None):
+                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None):
         """`plan` = (weights, records) of `general_plan` for k lists that are not the np.fft-ordered Gamma-centred mesh
         (then `kmesh` only carries the number of k-points, [nk, 1, 1]); default: the integer-mesh plan of libdmetk.
         `inv_cache`: an EriInvariantCache; the library attaches it only where the invariant region exists (the grouped
         nemb = 256 path, time reversal, no GSO, no `track_imag`), `self.inv_attached` tells; kL fed by a provider without a
         `df_token` run dense all the same.
+        `inv_cols`: how many leading columns of C_ao_emb the caller expects to stay the same (the impurity orbitals).  With it
+        the cache also attaches on the table-driven path of any other embedding dimension (dmk_eri_attach_cache_cols), and
+        `self.inv_cols_used` tells how many columns are stored and compared (192, or 16 floor(inv_cols / 16); 0: not attached).
         `rows_only`: a pipeline WITHOUT an ERI of its own (`eri_dev` may be None): its planes are only ever taken slab-wise
         with `contract_rows_into`; every path that would contract into an internal ERI refuses instead (dmk_eri_begin flag 4).
         `track_imag`: without time reversal also accumulate the imaginary part of the contraction for the reference's
@@ -1008,11 +1016,15 @@ class EriEngine(object):
         self.by_kL = {}
         for r in self.records:
             self.by_kL.setdefault(int(r[0]), []).append(r)
-        self.inv_cache, self.inv_attached = None, False
+        self.inv_cache, self.inv_attached, self.inv_cols_used = None, False, 0
         if inv_cache is not None and not self.gso and self.tr and not self.track_imag:
-            att = C.c_int(0)
-            ctx.check(lib.dmk_eri_attach_cache(self.h, inv_cache.h, C.byref(att)))
+            att, used = C.c_int(0), C.c_int(0)
+            if inv_cols is None:
+                ctx.check(lib.dmk_eri_attach_cache(self.h, inv_cache.h, C.byref(att)))
+            else:
+                ctx.check(lib.dmk_eri_attach_cache_cols(self.h, inv_cache.h, int(inv_cols), C.byref(att), C.byref(used)))
             self.inv_attached = bool(att.value)
+            self.inv_cols_used = int(used.value)
             if self.inv_attached:
                 self.inv_cache = inv_cache                # (kept alive while the pipeline holds its address)
 
@@ -1376,9 +1388,27 @@ def get_emb_eri_fast_gdf(cell, mydf, C_ao_lo=None, basis=None, feri=None, kscale
 RESIDENT_DF = os.environ.get("DMK_DF_RESIDENT", "0") == "1"
 RESIDENT_DF_FRACTION = float(os.environ.get("DMK_DF_RESIDENT_FRACTION", "0.5"))
 # INVARIANT_PLANES (patch.install(invariant_planes=True); off by default): with RESIDENT_DF, an EriInvariantCache is kept next to
-# the cached resident tensor (`res.inv_cache`) and handed to every transform that reads it; drop_resident() frees both.
+# the cached resident tensor (`res.inv_cache`) and handed to every transform that reads it; drop_resident() frees both.  At
+# nemb = 256 the region is that of the specialised kernel; at any other nemb a `basis=` of the form [I_imp | bath] gives the hint
+# for the table path's region (leading_identity_columns); the `C_ao_eo=` entry carries no hint and stays dense there.
 INVARIANT_PLANES = False
 _resident_cache = {}
+
+
+def leading_identity_columns(basis):
+    """The largest n such that, for every spin, basis[s, 0, :, :n] == eye(nlo)[:, :n] and basis[s, 1:, :, :n] == 0: the embedding
+    basis [I_imp | bath] with the impurity in the first cell (routine/slater.py, embBasis).  0 for anything else.  Only a hint
+    for `EriEngine(inv_cols=)`: what makes a cache hit legal is the library's compare of the columns on the device."""
+    b = np.asarray(basis)
+    if b.ndim == 3:
+        b = b[np.newaxis]
+    if b.ndim != 4 or b.shape[1] < 1:
+        return 0
+    n = min(b.shape[2], b.shape[3])
+    want = np.zeros((b.shape[1], b.shape[2], n))
+    want[0, np.arange(n), np.arange(n)] = 1.0
+    bad = np.flatnonzero(~(b[..., :n] == want[np.newaxis]).all(axis=(0, 1, 2)))
+    return int(bad[0]) if bad.size else int(n)
 
 
 def drop_resident():
@@ -1482,14 +1512,19 @@ def _emb_eri_fast_gdf(cell, mydf, C_ao_lo, basis, kscaled_center, symmetry, C_ao
         return _emb_eri_outcore(ctx, cell, mydf, kmesh, plan, C_dev, nao, naux, nemb, spin, fout, use_mpi)
 
     eri_dev = ctx.zeros((spin_pair, npair, npair), np.float64)
-    inv = None
-    if (INVARIANT_PLANES and nemb == 256 and t_reversal_symm and any(r is mydf for _, r in _resident_cache.values())
+    inv, inv_cols = None, None
+    if (INVARIANT_PLANES and t_reversal_symm and any(r is mydf for _, r in _resident_cache.values())
             and os.environ.get("DMK_ERI_INV", "1") != "0"):
-        if getattr(mydf, "inv_cache", None) is None:
-            mydf.inv_cache = EriInvariantCache(ctx)
-        inv = mydf.inv_cache
+        if basis is not None and C_ao_eo is None and not unit_eri:
+            inv_cols = leading_identity_columns(basis)
+            if inv_cols < 16:
+                inv_cols = None
+        if nemb == 256 or inv_cols is not None:
+            if getattr(mydf, "inv_cache", None) is None:
+                mydf.inv_cache = EriInvariantCache(ctx)
+            inv = mydf.inv_cache
     eng = EriEngine(ctx, kmesh, nao, naux, nemb, spin, C_dev, eri_dev, t_reversal_symm, plan=plan,
-                    track_imag=not t_reversal_symm, inv_cache=inv)
+                    track_imag=not t_reversal_symm, inv_cache=inv, inv_cols=inv_cols)
     try:
         kL_list = None
         dist = None

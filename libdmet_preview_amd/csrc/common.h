@@ -40,8 +40,9 @@ struct dmk_ctx {
     // tile visiting orders of the contraction kernel (dgemm_tn.hip), one per (tiles_m, tiles_n, symm)
     struct TileTable { int tiles_m, tiles_n, symm, lo, hi; unsigned count; unsigned *dev; };
     std::vector<TileTable> tile_tables;
-    // block-ownership tables of the general-nemb step-2 kernel (zhot_tab.hip), one per embedding dimension
-    struct StepTable { int nemb, cfg, nitems; double useful_blocks, folded_blocks; int *dev; };
+    // block-ownership tables of the general-nemb step-2 kernel (zhot_tab.hip), one per embedding dimension, occupancy point and
+    // first block row (lo > 0: the warm tables of the invariant planes cache)
+    struct StepTable { int nemb, cfg, lo, nitems; double useful_blocks, folded_blocks; int *dev; };
     std::vector<StepTable> step2_tables;
     // caller-side cache release (dmk_set_oom_hook): the host binding parks freed device blocks in a pool the library cannot
     // see; before any allocation inside the library is reported as failed the hook is asked to give that memory back
@@ -319,7 +320,8 @@ int half1_hot_usable(int nL, int nao, int nemb);
 int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj,
                      const int *sym, double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
                      long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int nsub = 1,
-                     double *planes_sub = nullptr, long long sub_stride = 0, int kdim = 0, int re_only = 0);
+                     double *planes_sub = nullptr, long long sub_stride = 0, int kdim = 0, int re_only = 0,
+                     int first_row_block = 0);
 int half2_tab_subgroups(dmk_ctx *ctx, int nL, int nao, int nemb, int nspin, int nslot, int max_sub);
 int half2_tab_usable(int nao, int nemb);
 int half2_tab_maxslot();

@@ -85,10 +85,13 @@ struct dmk_eri {
     const double *probe_x = nullptr;
     double *probe_y = nullptr;
     bool probe_pending = false;      // planes entered the stack since the probe last ran over it
-    // iteration-invariant planes (dmk_eri_attach_cache): inv_warm -- the region of the current kL came from the cache and step 2
-    // runs the two-type grid; inv_save -- a cold kL begun with a key, whose region goes into a new entry when it ends
+    // iteration-invariant planes (dmk_eri_attach_cache / _cols): inv_warm -- the region of the current kL came from the cache and
+    // step 2 runs the two-type grid (nemb = 256 kernel) or the table without the region's block rows (table kernel); inv_save -- a
+    // cold kL begun with a key, whose region goes into a new entry when it ends.  inv_A: 0 with the region of the nemb = 256 kernel,
+    // else the table path's region -- the pairs b <= a < inv_A (a multiple of 16), the prefix of every plane row.
     dmk_eri_cache *cache = nullptr;
     bool inv_warm = false, inv_save = false;
+    int inv_A = 0;
     uint64_t inv_key = 0;
     dmk_eri(dmk_ctx *c, const int m[3]) : ctx(c), mesh(m) {}
 
@@ -459,7 +462,10 @@ static int eri_flush(dmk_eri *h) {
         const int nsub = h->sub_planes ? half2_tab_subgroups(ctx, naux, nao, nemb, h->spin, h->pending, h->nsub_max) : 1;
         rc = launch_half2_tab(ctx, h->Ut, slot_elems, h->pending, cj, h->pend_sym, h->slot_planes(h->cur_slot, 0), h->pr, h->pl,
                               naux, nao, nemb, h->spin, ut_spin_stride, h->c_spin_stride(), h->planes_spin_stride(), nsub,
-                              h->sub_planes, (long long)h->spin * 2LL * h->pr * h->pl, h->kdim, h->re_only ? 1 : 0);
+                              h->sub_planes, (long long)h->spin * 2LL * h->pr * h->pl, h->kdim, h->re_only ? 1 : 0,
+                              h->inv_warm ? h->inv_A / 16 : 0);
+        if (rc == 0 && h->inv_warm)      // (the generic fallback below would add the cached region a second time)
+            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the table-driven step-2 kernel declined a kL whose invariant planes came from the cache");
         if (rc == 1) h->sub_used = std::max(h->sub_used, nsub);
     }
     if (rc < 0) return rc;
@@ -1073,14 +1079,20 @@ int dmk_eri_end_kL_gso(dmk_eri *h, int weight) {
 // their own: the prefix [0, 8256) of the packed pair index (triangle [0,128)^2) and, for a in [128,192), the 128 entries from
 // a (a + 1) / 2 (rows [128,192) x cols [0,128)).  They are a function of columns [0,192) of C_ao_emb, the DF blocks and the visiting
 // plan alone; a cache entry holds that region of one kL's finished planes, INV_ROW doubles per auxiliary row and plane.
+//
+// The table-driven kernel (zhot_tab.hip) owns blocks by data: with A = 16 floor(ninv / 16) for `ninv` invariant leading columns, the
+// 16 x 16 blocks of block rows below A / 16 hold exactly the pairs b <= a < A -- the prefix [0, A (A + 1) / 2) of every plane row, a
+// function of columns [0, A) alone.  A warm kL copies the prefix back and launches the table without those block rows.
 constexpr int INV_COLS = 192, INV_PREFIX = 8256, INV_ROW = INV_PREFIX + 64 * 128;
 
 struct dmk_eri_cache {
     dmk_ctx *ctx;
     size_t budget = 0, held = 0;
-    // what the entries were built from: the shape and columns [0, INV_COLS) of C_ao_emb ([spin nk nao][INV_COLS] c128)
+    // what the entries were built from: the shape, the region (tab_A: 0 = that of the nemb = 256 kernel, else A of the table path)
+    // and columns [0, ncols) of C_ao_emb ([spin nk nao][ncols] c128; ncols = INV_COLS or A)
     bool have_cols = false;
     int shape[7] = {0, 0, 0, 0, 0, 0, 0};       // mesh, nao, naux, nemb, spin
+    int tab_A = 0, ncols = 0;
     double2 *cols = nullptr;
     size_t cols_rows = 0;
     int *flag = nullptr;                         // device: mismatch flag of the column compare
@@ -1091,36 +1103,41 @@ struct dmk_eri_cache {
 };
 
 namespace {
-// flag = 1 if any of the 128-bit patterns of columns [0, INV_COLS) of C ([rows][nemb]) differs from cols ([rows][INV_COLS])
-__global__ void inv_cols_compare_kernel(long long n, int nemb, const ulonglong2 *__restrict__ Cm, const ulonglong2 *__restrict__ cols,
-                                        int *__restrict__ flag) {
+// flag = 1 if any of the 128-bit patterns of columns [0, ncols) of C ([rows][nemb]) differs from cols ([rows][ncols]); n = rows x ncols
+__global__ void inv_cols_compare_kernel(long long n, int nemb, int ncols, const ulonglong2 *__restrict__ Cm,
+                                        const ulonglong2 *__restrict__ cols, int *__restrict__ flag) {
     bool diff = false;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
-        const long long row = t / INV_COLS;
-        const int col = (int)(t - row * INV_COLS);
+        const long long row = t / ncols;
+        const int col = (int)(t - row * ncols);
         const ulonglong2 x = Cm[row * nemb + col], y = cols[t];
         diff = diff || x.x != y.x || x.y != y.y;
     }
     if (diff) *flag = 1;
 }
 
-// The invariant region of the planes of one kL <-> a cache entry.  grid (chunks of INV_ROW, auxiliary row L, spin x plane);
-// entry: [spin][plane][naux][INV_ROW], planes: (ri * pr + L) * pl + a (a + 1) / 2 + b per spin.
+// The invariant region of the planes of one kL <-> a cache entry.  grid (chunks of the region row, auxiliary row L, spin x plane);
+// entry: [spin][plane][naux][row], planes: (ri * pr + L) * pl + a (a + 1) / 2 + b per spin.  A region row is the prefix [0, prefix)
+// of the plane row and then, for a = 128, 129, ..., 128 entries from a (a + 1) / 2 (the nemb = 256 kernel: prefix INV_PREFIX of
+// INV_ROW; the table path: the prefix alone, row == prefix).  Consecutive threads move consecutive doubles on both sides.
 template <bool TO_PLANES>
 __global__ void inv_region_copy_kernel(double *__restrict__ planes, double *__restrict__ entry, long long planes_spin_stride,
-                                       long long pr, long long pl, int naux, int nplanes) {
+                                       long long pr, long long pl, int naux, int nplanes, int row, int prefix) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= INV_ROW) return;
+    if (e >= row) return;
     const int L = blockIdx.y, s = blockIdx.z / nplanes, ri = blockIdx.z - s * nplanes;
     long long pair = e;
-    if (e >= INV_PREFIX) {
-        const int a = 128 + ((e - INV_PREFIX) >> 7), b = (e - INV_PREFIX) & 127;
+    if (e >= prefix) {
+        const int a = 128 + ((e - prefix) >> 7), b = (e - prefix) & 127;
         pair = (long long)a * (a + 1) / 2 + b;
     }
     double *p = planes + (long long)s * planes_spin_stride + ((long long)ri * pr + L) * pl + pair;
-    double *q = entry + (((long long)s * nplanes + ri) * naux + L) * INV_ROW + e;
+    double *q = entry + (((long long)s * nplanes + ri) * naux + L) * row + e;
     if (TO_PLANES) *p = *q; else *q = *p;
 }
+
+// doubles per auxiliary row and plane of a cache entry of this pipeline's region
+int inv_row_len(const dmk_eri *h) { return h->inv_A ? h->inv_A * (h->inv_A + 1) / 2 : INV_ROW; }
 }  // namespace
 
 extern "C" {
@@ -1128,10 +1145,12 @@ extern "C" {
 static int inv_region_copy(dmk_eri *h, double *entry, bool to_planes) {
     dmk_ctx *ctx = h->ctx;
     const int nplanes = h->re_only ? 1 : 2;
-    const dim3 grid((INV_ROW + 255) / 256, (unsigned)h->naux, (unsigned)(h->spin * nplanes));
+    const int row = inv_row_len(h), prefix = h->inv_A ? row : INV_PREFIX;
+    const dim3 grid((row + 255) / 256, (unsigned)h->naux, (unsigned)(h->spin * nplanes));
     FamScope fs(ctx, DMK_FAM_MISC);
     hipLaunchKernelGGL(to_planes ? inv_region_copy_kernel<true> : inv_region_copy_kernel<false>, grid, dim3(256), 0, ctx->stream,
-                       h->slot_planes(h->cur_slot, 0), entry, h->planes_spin_stride(), (long long)h->pr, (long long)h->pl, h->naux, nplanes);
+                       h->slot_planes(h->cur_slot, 0), entry, h->planes_spin_stride(), (long long)h->pr, (long long)h->pl, h->naux, nplanes,
+                       row, prefix);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -1141,7 +1160,7 @@ static int inv_save_entry(dmk_eri *h) {
     dmk_eri_cache *c = h->cache;
     h->inv_save = false;
     if (!c) return DMK_OK;
-    const size_t bytes = (size_t)h->spin * (h->re_only ? 1 : 2) * h->naux * INV_ROW * sizeof(double);
+    const size_t bytes = (size_t)h->spin * (h->re_only ? 1 : 2) * h->naux * inv_row_len(h) * sizeof(double);
     if (c->held + bytes > c->budget) return DMK_OK;
     double *buf = nullptr;
     if (dmk_dev_alloc(h->ctx, reinterpret_cast<void **>(&buf), bytes) != hipSuccess) {
@@ -1206,26 +1225,23 @@ int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]) {
     return DMK_OK;
 }
 
-int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached) {
-    if (!h || !cache) return DMK_ERR_INVALID;
+// What both attach entry points share once the path and its region are known: tab_A = 0 and ncols = INV_COLS (nemb = 256 kernel) or
+// tab_A = ncols = A (table kernel).  The stored columns are compared bitwise on the device; any difference in the shape, the region
+// or a single bit drops every entry.
+static int inv_attach(dmk_eri *h, dmk_eri_cache *cache, int tab_A, int ncols, int *attached) {
     dmk_ctx *ctx = h->ctx;
-    if (attached) *attached = 0;
-    if (cache->ctx != ctx) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_attach_cache: the cache belongs to another context");
-    if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_attach_cache: a kL is in progress");
-    // only the grouped nemb = 256 path has the workgroup types the region is made of; the partner term and Re-only planes need time reversal
-    if (!h->hot256 || h->group <= 1 || !h->tr || h->imag || h->sub_planes || h->nemb != 256) return DMK_OK;
     const int shape[7] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin};
     const size_t rows = (size_t)h->spin * h->mesh.nk * h->nao;
-    bool same = cache->have_cols && cache->cols_rows == rows;
+    bool same = cache->have_cols && cache->cols_rows == rows && cache->tab_A == tab_A && cache->ncols == ncols;
     for (int i = 0; i < 7 && same; ++i) same = cache->shape[i] == shape[i];
     if (same) {
-        // bit patterns of columns [0, 192) of every (spin, k, AO row), reduced to one flag on the device and read back once
-        const long long n = (long long)rows * INV_COLS;
+        // bit patterns of columns [0, ncols) of every (spin, k, AO row), reduced to one flag on the device and read back once
+        const long long n = (long long)rows * ncols;
         DMK_HIP(ctx, hipMemsetAsync(cache->flag, 0, sizeof(int), ctx->stream));
         {
             FamScope fs(ctx, DMK_FAM_MISC);
             const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, n, h->nemb,
+            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, n, h->nemb, ncols,
                                reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(cache->cols), cache->flag);
             DMK_CHECK_LAUNCH(ctx);
         }
@@ -1236,20 +1252,59 @@ int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached) {
     }
     if (!same) {
         inv_cache_clear(cache, true);
-        if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&cache->cols), rows * INV_COLS * sizeof(double2)) != hipSuccess) {
+        if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&cache->cols), rows * ncols * sizeof(double2)) != hipSuccess) {
             (void)hipGetLastError();
             cache->cols = nullptr;
             return DMK_OK;                          // no room for the columns: the pipeline stays dense
         }
-        DMK_HIP(ctx, hipMemcpy2DAsync(cache->cols, (size_t)INV_COLS * sizeof(double2), h->C, (size_t)h->nemb * sizeof(double2),
-                                      (size_t)INV_COLS * sizeof(double2), rows, hipMemcpyDeviceToDevice, ctx->stream));
+        DMK_HIP(ctx, hipMemcpy2DAsync(cache->cols, (size_t)ncols * sizeof(double2), h->C, (size_t)h->nemb * sizeof(double2),
+                                      (size_t)ncols * sizeof(double2), rows, hipMemcpyDeviceToDevice, ctx->stream));
         for (int i = 0; i < 7; ++i) cache->shape[i] = shape[i];
+        cache->tab_A = tab_A;
+        cache->ncols = ncols;
         cache->cols_rows = rows;
         cache->have_cols = true;
     }
     h->cache = cache;
+    h->inv_A = tab_A;
     if (attached) *attached = 1;
     return DMK_OK;
+}
+
+int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached) {
+    if (!h || !cache) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (attached) *attached = 0;
+    if (cache->ctx != ctx) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_attach_cache: the cache belongs to another context");
+    if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_attach_cache: a kL is in progress");
+    // only the grouped nemb = 256 path has the workgroup types the region is made of; the partner term and Re-only planes need time reversal
+    if (!h->hot256 || h->group <= 1 || !h->tr || h->imag || h->sub_planes || h->nemb != 256) return DMK_OK;
+    return inv_attach(h, cache, 0, INV_COLS, attached);
+}
+
+int dmk_eri_attach_cache_cols(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *attached, int *cols_used) {
+    if (!h || !cache) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (attached) *attached = 0;
+    if (cols_used) *cols_used = 0;
+    if (cache->ctx != ctx) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_attach_cache_cols: the cache belongs to another context");
+    if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_attach_cache_cols: a kL is in progress");
+    int att = 0, rc;
+    if (h->hot256) {
+        // the region of the nemb = 256 kernel is fixed: all of its INV_COLS columns must be invariant
+        if (ninv < INV_COLS) return DMK_OK;
+        rc = dmk_eri_attach_cache(h, cache, &att);
+        if (rc == DMK_OK && att && cols_used) *cols_used = INV_COLS;
+    } else {
+        // the grouped table path; the partner term and Re-only planes need time reversal, sub-group copies hold parts of the planes
+        if (h->group <= 1 || !h->tr || h->imag || h->sub_planes || !half2_tab_usable(h->nao, h->nemb)) return DMK_OK;
+        const int A = 16 * (std::min(ninv, h->nemb) / 16);
+        if (A < 16) return DMK_OK;
+        rc = inv_attach(h, cache, A, A, &att);
+        if (rc == DMK_OK && att && cols_used) *cols_used = A;
+    }
+    if (attached) *attached = att;
+    return rc;
 }
 
 int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64) {

@@ -302,8 +302,11 @@ bool tab_enabled() {
 }
 
 // Host side of the decomposition described at the top: items of the lower block triangle and the per-wave block lists.
-void build_table(int nemb, int T_MAXBLK, int T_SEG, std::vector<int> &tab, double &useful_blocks, double &slots, double &folded) {
+// `lo` (first block row): only blocks with global block row R >= lo are dealt out -- the table of a launch whose planes already
+// hold the pairs (a, b) with b <= a < 16 lo (the invariant region of dmk_eri_cache).  lo = 0 is the dense table.
+void build_table(int nemb, int T_MAXBLK, int T_SEG, int lo, std::vector<int> &tab, double &useful_blocks, double &slots, double &folded) {
     const int nb = (nemb + 15) / 16;
+    lo = std::max(0, std::min(lo, nb));
     tab.clear();
     useful_blocks = slots = folded = 0.0;
     auto push_item = [&](int kind, int R0, int C0, std::vector<std::pair<int, int>> lists[4]) {
@@ -349,16 +352,17 @@ void build_table(int nemb, int T_MAXBLK, int T_SEG, std::vector<int> &tab, doubl
         // one per wave, then every off-diagonal block goes to the wave with the lightest load (ties: fewer blocks): C4 ->
         // nine waves of 3 + 1 blocks (7 segments) and three of 3 (6 segments), 81 of 84 slots; by block count (groups that
         // are not all symmetrised) the same lists are 4, 4, 4, 3 per workgroup.
-        const int nblk_all = nb * (nb + 1) / 2;
+        // With a first block row the same deal runs over the remaining block rows only, and the number of workgroups follows.
+        const int nblk_all = nb * (nb + 1) / 2 - lo * (lo + 1) / 2;
         const int nwg = (nblk_all + 4 * T_MAXBLK - 1) / (4 * T_MAXBLK);
         const int nw = 4 * nwg;
         std::vector<std::vector<std::pair<int, int>>> wl(nw);
         std::vector<int> load(nw, 0);
-        for (int d = 0; d < nb; ++d) {                                // diagonal blocks round-robin
-            wl[d % nw].push_back({d, d});
-            load[d % nw] += 1;
+        for (int d = lo; d < nb; ++d) {                               // diagonal blocks round-robin
+            wl[(d - lo) % nw].push_back({d, d});
+            load[(d - lo) % nw] += 1;
         }
-        for (int r = 0; r < nb; ++r)
+        for (int r = lo; r < nb; ++r)
             for (int c = 0; c < r; ++c) {
                 int best = -1;
                 for (int w = 0; w < nw; ++w) {
@@ -379,11 +383,13 @@ void build_table(int nemb, int T_MAXBLK, int T_SEG, std::vector<int> &tab, doubl
         }
         return;
     }
+    // An item keeps its origin and its panels and drops its block rows R < lo; one left without a block is not pushed.
     for (int s0 = 0; s0 < nb; s0 += T_SEG) {
         const int w = std::min(T_SEG, nb - s0);
+        if (s0 + w <= lo) continue;
         {   // diagonal triangle of width w: w (w + 1) / 2 <= 28 blocks, row-major, cut evenly over the four waves
             std::vector<std::pair<int, int>> all, lists[4];
-            for (int r = 0; r < w; ++r)
+            for (int r = std::max(0, lo - s0); r < w; ++r)
                 for (int c = 0; c <= r; ++c) all.push_back({r, c});
             even_split(all, lists);
             push_item(0, s0, s0, lists);
@@ -392,8 +398,9 @@ void build_table(int nemb, int T_MAXBLK, int T_SEG, std::vector<int> &tab, doubl
             const int cw = T_SEG;                           // earlier segments are always full
             for (int rh = 0; rh < w; rh += 4) {
                 const int rw = std::min(4, w - rh);
+                if (s0 + rh + rw <= lo) continue;
                 std::vector<std::pair<int, int>> all, lists[4];
-                for (int r = 0; r < rw; ++r)
+                for (int r = std::max(0, lo - s0 - rh); r < rw; ++r)
                     for (int c = 0; c < cw; ++c) all.push_back({r, c});
                 even_split(all, lists);
                 push_item(1, s0 + rh, t0, lists);
@@ -409,7 +416,6 @@ int half2_tab_usable(int nao, int nemb) {
 }
 int half2_tab_maxslot() { return T_MAXSLOT; }
 
-// Returns 1 if handled, 0 if the caller must use the generic kernel, < 0 on error.  Arguments as launch_half2_hot (zhot.hip).
 // Sub-groups of a step-2 launch (see H2TArgs): how many runs the queue of `nslot` blocks should be cut into so that the launch
 // has at least ~6 rounds of resident workgroups; 1 when it already has, or when the queue is too short to cut.
 int half2_tab_subgroups(dmk_ctx *ctx, int nL, int nao, int nemb, int nspin, int nslot, int max_sub) {
@@ -423,10 +429,28 @@ int half2_tab_subgroups(dmk_ctx *ctx, int nL, int nao, int nemb, int nspin, int 
     return std::max(1, std::min(std::min(p, max_sub), std::max(1, nslot / 2)));
 }
 
+// The host-side partition alone (libdmetk.h): no context, no GPU.
+extern "C" int dmk_half2_tab_table(int nemb, int occ, int first_row_block, int *table, int cap_ints, int *nitems, double stats[3]) {
+    if (nemb < 32 || nemb > 4096 || (occ != 2 && occ != 3) || first_row_block < 0 || !nitems) return DMK_ERR_INVALID;
+    std::vector<int> h;
+    double useful, slots, folded;
+    if (occ == 2) build_table(nemb, Cfg2::MAXBLK, Cfg2::SEG, first_row_block, h, useful, slots, folded);
+    else build_table(nemb, Cfg3::MAXBLK, Cfg3::SEG, first_row_block, h, useful, slots, folded);
+    *nitems = (int)(h.size() / T_ITEM);
+    if (stats) { stats[0] = useful; stats[1] = slots; stats[2] = folded; }
+    if (table) {
+        if ((size_t)cap_ints < h.size()) return DMK_ERR_INVALID;
+        std::copy(h.begin(), h.end(), table);
+    }
+    return DMK_OK;
+}
+
+// Returns 1 if handled, 0 if the caller must use the generic kernel, < 0 on error.  Arguments as launch_half2_hot (zhot.hip);
+// first_row_block: the launch leaves out the block rows below it (build_table), 1 without a launch when none is left.
 int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj, const int *sym,
                      double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
                      long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int nsub,
-                     double *planes_sub, long long sub_stride, int kdim, int re_only) {
+                     double *planes_sub, long long sub_stride, int kdim, int re_only, int first_row_block) {
     if (kdim == 0) kdim = nao;
     if (kdim < nao || (kdim % T_BK) != 0) return 0;
     if (!half2_tab_usable(nao, nemb) || nslot < 1 || nslot > T_MAXSLOT || nspin < 1 || nspin > 2) return 0;
@@ -440,14 +464,17 @@ int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int ns
     const char *occ_e = getenv("DMK_ERI_TAB_OCC");          // read per launch (a handful per second): tests toggle it
     const int occ_env = occ_e ? atoi(occ_e) : 0;
     const int occ = (occ_env == 2 || occ_env == 3) ? occ_env : ((nemb + 15) / 16 <= T_WIDE_MAXNB ? 3 : 2);
+    const int nb = (nemb + 15) / 16;
+    if (first_row_block < 0) first_row_block = 0;
+    if (first_row_block >= nb) return 1;                   // every block row is already in the planes: nothing to launch
     const dmk_ctx::StepTable *tb = nullptr;
     for (auto &t : ctx->step2_tables)
-        if (t.nemb == nemb && t.cfg == occ) tb = &t;
+        if (t.nemb == nemb && t.cfg == occ && t.lo == first_row_block) tb = &t;
     if (!tb) {
         std::vector<int> h;
         double useful, slots, folded;
-        if (occ == 2) build_table(nemb, Cfg2::MAXBLK, Cfg2::SEG, h, useful, slots, folded);
-        else build_table(nemb, Cfg3::MAXBLK, Cfg3::SEG, h, useful, slots, folded);
+        if (occ == 2) build_table(nemb, Cfg2::MAXBLK, Cfg2::SEG, first_row_block, h, useful, slots, folded);
+        else build_table(nemb, Cfg3::MAXBLK, Cfg3::SEG, first_row_block, h, useful, slots, folded);
         int *dev = nullptr;
         if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&dev), h.size() * sizeof(int)) != hipSuccess)
             return dmk_fail(ctx, DMK_ERR_NOMEM, "half2_tab: table allocation failed");
@@ -455,7 +482,7 @@ int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int ns
             (void)hipFree(dev);
             return dmk_fail(ctx, DMK_ERR_HIP, "half2_tab: table upload failed");
         }
-        ctx->step2_tables.push_back({nemb, occ, (int)(h.size() / T_ITEM), useful, folded, dev});
+        ctx->step2_tables.push_back({nemb, occ, first_row_block, (int)(h.size() / T_ITEM), useful, folded, dev});
         tb = &ctx->step2_tables.back();
     }
     H2TArgs a;

@@ -419,9 +419,11 @@ def eri_stage(ctx, sysm, d_C, nemb, eri_dev, kL_list=None, timers=None, max_bloc
     inv = None
     if os.environ.get("DMK_ERI_INV", "1") != "0":
         inv = getattr(sysm, "eri_inv_cache", None)
-        if inv is None and nemb == 256 and len(sysm.imp_idx) >= 192:
+        nimp = len(sysm.imp_idx)
+        if inv is None and ((nemb == 256 and nimp >= 192) or (nemb != 256 and nimp >= 16)):
             inv = sysm.eri_inv_cache = et.EriInvariantCache(ctx)
-    eng = et.EriEngine(ctx, sysm.mesh, sysm.nao, sysm.naux, nemb, sysm.spin, d_C, eri_dev, True, inv_cache=inv)
+    eng = et.EriEngine(ctx, sysm.mesh, sysm.nao, sysm.naux, nemb, sysm.spin, d_C, eri_dev, True, inv_cache=inv,
+                       inv_cols=len(sysm.imp_idx))
     rows = None
     try:
         todo = eng.irreducible_kL() if kL_list is None else list(kL_list)
