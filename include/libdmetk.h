@@ -385,6 +385,24 @@ int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]);
 int dmk_eri_attach_cache(dmk_eri *h, dmk_eri_cache *cache, int *attached);
 int dmk_eri_attach_cache_cols(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *attached, int *cols_used);
 int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64);
+/* The invariant block of the RESULT.  The pairs (a, b) with b <= a < n_e, n_e = min(ninv, nemb), are the prefix [0, P) of the packed
+ * pair index, P = n_e (n_e + 1) / 2, and their plane entries depend on columns [0, n_e) of C_ao_emb alone: the corner
+ * eri[blk][0 : S 128, 0 : S 128], S = floor(P / 128), of every spin block comes out the same, bit for bit, whenever the same kL
+ * are contracted in the same order into a zeroed ERI.  The cache keeps ONE such corner (spin_blocks x (S 128)^2 doubles, out of the
+ * cache's budget); a later contraction of the same plane set leaves those tiles out of every launch and copies the corner back.
+ *   dmk_eri_attach_cache_block : call it after dmk_eri_attach_cache(_cols) accepted the same cache, before the first kL.
+ *       *tiles = S when the block is armed, 0 when not: S < 1, a pipeline without an ERI of its own, without time reversal or
+ *       with the imaginary-part accumulator, or a contraction off the LDS-DMA kernel.  Not for the GSO contraction.
+ *       Columns [ncols, n_e) of C_ao_emb beyond the ones the plane entries compare are compared bitwise as well: a difference
+ *       there (or another n_e) drops the block alone.  `ninv` is a hint: claiming too much only costs the hits.
+ *   It applies to the stacked contraction of everything (dmk_eri_contract(-1, -1), a full stack, dmk_eri_finish) when every
+ *   resident kL was begun with dmk_eri_begin_kL_cached and a device check finds the corner of the ERI exactly zero; never to the
+ *   single-slot dmk_eri_end_kL, a band or dmk_eri_contract_rows.  The key of the entry is a hash of the shape, n_e, S, the
+ *   slots-per-launch rule and (kL, key64, weight, Re-only flag) of every resident kL in contraction order.  Unknown key: the
+ *   contraction runs dense and its corner replaces the entry (when the budget holds it).  Everything else runs dense.
+ *   dmk_eri_cache_block_stats : hits, misses, bytes of the entry, S of the entry. */
+int dmk_eri_attach_cache_block(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *tiles);
+int dmk_eri_cache_block_stats(const dmk_eri_cache *cache, int64_t stats[4]);
 /* The block-ownership table of the table-driven step-2 kernel, built on the host (no context, no GPU): the lower triangle of the
  * nb x nb grid of 16 x 16 blocks (nb = ceil(nemb / 16)) without the block rows below `first_row_block`, dealt out to workgroups
  * ("items") of four waves.  `occ` is the occupancy point, 2 (lists of up to 8 blocks per wave) or 3 (up to 5).  *nitems items of
@@ -478,6 +496,18 @@ int dmk_dgemm_tn_acc(dmk_ctx *ctx, int N, int K, double alpha, const double *X,
  * routine/bcs.py:92. */
 int dmk_dgemm_tn_acc_rect(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx,
                           const double *Y, int64_t ldy, double *C, int64_t ldc);
+/* The rectangular form without the corner of 128 x 128 tiles tm < skip_tiles && tn < skip_tiles (tm: tile row, tn: tile column):
+ * those tiles are not computed and that part of C is neither read nor written -- X == Y with equal strides and M == N runs the
+ * symmetric launch, whose mirrored writes stay outside the corner too.  skip_tiles = 0 is dmk_dgemm_tn_acc_rect.  Only the
+ * LDS-DMA kernel can leave tiles out (K a multiple of 8, even M, N, ldx, ldy, 16-byte aligned X, Y): other arguments with
+ * skip_tiles > 0 are refused with DMK_ERR_STATE, never run dense. */
+int dmk_dgemm_tn_acc_skip(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx, const double *Y,
+                          int64_t ldy, double *C, int64_t ldc, int skip_tiles);
+/* The tile visiting order of that kernel, built on the host (no context, no GPU): entries (tm << 16 | tn) of a tiles_m x tiles_n
+ * grid of tiles; symm != 0 (tiles_m == tiles_n): tiles with tm >= tn only; [lo, hi): band of tile columns (symm) or tile rows
+ * (-1, -1: all); skip: the corner tm < skip && tn < skip is left out and the order of the other tiles stays.  *n entries are
+ * written to `out` (NULL: only *n is set; else `capacity` entries must hold them). */
+int dmk_dgemm_tile_table(int tiles_m, int tiles_n, int symm, int lo, int hi, int skip, unsigned *out, int64_t capacity, int64_t *n);
 /* Full SVD of a small square matrix A = U diag(sigma) Vt (one-sided Jacobi, n <= 84; sigma descending;
  * columns of U belonging to exactly zero singular values are returned as zero).  Replaces
  * scipy.linalg.svd at dmet/HubPhSymm.py:42. */

@@ -94,6 +94,9 @@ PROTOTYPES = {
     "dmk_eri_attach_cache": (c_int, [c_vp, c_vp, P(c_int)]),
     "dmk_eri_attach_cache_cols": (c_int, [c_vp, c_vp, c_int, P(c_int), P(c_int)]),
     "dmk_eri_begin_kL_cached": (c_int, [c_vp, c_int, c_int, C.c_uint64]),
+    "dmk_eri_attach_cache_block": (c_int, [c_vp, c_vp, c_int, P(c_int)]),
+    "dmk_eri_cache_block_stats": (c_int, [c_vp, P(c_i64)]),
+    "dmk_dgemm_tile_table": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P(C.c_uint32), c_i64, P(c_i64)]),
     "dmk_half2_tab_table": (c_int, [c_int, c_int, c_int, P(c_int), c_int, P(c_int), P(C.c_double)]),
     "dmk_eri_contract": (c_int, [c_vp, c_int, c_int, c_int]),
     "dmk_eri_probe": (c_int, [c_vp, c_vp, c_vp]),
@@ -110,6 +113,7 @@ PROTOTYPES = {
     "dmk_eri_restore": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
     "dmk_dgemm_tn_acc": (c_int, [c_vp, c_int, c_int, c_dbl, c_vp, c_vp, c_i64, c_vp, c_i64]),
     "dmk_dgemm_tn_acc_rect": (c_int, [c_vp, c_int, c_int, c_int, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
+    "dmk_dgemm_tn_acc_skip": (c_int, [c_vp, c_int, c_int, c_int, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int]),
     "dmk_svd_small": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "dmk_dgemm_nn_small": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
     "dmk_bcs_weight": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),

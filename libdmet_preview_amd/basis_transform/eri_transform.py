@@ -940,6 +940,10 @@ class EriInvariantCache(object):
     (half of the block products at nemb = 256, 40 - 50 % at nemb 136 - 272 with a typical impurity).  A hit is only ever
     made legal by the library's bitwise compare of columns [0,192) / [0,A) of C_ao_emb on the device plus the key of the kL
     (`inv_key64`).
+    The cache also keeps ONE invariant block of the RESULT (`EriEngine(inv_block=True)`, dmk_eri_attach_cache_block): the corner
+    of S x S tiles of 128 pair indices of every spin block that belongs to the pairs b <= a < inv_cols.  A stacked contraction of
+    the same keyed kL, in the same order, into a zeroed ERI leaves those tiles out of every launch and copies the corner back;
+    `block_stats()` counts that.  It shares the budget with the plane entries.
     `budget_gb`: default DMK_ERI_INV_GB (64), capped by the library at a quarter of the free device memory; never evicts."""
 
     def __init__(self, ctx, budget_gb=None):
@@ -954,6 +958,12 @@ class EriInvariantCache(object):
         v = (C.c_int64 * 5)()
         self.ctx.check(lib.dmk_eri_cache_stats(self.h, v))
         return {"hits": int(v[0]), "misses": int(v[1]), "entries": int(v[2]), "bytes": int(v[3]), "drops": int(v[4])}
+
+    def block_stats(self):
+        """The invariant block of the result: contractions that used it / that could not, bytes and tiles per side of the entry."""
+        v = (C.c_int64 * 4)()
+        self.ctx.check(lib.dmk_eri_cache_block_stats(self.h, v))
+        return {"hits": int(v[0]), "misses": int(v[1]), "bytes": int(v[2]), "tiles": int(v[3])}
 
     def drop(self):
         """Forget every entry (and the stored columns)."""
@@ -975,7 +985,7 @@ class EriEngine(object):
     """Owns a dmk_eri pipeline: plan -> (begin_kL, push_block*, end_kL)* on one GPU."""
 
     def __init__(self, ctx, kmesh, nao, naux, nemb, spin, C_ao_emb_dev, eri_dev, t_reversal_symm=True, gso=False, plan=None,
-                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None):
+                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None, inv_block=True):
         """`plan` = (weights, records) of `general_plan` for k lists that are not the np.fft-ordered Gamma-centred mesh
         (then `kmesh` only carries the number of k-points, [nk, 1, 1]); default: the integer-mesh plan of libdmetk.
         `inv_cache`: an EriInvariantCache; the library attaches it only where the invariant region exists (the grouped
@@ -984,6 +994,9 @@ class EriEngine(object):
         `inv_cols`: how many leading columns of C_ao_emb the caller expects to stay the same (the impurity orbitals).  With it
         the cache also attaches on the table-driven path of any other embedding dimension (dmk_eri_attach_cache_cols), and
         `self.inv_cols_used` tells how many columns are stored and compared (192, or 16 floor(inv_cols / 16); 0: not attached).
+        `inv_block`: with an attached cache also arm the invariant block of the result for the stacked contraction
+        (dmk_eri_attach_cache_block) over `inv_cols` columns, or the compared columns of the region when no hint is given;
+        `self.inv_block_tiles` tells its size in tiles of 128 pair indices (0: not armed).
         `rows_only`: a pipeline WITHOUT an ERI of its own (`eri_dev` may be None): its planes are only ever taken slab-wise
         with `contract_rows_into`; every path that would contract into an internal ERI refuses instead (dmk_eri_begin flag 4).
         `track_imag`: without time reversal also accumulate the imaginary part of the contraction for the reference's
@@ -1027,6 +1040,12 @@ class EriEngine(object):
             self.inv_cols_used = int(used.value)
             if self.inv_attached:
                 self.inv_cache = inv_cache                # (kept alive while the pipeline holds its address)
+        self.inv_block_tiles = 0
+        if self.inv_attached and inv_block and not rows_only:
+            tiles = C.c_int(0)
+            ncols = int(inv_cols) if inv_cols is not None else (self.inv_cols_used or 192)
+            ctx.check(lib.dmk_eri_attach_cache_block(self.h, inv_cache.h, ncols, C.byref(tiles)))
+            self.inv_block_tiles = int(tiles.value)
 
     def irreducible_kL(self):
         return [kL for kL in range(len(self.weights)) if self.weights[kL] > 0]

@@ -37,8 +37,8 @@ struct dmk_ctx {
     // dmk_eri_begin so that a self-consistency loop does not pay hipMalloc of it (~0.25 s) every iteration
     void *eri_ws[3] = {nullptr, nullptr, nullptr};   // planes, Ut, AO-block ring: parked between pipelines
     size_t eri_ws_bytes[3] = {0, 0, 0};
-    // tile visiting orders of the contraction kernel (dgemm_tn.hip), one per (tiles_m, tiles_n, symm)
-    struct TileTable { int tiles_m, tiles_n, symm, lo, hi; unsigned count; unsigned *dev; };
+    // tile visiting orders of the contraction kernel (dgemm_tn.hip), one per (tiles_m, tiles_n, symm, band, skipped corner)
+    struct TileTable { int tiles_m, tiles_n, symm, lo, hi, skip; unsigned count; unsigned *dev; };
     std::vector<TileTable> tile_tables;
     // block-ownership tables of the general-nemb step-2 kernel (zhot_tab.hip), one per embedding dimension, occupancy point and
     // first block row (lo > 0: the warm tables of the invariant planes cache)
@@ -249,7 +249,11 @@ int launch_dgemm_tn_acc(dmk_ctx *ctx, int M, int N, int K, double alpha, const d
 // Mp / Np (0: M / N): columns of X / Y that may be loaded, zero beyond M / N -- an odd M padded to the even row length of the planes
 int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx, const double *Y,
                             int64_t ldy, double *C, int64_t ldc, int seg_rows, int64_t seg_stride_x, int64_t seg_stride_y,
-                            int band_lo, int band_hi, int Mp = 0, int Np = 0);
+                            int band_lo, int band_hi, int Mp = 0, int Np = 0, int skip_tiles = 0);
+// skip_tiles > 0 leaves the tiles tm < skip_tiles && tn < skip_tiles out; only the LDS-DMA kernel can: this predicate (same
+// arguments) tells whether the launch would run there.  A launch with skip_tiles > 0 that would not is refused (DMK_ERR_STATE).
+bool dgemm_tn_can_skip(int M, int N, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, int seg_rows,
+                       int64_t seg_stride_x, int64_t seg_stride_y, int Mp, int Np);
 
 struct ZSeg {
     const void *A = nullptr;   // complex (or real if a_real) operand A

@@ -320,16 +320,12 @@ __global__ __launch_bounds__(NTHREADS, 3) void dgemm_tn_acc_dma_kernel(
 // [lo, hi): restriction to a band of tiles -- tile COLUMNS tn for the symmetric launch (its direct writes then cover the
 // lower part of that column band and its mirrored writes the rows of the band right of the diagonal: after the bands
 // 0 .. b have run, the ROWS of band b are complete), tile ROWS tm for the rectangular one.  (-1, -1) = everything.
-static const unsigned *dgemm_tile_table(dmk_ctx *ctx, int tiles_m, int tiles_n, bool symm, unsigned *count_out, int lo = -1,
-                                        int hi = -1) {
-    for (auto &t : ctx->tile_tables)
-        if (t.tiles_m == tiles_m && t.tiles_n == tiles_n && t.symm == (int)symm && t.lo == lo && t.hi == hi) {
-            *count_out = t.count;
-            return t.dev;
-        }
+// skip: the corner tm < skip && tn < skip is left out, the order of the other tiles stays (skip = 0: the table as it always
+// was).  The mirror of a kept tile of the symmetric launch has tile column tm >= skip, so the corner of C is not touched at all.
+static void dgemm_tile_table_host(int tiles_m, int tiles_n, bool symm, int lo, int hi, int skip, std::vector<unsigned> &h) {
     int SB = 8;
     if (const char *e = getenv("DMK_DGEMM_SUPER")) SB = atoi(e) > 0 ? atoi(e) : 8;     // ablation: 1 = plain row-major order
-    std::vector<unsigned> h;
+    h.clear();
     const int sm = (tiles_m + SB - 1) / SB, sn = (tiles_n + SB - 1) / SB;
     for (int Tm = 0; Tm < sm; ++Tm) {
         const int ncol = symm ? Tm + 1 : sn;
@@ -340,33 +336,85 @@ static const unsigned *dgemm_tile_table(dmk_ctx *ctx, int tiles_m, int tiles_n, 
                     const int tm = Tm * SB + im, tn = Tn * SB + jn;
                     if (tm >= tiles_m || tn >= tiles_n || (symm && tn > tm)) continue;
                     if (lo >= 0 && ((symm ? tn : tm) < lo || (symm ? tn : tm) >= hi)) continue;
+                    if (tm < skip && tn < skip) continue;
                     h.push_back(((unsigned)tm << 16) | (unsigned)tn);
                 }
         }
     }
+}
+
+static const unsigned *dgemm_tile_table(dmk_ctx *ctx, int tiles_m, int tiles_n, bool symm, unsigned *count_out, int lo, int hi,
+                                        int skip) {
+    for (auto &t : ctx->tile_tables)
+        if (t.tiles_m == tiles_m && t.tiles_n == tiles_n && t.symm == (int)symm && t.lo == lo && t.hi == hi && t.skip == skip) {
+            *count_out = t.count;
+            return t.dev;
+        }
+    std::vector<unsigned> h;
+    dgemm_tile_table_host(tiles_m, tiles_n, symm, lo, hi, skip, h);
     unsigned *dev = nullptr;
     if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&dev), std::max<size_t>(h.size(), 1) * sizeof(unsigned)) != hipSuccess) return nullptr;
     if (!h.empty() && hipMemcpy(dev, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(dev);
         return nullptr;
     }
-    ctx->tile_tables.push_back({tiles_m, tiles_n, (int)symm, lo, hi, (unsigned)h.size(), dev});
+    ctx->tile_tables.push_back({tiles_m, tiles_n, (int)symm, lo, hi, skip, (unsigned)h.size(), dev});
     *count_out = (unsigned)h.size();
     return dev;
 }
 
+// The table on the host, for tests and tools (no context, no GPU): packed (tm << 16 | tn) entries in visiting order.
+extern "C" int dmk_dgemm_tile_table(int tiles_m, int tiles_n, int symm, int lo, int hi, int skip, unsigned *out, int64_t capacity,
+                                    int64_t *n) {
+    if (!n || tiles_m < 0 || tiles_n < 0 || tiles_m >= 65536 || tiles_n >= 65536 || skip < 0 || (symm && tiles_m != tiles_n))
+        return DMK_ERR_INVALID;
+    std::vector<unsigned> h;
+    dgemm_tile_table_host(tiles_m, tiles_n, symm != 0, lo, hi, skip, h);
+    *n = (int64_t)h.size();
+    if (!out) return DMK_OK;
+    if (capacity < (int64_t)h.size()) return DMK_ERR_INVALID;
+    std::copy(h.begin(), h.end(), out);
+    return DMK_OK;
+}
+
+// Would a launch with these arguments run on the LDS-DMA kernel (the only one that walks a tile table)?
+static bool dgemm_dma_path(int M, int N, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, int seg_rows,
+                           int64_t seg_stride_x, int64_t seg_stride_y, int Mp, int Np) {
+    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    const bool vec2 = ((ldx & 1) == 0) && ((ldy & 1) == 0) &&
+                      ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
+                      ((reinterpret_cast<uintptr_t>(Y) & 15) == 0) && ((seg_stride_x & 1) == 0) && ((seg_stride_y & 1) == 0);
+    static const bool dma_enabled = [] { const char *e = getenv("DMK_DGEMM_DMA"); return !(e && atoi(e) == 0); }();
+    return dma_enabled && vec2 && (seg_rows % GBK) == 0 && K >= GBK && (Mp % 2) == 0 && (Np % 2) == 0 && Mp <= ldx && Np <= ldy &&
+           M >= 2 && N >= 2 && tiles_m < 65536 && tiles_n < 65536;
+}
+
+// Same arguments as launch_dgemm_tn_acc_seg: true when that launch could leave a corner of tiles out (skip_tiles > 0).
+bool dgemm_tn_can_skip(int M, int N, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, int seg_rows,
+                       int64_t seg_stride_x, int64_t seg_stride_y, int Mp, int Np) {
+    if (M <= 0 || N <= 0 || K <= 0) return false;
+    if (Mp < M) Mp = M;
+    if (Np < N) Np = N;
+    if (seg_rows <= 0 || seg_rows >= K) { seg_rows = K; seg_stride_x = seg_stride_y = 0; }
+    if (K % seg_rows) return false;
+    return dgemm_dma_path(M, N, K, X, ldx, Y, ldy, seg_rows, seg_stride_x, seg_stride_y, Mp, Np);
+}
+
 int launch_dgemm_tn_acc(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X,
                         int64_t ldx, const double *Y, int64_t ldy, double *C, int64_t ldc) {
-    return launch_dgemm_tn_acc_seg(ctx, M, N, K, alpha, X, ldx, Y, ldy, C, ldc, 0, 0, 0, -1, -1, 0, 0);
+    return launch_dgemm_tn_acc_seg(ctx, M, N, K, alpha, X, ldx, Y, ldy, C, ldc, 0, 0, 0, -1, -1, 0, 0, 0);
 }
 
 // The same product with (i) K given as K / seg_rows row segments that start seg_stride_x / seg_stride_y ELEMENTS apart
 // (seg_rows = 0: one contiguous segment) and (ii) the output restricted to the tile band [band_lo, band_hi) (128-row /
 // 128-column tiles; -1: everything) -- see dgemm_tile_table.  The ERI pipeline stacks the planes of many kL along K and
 // finishes the contraction band by band so that finished rows can be reduced over ranks while later bands are computed.
+// skip_tiles > 0: the tiles tm < skip_tiles && tn < skip_tiles are not computed and that corner of C is not touched (LDS-DMA
+// kernel only; a launch that would fall to the register-staged kernel is refused -- ask dgemm_tn_can_skip first).
 int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx, const double *Y,
                             int64_t ldy, double *C, int64_t ldc, int seg_rows, int64_t seg_stride_x, int64_t seg_stride_y,
-                            int band_lo, int band_hi, int Mp, int Np) {
+                            int band_lo, int band_hi, int Mp, int Np, int skip_tiles) {
+    if (skip_tiles < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn: negative skip_tiles");
     if (M <= 0 || N <= 0 || K <= 0) return DMK_OK;
     if (Mp < M) Mp = M;                 // loadable columns of X / Y (>= M / N, zero beyond): see the LDS-DMA kernel
     if (Np < N) Np = N;
@@ -378,13 +426,11 @@ int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, con
     const bool vec2 = ((ldx & 1) == 0) && ((ldy & 1) == 0) &&
                       ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
                       ((reinterpret_cast<uintptr_t>(Y) & 15) == 0) && ((seg_stride_x & 1) == 0) && ((seg_stride_y & 1) == 0);
-    static const bool dma_enabled = [] { const char *e = getenv("DMK_DGEMM_DMA"); return !(e && atoi(e) == 0); }();
-    if (dma_enabled && vec2 && (seg_rows % GBK) == 0 && K >= GBK && (Mp % 2) == 0 && (Np % 2) == 0 && Mp <= ldx && Np <= ldy &&
-        M >= 2 && N >= 2 && tiles_m < 65536 && tiles_n < 65536) {
+    if (dgemm_dma_path(M, N, K, X, ldx, Y, ldy, seg_rows, seg_stride_x, seg_stride_y, Mp, Np)) {
         static const bool symm_enabled = [] { const char *e = getenv("DMK_DGEMM_SYMM"); return !(e && atoi(e) == 0); }();
         const bool symm = symm_enabled && X == Y && ldx == ldy && seg_stride_x == seg_stride_y && M == N && tiles_m >= 2;
         unsigned count = 0;
-        const unsigned *table = dgemm_tile_table(ctx, tiles_m, tiles_n, symm, &count, band_lo, band_hi);
+        const unsigned *table = dgemm_tile_table(ctx, tiles_m, tiles_n, symm, &count, band_lo, band_hi, skip_tiles);
         if (!table) return dmk_fail(ctx, DMK_ERR_NOMEM, "dgemm_tn: tile table allocation failed");
         if (count == 0) return DMK_OK;
         const int seg_tiles = seg_rows / GBK;
@@ -409,6 +455,8 @@ int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, con
         DMK_CHECK_LAUNCH(ctx);
         return DMK_OK;
     }
+    if (skip_tiles > 0)     // (running dense here would add the corner a second time on top of what the caller puts there)
+        return dmk_fail(ctx, DMK_ERR_STATE, "dgemm_tn: skip_tiles = %d, but these arguments run on the register-staged kernel", skip_tiles);
     // register-staged kernel (odd sizes): one launch per segment; a band is a row range of C (no mirroring here, so every
     // band writes its own rows over the full width)
     int m_lo = 0, m_hi = M;

@@ -1,6 +1,6 @@
 // ERI pipeline of libdmetk (a11 - a14): the dmk_eri handle, the block queue (direct pushes, ring, resident groups, host feed), the
 // plane stack and its contractions (spin blocks, row slabs, GSO), the Freivalds probe hook and the iteration-invariant planes
-// cache (dmk_eri_cache).  The half-transform, contraction and probe kernels live in zhot*.hip, zgemm.hip, dgemm_tn.hip and
+// cache with its block of the result (dmk_eri_cache).  The half-transform, contraction and probe kernels live in zhot*.hip, zgemm.hip, dgemm_tn.hip and
 // eri_probe.hip; the device code here is a handful of small plane / staging kernels.
 #include "common.h"
 #include "kmesh.h"
@@ -93,6 +93,14 @@ struct dmk_eri {
     bool inv_warm = false, inv_save = false;
     int inv_A = 0;
     uint64_t inv_key = 0;
+    // invariant block of the result (dmk_eri_attach_cache_block): blk_S > 0 -- armed, the corner of blk_S x blk_S tiles of every spin
+    // block is a function of columns [0, blk_ne) of C alone.  slot_keys: what the planes resident in each stack slot were begun
+    // with (keyed: by dmk_eri_begin_kL_cached with the cache attached) -- the block's key is made of them.
+    int blk_S = 0, blk_ne = 0;
+    struct SlotKey { int kL; uint64_t key; int weight, re_only; bool keyed; };
+    std::vector<SlotKey> slot_keys;
+    uint64_t cur_key = 0;
+    bool cur_keyed = false;
     dmk_eri(dmk_ctx *c, const int m[3]) : ctx(c), mesh(m) {}
 
     double *slot_planes(int slot, int spin_idx) const {
@@ -221,6 +229,8 @@ extern "C" {
 
 static int eri_contract_stack(dmk_eri *h, int band_lo, int band_hi);
 static int inv_save_entry(dmk_eri *h);
+static int blk_decide(dmk_eri *h, int kchunk_w2, int kchunk_w1, int *skip, bool *save, uint64_t *key);
+static int blk_finish(dmk_eri *h, bool warm, bool save, uint64_t key);
 
 // =============================================================================================
 // begin / finish
@@ -366,6 +376,7 @@ static int eri_begin_kL_impl(dmk_eri *h, int kL, int weight) {
     h->cur_kL = kL;
     h->slot_reserved = -1;
     h->inv_warm = h->inv_save = false;
+    h->cur_keyed = false;
     return DMK_OK;
 }
 
@@ -783,12 +794,13 @@ static int eri_probe_slot(dmk_eri *h, int slot, int nrows, double w) {
 // The spin blocks aa (, ab, bb) of alpha X^T X over K plane rows starting at `slot`: C[b] += alpha X_a[:, row0 : row0 + M]^T X_b,
 // blocks `blk` doubles apart.  Mp: columns of X_a that may be loaded (M, or up to the padding column); seg_rows / seg_stride: K in
 // segments of seg_rows rows, seg_stride doubles apart (0: one contiguous range); [band_lo, band_hi): tile band of the pair index.
+// skip: the corner of skip x skip tiles of every block is left out (the invariant block of the result; full products only).
 static int eri_spin_products(dmk_eri *h, int slot, int64_t row0, int M, int Mp, int K, double alpha, double *C, size_t blk, int seg_rows,
-                             int64_t seg_stride, int band_lo, int band_hi) {
+                             int64_t seg_stride, int band_lo, int band_hi, int skip = 0) {
     const int64_t np = h->npair, pl = h->pl;
     auto gemm = [&](const double *A, const double *B, double *Cb) {
         return launch_dgemm_tn_acc_seg(h->ctx, M, (int)np, K, alpha, A + row0, pl, B, pl, Cb, np, seg_rows, seg_stride, seg_stride, band_lo,
-                                       band_hi, Mp, (int)pl);
+                                       band_hi, Mp, (int)pl, skip);
     };
     const double *X0 = h->slot_planes(slot, 0);
     int rc = gemm(X0, X0, C);
@@ -846,6 +858,8 @@ int dmk_eri_end_kL(dmk_eri *h, int weight) {
                             h->cur_weight);
         if (weight == 2) h->n_w2 += 1; else h->n_w1 += 1;
         h->probe_pending = true;
+        if ((int)h->slot_keys.size() < h->nslots) h->slot_keys.resize(h->nslots, dmk_eri::SlotKey{-1, 0, 0, 0, false});
+        h->slot_keys[h->cur_slot] = dmk_eri::SlotKey{h->cur_kL, h->cur_key, weight, h->re_only ? 1 : 0, h->cur_keyed};
     } else {
         if (!h->eri) return dmk_fail(ctx, DMK_ERR_STATE, "eri_end_kL: a pipeline without an ERI of its own needs a plane stack (dmk_eri_stack)");
         if (h->probe_x) {
@@ -904,16 +918,26 @@ static int eri_contract_stack(dmk_eri *h, int band_lo, int band_hi) {
         }
         h->probe_pending = false;
     }
+    // the invariant block of the result: a whole contraction into a zeroed corner either leaves the corner's tiles out of every
+    // launch and copies the kept corner back (warm) or runs dense and keeps its corner (cold); see blk_decide
+    int skip = 0;
+    bool save = false;
+    uint64_t bkey = 0;
+    if (band_lo < 0 && band_hi < 0 && h->blk_S > 0 && h->cache) {
+        int rc = blk_decide(h, kchunk_for(h->weight_class(2).seg_rows), kchunk_for(h->weight_class(1).seg_rows), &skip, &save, &bkey);
+        if (rc) return rc;
+    }
     for (int w = 2; w >= 1; --w) {
         const dmk_eri::WeightClass wc = h->weight_class(w);
         const int kchunk = kchunk_for(wc.seg_rows);
         for (int s0 = 0; s0 < wc.n; s0 += kchunk) {
             const int K = std::min(kchunk, wc.n - s0) * wc.seg_rows;
             int rc = eri_spin_products(h, wc.first + s0, 0, (int)np, (int)pl, K, wc.weight, h->eri, (size_t)np * np, wc.seg_rows, slot_stride,
-                                       band_lo, band_hi);
+                                       band_lo, band_hi, skip);
             if (rc) return rc;
         }
     }
+    if (skip > 0 || save) return blk_finish(h, skip > 0, save, bkey);
     return DMK_OK;
 }
 
@@ -1099,18 +1123,29 @@ struct dmk_eri_cache {
     struct Entry { int kL; uint64_t key; int re_only; double *buf; size_t bytes; };
     std::vector<Entry> entries;
     long long hits = 0, misses = 0, drops = 0;
+    // The invariant block of the result (one entry): the corner [0, blk_S 128)^2 of every spin block, [blocks][blk_S 128][blk_S 128],
+    // built from columns [0, blk_ne) of C_ao_emb -- [0, ncols) are the stored `cols`, [blk_lo, blk_ne) (blk_lo = ncols when the
+    // block was set up) are kept in blk_cols ([rows][blk_ne - blk_lo]).  blk_bytes counts against the budget while blk_buf is held.
+    int blk_ne = 0, blk_lo = 0, blk_S = 0;
+    double2 *blk_cols = nullptr;
+    double *blk_buf = nullptr;
+    size_t blk_bytes = 0;
+    bool blk_valid = false;
+    uint64_t blk_key = 0;
+    long long blk_hits = 0, blk_misses = 0;
     explicit dmk_eri_cache(dmk_ctx *c) : ctx(c) {}
 };
 
 namespace {
 // flag = 1 if any of the 128-bit patterns of columns [0, ncols) of C ([rows][nemb]) differs from cols ([rows][ncols]); n = rows x ncols
-__global__ void inv_cols_compare_kernel(long long n, int nemb, int ncols, const ulonglong2 *__restrict__ Cm,
+// (col0: the first compared column)
+__global__ void inv_cols_compare_kernel(long long n, int nemb, int ncols, int col0, const ulonglong2 *__restrict__ Cm,
                                         const ulonglong2 *__restrict__ cols, int *__restrict__ flag) {
     bool diff = false;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
         const long long row = t / ncols;
         const int col = (int)(t - row * ncols);
-        const ulonglong2 x = Cm[row * nemb + col], y = cols[t];
+        const ulonglong2 x = Cm[row * nemb + col0 + col], y = cols[t];
         diff = diff || x.x != y.x || x.y != y.y;
     }
     if (diff) *flag = 1;
@@ -1134,6 +1169,30 @@ __global__ void inv_region_copy_kernel(double *__restrict__ planes, double *__re
     double *p = planes + (long long)s * planes_spin_stride + ((long long)ri * pr + L) * pl + pair;
     double *q = entry + (((long long)s * nplanes + ri) * naux + L) * row + e;
     if (TO_PLANES) *p = *q; else *q = *p;
+}
+
+// The corner [0, n)^2 (n a multiple of 128) of `blocks` spin blocks of the ERI (row pitch np, blocks blk_stride doubles apart) <-> the
+// block entry [blocks][n][n].  One workgroup per 1024-column chunk of one row (cpr chunks per row): consecutive threads move
+// consecutive doubles, plain loads and stores.  MODE 0: corner -> entry, 1: entry -> corner, 2: flag = 1 if any bit of the corner is set.
+constexpr int BLK_CHUNK = 1024;
+template <int MODE>
+__global__ void blk_corner_kernel(double *__restrict__ eri, double *__restrict__ entry, long long n, long long np, long long blk_stride,
+                                  int cpr, int *__restrict__ flag) {
+    const long long id = blockIdx.x;
+    const int cx = (int)(id % cpr);
+    const long long rr = id / cpr, r = rr % n, b = rr / n;
+    double *p = eri + b * blk_stride + r * np;
+    double *q = entry + (b * n + r) * n;
+    bool set = false;
+#pragma unroll
+    for (int i = 0; i < BLK_CHUNK / 256; ++i) {
+        const long long c = (long long)cx * BLK_CHUNK + i * 256 + threadIdx.x;
+        if (c >= n) continue;
+        if (MODE == 0) q[c] = p[c];
+        else if (MODE == 1) p[c] = q[c];
+        else set = set || __double_as_longlong(p[c]) != 0;
+    }
+    if (MODE == 2 && set) *flag = 1;
 }
 
 // doubles per auxiliary row and plane of a cache entry of this pipeline's region
@@ -1161,7 +1220,7 @@ static int inv_save_entry(dmk_eri *h) {
     h->inv_save = false;
     if (!c) return DMK_OK;
     const size_t bytes = (size_t)h->spin * (h->re_only ? 1 : 2) * h->naux * inv_row_len(h) * sizeof(double);
-    if (c->held + bytes > c->budget) return DMK_OK;
+    if (c->held + c->blk_bytes + bytes > c->budget) return DMK_OK;
     double *buf = nullptr;
     if (dmk_dev_alloc(h->ctx, reinterpret_cast<void **>(&buf), bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -1174,8 +1233,21 @@ static int inv_save_entry(dmk_eri *h) {
     return DMK_OK;
 }
 
-// forget every entry (and, with `cols`, the columns they were built from)
+// forget the invariant block of the result and the columns kept for it
+static void blk_drop(dmk_eri_cache *c) {
+    if (c->blk_buf || c->blk_cols) (void)hipStreamSynchronize(c->ctx->stream);
+    if (c->blk_buf) (void)hipFree(c->blk_buf);
+    if (c->blk_cols) (void)hipFree(c->blk_cols);
+    c->blk_buf = nullptr;
+    c->blk_cols = nullptr;
+    c->blk_bytes = 0;
+    c->blk_valid = false;
+    c->blk_ne = c->blk_lo = c->blk_S = 0;
+}
+
+// forget every entry (and, with `cols`, the columns they were built from and the block of the result, which rests on them too)
 static void inv_cache_clear(dmk_eri_cache *c, bool cols) {
+    if (cols) blk_drop(c);
     if (!c->entries.empty() || (cols && c->cols)) (void)hipStreamSynchronize(c->ctx->stream);
     for (auto &e : c->entries) (void)hipFree(e.buf);
     c->drops += (long long)c->entries.size();
@@ -1241,7 +1313,7 @@ static int inv_attach(dmk_eri *h, dmk_eri_cache *cache, int tab_A, int ncols, in
         {
             FamScope fs(ctx, DMK_FAM_MISC);
             const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, n, h->nemb, ncols,
+            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, n, h->nemb, ncols, 0,
                                reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(cache->cols), cache->flag);
             DMK_CHECK_LAUNCH(ctx);
         }
@@ -1307,11 +1379,214 @@ int dmk_eri_attach_cache_cols(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *a
     return rc;
 }
 
+// =============================================================================================
+// the invariant block of the result
+// =============================================================================================
+
+int dmk_eri_cache_block_stats(const dmk_eri_cache *cache, int64_t stats[4]) {
+    if (!cache || !stats) return DMK_ERR_INVALID;
+    stats[0] = cache->blk_hits; stats[1] = cache->blk_misses;
+    stats[2] = cache->blk_valid ? (int64_t)cache->blk_bytes : 0; stats[3] = cache->blk_valid ? cache->blk_S : 0;
+    return DMK_OK;
+}
+
+// Would every launch of the stacked contraction run on the kernel that can leave tiles out?  Both weight classes (a class differs
+// in its segment length) and both spin operands (a launch of a later K chunk starts whole slots further on: the same alignment).
+static bool blk_can_skip(const dmk_eri *h) {
+    const int np = (int)h->npair, pl = (int)h->pl;
+    const int64_t slot_stride = 2LL * h->pr * h->pl;
+    for (int w = 2; w >= 1; --w) {
+        const dmk_eri::WeightClass wc = h->weight_class(w);
+        for (int s = 0; s < h->spin; ++s) {
+            const double *X = h->slot_planes(0, s);
+            if (!dgemm_tn_can_skip(np, np, wc.seg_rows, X, pl, X, pl, wc.seg_rows, slot_stride, slot_stride, pl, pl)) return false;
+        }
+    }
+    return true;
+}
+
+static unsigned blk_grid(const dmk_eri *h, long long n, int *cpr) {
+    *cpr = (int)((n + BLK_CHUNK - 1) / BLK_CHUNK);
+    return (unsigned)((long long)h->spin_blocks() * n * *cpr);
+}
+
+int dmk_eri_attach_cache_block(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *tiles) {
+    if (!h || !cache) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (tiles) *tiles = 0;
+    h->blk_S = h->blk_ne = 0;
+    if (cache->ctx != ctx) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_attach_cache_block: the cache belongs to another context");
+    if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_attach_cache_block: a kL is in progress");
+    if (h->cache != cache || !cache->have_cols) return DMK_OK;              // the planes of this pipeline are not keyed by this cache
+    if (!h->eri || !h->tr || h->imag) return DMK_OK;
+    const int n_e = std::min(ninv, h->nemb);
+    if (n_e < 1) return DMK_OK;
+    const long long P = (long long)n_e * (n_e + 1) / 2;
+    const int S = (int)(P / 128);
+    if (S < 1) return DMK_OK;
+    const long long n = (long long)S * 128;
+    if ((long long)h->spin_blocks() * n * ((n + BLK_CHUNK - 1) / BLK_CHUNK) > 0x7fffffffLL) return DMK_OK;    // grid of the corner kernels
+    if (!blk_can_skip(h)) return DMK_OK;
+    // columns [0, ncols) were compared when the planes attached (a difference there dropped the block too); the rest of [0, n_e) here
+    const int lo = std::min(cache->ncols, n_e), extra = n_e - lo;
+    const size_t rows = cache->cols_rows;
+    bool same = cache->blk_ne == n_e && cache->blk_lo == lo && (extra == 0 || cache->blk_cols);
+    if (same && extra > 0) {
+        const long long cnt = (long long)rows * extra;
+        DMK_HIP(ctx, hipMemsetAsync(cache->flag, 0, sizeof(int), ctx->stream));
+        {
+            FamScope fs(ctx, DMK_FAM_MISC);
+            const unsigned grid = (unsigned)std::min<long long>((cnt + 255) / 256, 4096);
+            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, cnt, h->nemb, extra, lo,
+                               reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(cache->blk_cols), cache->flag);
+            DMK_CHECK_LAUNCH(ctx);
+        }
+        int diff = 1;
+        DMK_HIP(ctx, hipMemcpyAsync(&diff, cache->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        same = diff == 0;
+    }
+    if (!same) {
+        blk_drop(cache);
+        if (extra > 0) {
+            if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&cache->blk_cols), rows * extra * sizeof(double2)) != hipSuccess) {
+                (void)hipGetLastError();
+                cache->blk_cols = nullptr;
+                return DMK_OK;                      // no room for the columns: the contraction stays dense
+            }
+            DMK_HIP(ctx, hipMemcpy2DAsync(cache->blk_cols, (size_t)extra * sizeof(double2), h->C + lo, (size_t)h->nemb * sizeof(double2),
+                                          (size_t)extra * sizeof(double2), rows, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        cache->blk_ne = n_e;
+        cache->blk_lo = lo;
+    }
+    h->blk_S = S;
+    h->blk_ne = n_e;
+    if (tiles) *tiles = S;
+    return DMK_OK;
+}
+
+static inline uint64_t blk_mix(uint64_t hsh, uint64_t v) {       // FNV-1a over the eight bytes of v
+    for (int i = 0; i < 8; ++i) {
+        hsh ^= (v >> (8 * i)) & 0xffu;
+        hsh *= 0x100000001b3ULL;
+    }
+    return hsh;
+}
+
+// Before a whole stacked contraction of an armed pipeline: *skip = S (warm: every launch leaves the corner out, blk_finish copies
+// the entry back), or *save (cold: dense, blk_finish keeps the corner), or neither (dense, nothing kept).  The corner of the result
+// is the kept one only when the same planes are summed in the same order on top of zeros: every resident kL must carry a key, the
+// key of the block covers them in contraction order with the slots-per-launch rule, and the corner of the ERI is checked on the
+// device to be zero bit for bit -- which also turns away a caller that did not zero the buffer, the later rounds of a stack
+// smaller than the kL list and another engine that has added to the same ERI.
+static int blk_decide(dmk_eri *h, int kchunk_w2, int kchunk_w1, int *skip, bool *save, uint64_t *key) {
+    dmk_ctx *ctx = h->ctx;
+    dmk_eri_cache *c = h->cache;
+    *skip = 0;
+    *save = false;
+    const int S = h->blk_S;
+    const long long n = (long long)S * 128;
+    if (h->n_w2 + h->n_w1 == 0) return DMK_OK;
+    uint64_t k = 0xcbf29ce484222325ULL;
+    const int64_t head[] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin, h->pr, h->pl, h->blk_ne, S,
+                            kchunk_w2, kchunk_w1, h->n_w2, h->n_w1};
+    for (int64_t v : head) k = blk_mix(k, (uint64_t)v);
+    for (int w = 2; w >= 1; --w) {
+        const dmk_eri::WeightClass wc = h->weight_class(w);
+        for (int i = 0; i < wc.n; ++i) {
+            const int slot = wc.first + i;
+            if (slot >= (int)h->slot_keys.size() || !h->slot_keys[slot].keyed) {       // planes without a key: not eligible
+                c->blk_misses += 1;
+                return DMK_OK;
+            }
+            const dmk_eri::SlotKey &sk = h->slot_keys[slot];
+            k = blk_mix(blk_mix(blk_mix(blk_mix(k, (uint64_t)sk.kL), sk.key), (uint64_t)sk.weight), (uint64_t)sk.re_only);
+        }
+    }
+    *key = k;
+    if (!blk_can_skip(h)) {
+        c->blk_misses += 1;
+        return DMK_OK;
+    }
+    int cpr;
+    const unsigned grid = blk_grid(h, n, &cpr);
+    DMK_HIP(ctx, hipMemsetAsync(c->flag, 0, sizeof(int), ctx->stream));
+    {
+        FamScope fs(ctx, DMK_FAM_MISC);
+        hipLaunchKernelGGL(blk_corner_kernel<2>, dim3(grid), dim3(256), 0, ctx->stream, h->eri, (double *)nullptr, n, (long long)h->npair,
+                           (long long)h->npair * h->npair, cpr, c->flag);
+        DMK_CHECK_LAUNCH(ctx);
+    }
+    int nonzero = 1;
+    DMK_HIP(ctx, hipMemcpyAsync(&nonzero, c->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (nonzero) {
+        c->blk_misses += 1;
+        return DMK_OK;
+    }
+    if (c->blk_valid && c->blk_buf && c->blk_key == k && c->blk_S == S && c->blk_ne == h->blk_ne) {
+        c->blk_hits += 1;
+        *skip = S;
+        return DMK_OK;
+    }
+    c->blk_misses += 1;
+    const size_t bytes = (size_t)h->spin_blocks() * (size_t)n * (size_t)n * sizeof(double);
+    *save = c->held + bytes <= c->budget;           // (the entry it replaces goes first)
+    return DMK_OK;
+}
+
+// After the launches of that contraction: the kept corner goes back into the ERI (warm) or the finished corner becomes the entry
+// (save; it replaces an older one; no memory: nothing is kept).
+static int blk_finish(dmk_eri *h, bool warm, bool save, uint64_t key) {
+    dmk_ctx *ctx = h->ctx;
+    dmk_eri_cache *c = h->cache;
+    const long long n = (long long)h->blk_S * 128;
+    int cpr;
+    const unsigned grid = blk_grid(h, n, &cpr);
+    if (warm) {
+        FamScope fs(ctx, DMK_FAM_MISC);
+        hipLaunchKernelGGL(blk_corner_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream, h->eri, c->blk_buf, n, (long long)h->npair,
+                           (long long)h->npair * h->npair, cpr, (int *)nullptr);
+        DMK_CHECK_LAUNCH(ctx);
+        return DMK_OK;
+    }
+    if (!save) return DMK_OK;
+    const size_t bytes = (size_t)h->spin_blocks() * (size_t)n * (size_t)n * sizeof(double);
+    c->blk_valid = false;
+    if (c->blk_buf && c->blk_bytes != bytes) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(c->blk_buf);
+        c->blk_buf = nullptr;
+        c->blk_bytes = 0;
+    }
+    if (!c->blk_buf) {
+        if (dmk_dev_alloc(ctx, reinterpret_cast<void **>(&c->blk_buf), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            c->blk_buf = nullptr;
+            return DMK_OK;
+        }
+        c->blk_bytes = bytes;
+    }
+    {
+        FamScope fs(ctx, DMK_FAM_MISC);
+        hipLaunchKernelGGL(blk_corner_kernel<0>, dim3(grid), dim3(256), 0, ctx->stream, h->eri, c->blk_buf, n, (long long)h->npair,
+                           (long long)h->npair * h->npair, cpr, (int *)nullptr);
+        DMK_CHECK_LAUNCH(ctx);
+    }
+    c->blk_key = key;
+    c->blk_S = h->blk_S;
+    c->blk_valid = true;
+    return DMK_OK;
+}
+
 int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64) {
     if (!h) return DMK_ERR_INVALID;
     int rc = eri_begin_kL_impl(h, kL, weight);
     if (rc || !h->cache) return rc;
     dmk_eri_cache *c = h->cache;
+    h->cur_key = key64;
+    h->cur_keyed = true;
     for (const auto &e : c->entries)
         if (e.kL == kL && e.key == key64 && e.re_only == (h->re_only ? 1 : 0)) {
             rc = inv_region_copy(h, e.buf, true);

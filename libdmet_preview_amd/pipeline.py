@@ -415,7 +415,8 @@ def eri_stage(ctx, sysm, d_C, nemb, eri_dev, kL_list=None, timers=None, max_bloc
     t = time.perf_counter()
     # iteration-invariant step-2 planes: the impurity columns of C_ao_emb come first and do not change between iterations.  The
     # tests below only avoid a cache that could never hit; what makes a hit legal is the library's bitwise compare of the columns
-    # (DMK_ERI_INV=0: the dense step 2 of every call, the A/B switch)
+    # (DMK_ERI_INV=0: the dense step 2 of every call, the A/B switch; DMK_ERI_INV_BLOCK=0: the planes are cached, but the
+    # contraction computes every tile of the result on every call)
     inv = None
     if os.environ.get("DMK_ERI_INV", "1") != "0":
         inv = getattr(sysm, "eri_inv_cache", None)
@@ -423,7 +424,7 @@ def eri_stage(ctx, sysm, d_C, nemb, eri_dev, kL_list=None, timers=None, max_bloc
         if inv is None and ((nemb == 256 and nimp >= 192) or (nemb != 256 and nimp >= 16)):
             inv = sysm.eri_inv_cache = et.EriInvariantCache(ctx)
     eng = et.EriEngine(ctx, sysm.mesh, sysm.nao, sysm.naux, nemb, sysm.spin, d_C, eri_dev, True, inv_cache=inv,
-                       inv_cols=len(sysm.imp_idx))
+                       inv_cols=len(sysm.imp_idx), inv_block=os.environ.get("DMK_ERI_INV_BLOCK", "1") != "0")
     rows = None
     try:
         todo = eng.irreducible_kL() if kL_list is None else list(kL_list)
