@@ -652,21 +652,24 @@ int dmk_dgemm_tn_acc(dmk_ctx *ctx, int N, int K, double alpha, const double *X, 
                      double *C, int64_t ldc) {
     if (!ctx) return DMK_ERR_INVALID;
     if (N < 0 || K < 0 || !X || !Y || !C) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn_acc: bad arguments");
-    return launch_dgemm_tn_acc(ctx, N, N, K, alpha, X, ldxy, Y, ldxy, C, ldc);
+    return dmk_dgemm_tn_acc_skip(ctx, N, N, K, alpha, X, ldxy, Y, ldxy, C, ldc, 0);
 }
 
 int dmk_dgemm_tn_acc_rect(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx,
                           const double *Y, int64_t ldy, double *C, int64_t ldc) {
     if (!ctx) return DMK_ERR_INVALID;
     if (M < 0 || N < 0 || K < 0 || !X || !Y || !C) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn_acc_rect: bad arguments");
-    return launch_dgemm_tn_acc(ctx, M, N, K, alpha, X, ldx, Y, ldy, C, ldc);
+    return dmk_dgemm_tn_acc_skip(ctx, M, N, K, alpha, X, ldx, Y, ldy, C, ldc, 0);
 }
 
 int dmk_dgemm_tn_acc_skip(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx, const double *Y,
                           int64_t ldy, double *C, int64_t ldc, int skip_tiles) {
     if (!ctx) return DMK_ERR_INVALID;
     if (M < 0 || N < 0 || K < 0 || !X || !Y || !C || skip_tiles < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn_acc_skip: bad arguments");
-    return launch_dgemm_tn_acc_seg(ctx, M, N, K, alpha, X, ldx, Y, ldy, C, ldc, 0, 0, 0, -1, -1, 0, 0, skip_tiles);
+    DgemmTn g;
+    g.M = M; g.N = N; g.K = K; g.alpha = alpha;
+    g.X = X; g.ldx = ldx; g.Y = Y; g.ldy = ldy; g.C = C; g.ldc = ldc; g.skip_tiles = skip_tiles;
+    return launch_dgemm_tn_acc(ctx, g);
 }
 
 int dmk_df_block_philox(dmk_ctx *ctx, uint64_t seed, int ki, int kj, int naux, int nao, void *out) {

@@ -242,18 +242,22 @@ __device__ double dmk_wave_sum(double v);
 
 // ---- launchers implemented in the .hip files ---------------------------------------------
 
-// C (M x N, ldc) += alpha * X^T Y;  X: K x M (ldx), Y: K x N (ldy)
-int launch_dgemm_tn_acc(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X,
-                        int64_t ldx, const double *Y, int64_t ldy, double *C, int64_t ldc);
-// K as a stack of row segments and / or the output restricted to a band of 128-wide tiles (dgemm_tn.hip)
-// Mp / Np (0: M / N): columns of X / Y that may be loaded, zero beyond M / N -- an odd M padded to the even row length of the planes
-int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx, const double *Y,
-                            int64_t ldy, double *C, int64_t ldc, int seg_rows, int64_t seg_stride_x, int64_t seg_stride_y,
-                            int band_lo, int band_hi, int Mp = 0, int Np = 0, int skip_tiles = 0);
-// skip_tiles > 0 leaves the tiles tm < skip_tiles && tn < skip_tiles out; only the LDS-DMA kernel can: this predicate (same
-// arguments) tells whether the launch would run there.  A launch with skip_tiles > 0 that would not is refused (DMK_ERR_STATE).
-bool dgemm_tn_can_skip(int M, int N, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, int seg_rows,
-                       int64_t seg_stride_x, int64_t seg_stride_y, int Mp, int Np);
+// C (M x N, ldc) += alpha * X^T Y;  X: K x M (ldx), Y: K x N (ldy)   (dgemm_tn.hip)
+struct DgemmTn {
+    int M = 0, N = 0, K = 0;
+    double alpha = 1.0;
+    const double *X = nullptr, *Y = nullptr;
+    double *C = nullptr; int64_t ldx = 0, ldy = 0, ldc = 0;
+    int seg_rows = 0;                             // K as K / seg_rows row segments (0: one contiguous range) ...
+    int64_t seg_stride_x = 0, seg_stride_y = 0;   // ... that start this many ELEMENTS apart
+    int band_lo = -1, band_hi = -1;               // output restricted to the band [band_lo, band_hi) of 128-wide tiles (-1: everything)
+    int Mp = 0, Np = 0;      // (0: M / N) loadable columns of X / Y, zero beyond M / N -- an odd M padded to the even row length of the planes
+    int skip_tiles = 0;      // > 0: the tiles tm < skip_tiles && tn < skip_tiles are left out (LDS-DMA kernel only)
+};
+int launch_dgemm_tn_acc(dmk_ctx *ctx, const DgemmTn &g);
+// Only the LDS-DMA kernel can leave tiles out: this predicate tells whether the launch of `g` would run there (both normalise `g`
+// with the same code).  A launch with skip_tiles > 0 that would not is refused (DMK_ERR_STATE).
+bool dgemm_tn_can_skip(const DgemmTn &g);
 
 struct ZSeg {
     const void *A = nullptr;   // complex (or real if a_real) operand A
@@ -306,26 +310,44 @@ int launch_philox_blocks_on(dmk_ctx *ctx, hipStream_t stream, uint64_t seed, int
 // pipeline's own, initialised one (its rows of the padding are read against those zeros).
 int hot_kdim(int nao);
 int half1_hot_max_rows(int nao);     // auxiliary rows per step-1 launch (32-bit lane offsets: < 4 GiB of the AO block)
-int launch_half1_hot(dmk_ctx *ctx, const void *Lpq, const void *Ci, void *Ut, int nL, int nao, int nemb, int nspin = 1,
-                     long long ci_spin_stride = 0, long long ut_spin_stride = 0, int kdim = 0);
-int launch_half1_hot_multi(dmk_ctx *ctx, const void *Lpq, long long a_slot_stride, int nslot, const int *ki, const void *C,
-                           void *Ut, long long ut_slot_stride, int nL, int nao, int nemb, int nspin, long long ci_spin_stride,
-                           long long ut_spin_stride, int kdim = 0);
-int launch_half2_hot(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj,
-                     const int *sym, double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
-                     long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int kdim = 0, int re_only = 0,
-                     int skip_invariant = 0);
+// Step 1 of `nslot` queued AO blocks in one launch: block s at Lpq + s * a_slot_stride is transformed with the C_i of its k point
+// into Ut + s * ut_slot_stride; both spin channels share the AO block and sit at constant strides in C and Ut.
+struct Half1Launch {
+    const void *Lpq = nullptr;           // [nslot][nL][nao][nao]
+    const void *C = nullptr;             // [spin][nk][kdim][nemb], or the one C_i of every slot (ki == nullptr)
+    void *Ut = nullptr;                  // [spin][nslot][nL][nao][nemb]
+    int nslot = 1; const int *ki = nullptr;             // k point of every slot: its C_i is C + ki[s] * kdim * nemb
+    long long a_slot_stride = 0, ut_slot_stride = 0;    // elements between the queued blocks
+    int nL = 0, nao = 0, nemb = 0, nspin = 1;
+    long long ci_spin_stride = 0, ut_spin_stride = 0;   // elements between the spin channels
+    int kdim = 0;                        // K loop bound (see above)
+};
+int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q);
+// Step 2 of `nslot` queued blocks in one launch, by the nemb = 256 kernel (zhot.hip) or the table-driven one for a general
+// embedding dimension (zhot_tab.hip).  A launcher refuses (DMK_ERR_INVALID) a field of the other kernel that is not at its default.
+struct Half2Launch {
+    const void *Ut = nullptr;            // [nslot][nL][nao][nemb]: step-1 outputs of `nslot` consecutive AO blocks
+    long long slot_stride = 0; int nslot = 0;   // elements between the Ut of consecutive slots
+    const void *const *Cj = nullptr;     // [nslot]: C_j ([kdim][nemb]) of every block
+    const int *sym = nullptr;            // [nslot]: add the time-reversal partner term of the block?
+    double *planes = nullptr;            // [(ri * plane_rows + L) * row_len + pair], ACCUMULATED
+    long long plane_rows = 0, row_len = 0;   // rows of a Re / Im plane and doubles per row (the pipeline's pr, pl)
+    int nL = 0, nao = 0, nemb = 0, nspin = 1;
+    long long ut_spin_stride = 0, cj_spin_stride = 0, planes_spin_stride = 0;   // elements between the spin channels
+    int kdim = 0; bool re_only = false;  // K loop bound (see above); only the Re planes (a kL that is its own time-reversal partner)
+    // nemb = 256 kernel only: the invariant region of the planes is already in place, two workgroup types of four run
+    bool skip_invariant = false;
+    // table kernel only: the launch leaves out the block rows below first_row_block (1 without a launch when none is left);
+    // nsub > 1: the queue is cut into nsub runs with one workgroup per (L, item, run); run p >= 1 accumulates into
+    // planes_sub + (p - 1) * sub_stride ([spin][2 plane_rows][row_len] each), which the caller adds to `planes` afterwards
+    int first_row_block = 0, nsub = 1;
+    double *planes_sub = nullptr; long long sub_stride = 0;
+};
+int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q);
+int launch_half2_tab(dmk_ctx *ctx, const Half2Launch &q);
 int half2_hot_usable(int nao, int nemb);
 int half2_hot_maxslot();
 int half1_hot_usable(int nL, int nao, int nemb);
-// step 2 for a general embedding dimension (zhot_tab.hip); same arguments and return convention as launch_half2_hot
-// nsub > 1: the queue is cut into nsub runs with one workgroup per (L, item, run); run p >= 1 accumulates into
-// planes_sub + (p - 1) * sub_stride ([spin][2 naux][npair] each), which the caller adds to `planes` afterwards
-int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj,
-                     const int *sym, double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
-                     long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int nsub = 1,
-                     double *planes_sub = nullptr, long long sub_stride = 0, int kdim = 0, int re_only = 0,
-                     int first_row_block = 0);
 int half2_tab_subgroups(dmk_ctx *ctx, int nL, int nao, int nemb, int nspin, int nslot, int max_sub);
 int half2_tab_usable(int nao, int nemb);
 int half2_tab_maxslot();

@@ -377,56 +377,51 @@ extern "C" int dmk_dgemm_tile_table(int tiles_m, int tiles_n, int symm, int lo, 
     return DMK_OK;
 }
 
-// Would a launch with these arguments run on the LDS-DMA kernel (the only one that walks a tile table)?
-static bool dgemm_dma_path(int M, int N, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, int seg_rows,
-                           int64_t seg_stride_x, int64_t seg_stride_y, int Mp, int Np) {
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    const bool vec2 = ((ldx & 1) == 0) && ((ldy & 1) == 0) &&
-                      ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
-                      ((reinterpret_cast<uintptr_t>(Y) & 15) == 0) && ((seg_stride_x & 1) == 0) && ((seg_stride_y & 1) == 0);
+// What the predicate and the launch both make of a descriptor with M, N, K > 0: the loadable columns and the segment length in
+// their normal form, and the kernel the launch runs on.  False: K is not a whole number of segments.
+struct DgemmPath { int tiles_m, tiles_n; bool vec2, dma; };   // vec2: 16-byte operand loads; dma: the LDS-DMA kernel (it alone walks a tile table)
+static bool dgemm_tn_normalise(DgemmTn &g, DgemmPath &p) {
+    if (g.Mp < g.M) g.Mp = g.M;                 // loadable columns of X / Y (>= M / N, zero beyond): see the LDS-DMA kernel
+    if (g.Np < g.N) g.Np = g.N;
+    if (g.seg_rows <= 0 || g.seg_rows >= g.K) { g.seg_rows = g.K; g.seg_stride_x = g.seg_stride_y = 0; }
+    if (g.K % g.seg_rows) return false;
+    p.tiles_m = (g.M + BM - 1) / BM;
+    p.tiles_n = (g.N + BN - 1) / BN;
+    p.vec2 = ((g.ldx & 1) == 0) && ((g.ldy & 1) == 0) &&
+             ((reinterpret_cast<uintptr_t>(g.X) & 15) == 0) &&
+             ((reinterpret_cast<uintptr_t>(g.Y) & 15) == 0) && ((g.seg_stride_x & 1) == 0) && ((g.seg_stride_y & 1) == 0);
     static const bool dma_enabled = [] { const char *e = getenv("DMK_DGEMM_DMA"); return !(e && atoi(e) == 0); }();
-    return dma_enabled && vec2 && (seg_rows % GBK) == 0 && K >= GBK && (Mp % 2) == 0 && (Np % 2) == 0 && Mp <= ldx && Np <= ldy &&
-           M >= 2 && N >= 2 && tiles_m < 65536 && tiles_n < 65536;
+    p.dma = dma_enabled && p.vec2 && (g.seg_rows % GBK) == 0 && g.K >= GBK && (g.Mp % 2) == 0 && (g.Np % 2) == 0 && g.Mp <= g.ldx &&
+            g.Np <= g.ldy && g.M >= 2 && g.N >= 2 && p.tiles_m < 65536 && p.tiles_n < 65536;
+    return true;
 }
 
-// Same arguments as launch_dgemm_tn_acc_seg: true when that launch could leave a corner of tiles out (skip_tiles > 0).
-bool dgemm_tn_can_skip(int M, int N, int K, const double *X, int64_t ldx, const double *Y, int64_t ldy, int seg_rows,
-                       int64_t seg_stride_x, int64_t seg_stride_y, int Mp, int Np) {
-    if (M <= 0 || N <= 0 || K <= 0) return false;
-    if (Mp < M) Mp = M;
-    if (Np < N) Np = N;
-    if (seg_rows <= 0 || seg_rows >= K) { seg_rows = K; seg_stride_x = seg_stride_y = 0; }
-    if (K % seg_rows) return false;
-    return dgemm_dma_path(M, N, K, X, ldx, Y, ldy, seg_rows, seg_stride_x, seg_stride_y, Mp, Np);
+// True when the launch of `g` could leave a corner of tiles out (skip_tiles > 0).
+bool dgemm_tn_can_skip(const DgemmTn &desc) {
+    DgemmTn g = desc; DgemmPath p;
+    return g.M > 0 && g.N > 0 && g.K > 0 && dgemm_tn_normalise(g, p) && p.dma;
 }
 
-int launch_dgemm_tn_acc(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X,
-                        int64_t ldx, const double *Y, int64_t ldy, double *C, int64_t ldc) {
-    return launch_dgemm_tn_acc_seg(ctx, M, N, K, alpha, X, ldx, Y, ldy, C, ldc, 0, 0, 0, -1, -1, 0, 0, 0);
-}
-
-// The same product with (i) K given as K / seg_rows row segments that start seg_stride_x / seg_stride_y ELEMENTS apart
-// (seg_rows = 0: one contiguous segment) and (ii) the output restricted to the tile band [band_lo, band_hi) (128-row /
+// C (M x N, ldc) += alpha X^T Y with (i) K given as K / seg_rows row segments that start seg_stride_x / seg_stride_y ELEMENTS
+// apart (seg_rows = 0: one contiguous segment) and (ii) the output restricted to the tile band [band_lo, band_hi) (128-row /
 // 128-column tiles; -1: everything) -- see dgemm_tile_table.  The ERI pipeline stacks the planes of many kL along K and
 // finishes the contraction band by band so that finished rows can be reduced over ranks while later bands are computed.
 // skip_tiles > 0: the tiles tm < skip_tiles && tn < skip_tiles are not computed and that corner of C is not touched (LDS-DMA
 // kernel only; a launch that would fall to the register-staged kernel is refused -- ask dgemm_tn_can_skip first).
-int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, const double *X, int64_t ldx, const double *Y,
-                            int64_t ldy, double *C, int64_t ldc, int seg_rows, int64_t seg_stride_x, int64_t seg_stride_y,
-                            int band_lo, int band_hi, int Mp, int Np, int skip_tiles) {
-    if (skip_tiles < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn: negative skip_tiles");
-    if (M <= 0 || N <= 0 || K <= 0) return DMK_OK;
-    if (Mp < M) Mp = M;                 // loadable columns of X / Y (>= M / N, zero beyond): see the LDS-DMA kernel
-    if (Np < N) Np = N;
-    if (seg_rows <= 0 || seg_rows >= K) { seg_rows = K; seg_stride_x = seg_stride_y = 0; }
-    if (K % seg_rows) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn: K = %d is not a multiple of the segment length %d", K, seg_rows);
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+int launch_dgemm_tn_acc(dmk_ctx *ctx, const DgemmTn &desc) {
+    if (desc.skip_tiles < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn: negative skip_tiles");
+    if (desc.M <= 0 || desc.N <= 0 || desc.K <= 0) return DMK_OK;
+    DgemmTn g = desc; DgemmPath path;
+    if (!dgemm_tn_normalise(g, path))
+        return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn: K = %d is not a multiple of the segment length %d", g.K, g.seg_rows);
+    const int M = g.M, N = g.N, K = g.K, seg_rows = g.seg_rows, Mp = g.Mp, Np = g.Np, band_lo = g.band_lo, band_hi = g.band_hi;
+    const int tiles_m = path.tiles_m, tiles_n = path.tiles_n, skip_tiles = g.skip_tiles;
+    const double alpha = g.alpha, *X = g.X, *Y = g.Y;
+    double *C = g.C;
+    const int64_t ldx = g.ldx, ldy = g.ldy, ldc = g.ldc, seg_stride_x = g.seg_stride_x, seg_stride_y = g.seg_stride_y;
     const int64_t nblocks = (int64_t)tiles_m * tiles_n;
     if (nblocks > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "dgemm_tn: grid too large");
-    const bool vec2 = ((ldx & 1) == 0) && ((ldy & 1) == 0) &&
-                      ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
-                      ((reinterpret_cast<uintptr_t>(Y) & 15) == 0) && ((seg_stride_x & 1) == 0) && ((seg_stride_y & 1) == 0);
-    if (dgemm_dma_path(M, N, K, X, ldx, Y, ldy, seg_rows, seg_stride_x, seg_stride_y, Mp, Np)) {
+    if (path.dma) {
         static const bool symm_enabled = [] { const char *e = getenv("DMK_DGEMM_SYMM"); return !(e && atoi(e) == 0); }();
         const bool symm = symm_enabled && X == Y && ldx == ldy && seg_stride_x == seg_stride_y && M == N && tiles_m >= 2;
         unsigned count = 0;
@@ -468,7 +463,7 @@ int launch_dgemm_tn_acc_seg(dmk_ctx *ctx, int M, int N, int K, double alpha, con
     const int Mb = m_hi - m_lo;
     const int tiles_mb = (Mb + BM - 1) / BM;
     const int64_t nb2 = (int64_t)tiles_mb * tiles_n;
-    const bool vec2b = vec2 && (m_lo % 2) == 0;
+    const bool vec2b = path.vec2 && (m_lo % 2) == 0;
     for (int k0 = 0, sidx = 0; k0 < K; k0 += seg_rows, ++sidx) {
         const double *Xs = X + (seg_rows == K ? 0 : (int64_t)sidx * seg_stride_x) + m_lo;
         const double *Ys = Y + (seg_rows == K ? 0 : (int64_t)sidx * seg_stride_y);

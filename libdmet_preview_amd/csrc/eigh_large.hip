@@ -739,12 +739,17 @@ int vectors(dmk_eighl *h, int m, const int32_t *idx, double *Vt) {
         DMK_HIP(ctx, hipMemsetAsync(S, 0, (size_t)NB * m * 8, st));
         int rc;
         // G = V V^T and S = V Y over the rows below the panel's first diagonal (the reflectors vanish above)
-        if ((rc = launch_dgemm_tn_acc(ctx, nbp, nbp, K, 1.0, VT + (size_t)lo * NB, NB, VT + (size_t)lo * NB, NB, G, NB))) return rc;
-        if ((rc = launch_dgemm_tn_acc(ctx, nbp, m, K, 1.0, VT + (size_t)lo * NB, NB, Y + (size_t)lo * m, m, S, m))) return rc;
+        DgemmTn vv, vy;
+        vv.M = vv.N = nbp; vv.K = K; vv.X = vv.Y = VT + (size_t)lo * NB; vv.ldx = vv.ldy = NB; vv.C = G; vv.ldc = NB;
+        vy.M = nbp; vy.N = m; vy.K = K; vy.X = vv.X; vy.ldx = NB; vy.Y = Y + (size_t)lo * m; vy.ldy = m; vy.C = S; vy.ldc = m;
+        if ((rc = launch_dgemm_tn_acc(ctx, vv))) return rc;
+        if ((rc = launch_dgemm_tn_acc(ctx, vy))) return rc;
         hipLaunchKernelGGL(wy_apply_t_kernel, dim3(std::min(256, (m + 255) / 256)), dim3(256), 0, st, nbp, m, tau + k0, G, S, U);
         DMK_CHECK_LAUNCH(ctx);
         // Y[lo:, :] -= V[:, lo:]^T U
-        if ((rc = launch_dgemm_tn_acc(ctx, K, m, nbp, -1.0, V + lo, n, U, m, Y + (size_t)lo * m, m))) return rc;
+        DgemmTn vu;
+        vu.M = K; vu.N = m; vu.K = nbp; vu.alpha = -1.0; vu.X = V + lo; vu.ldx = n; vu.Y = U; vu.ldy = m; vu.C = Y + (size_t)lo * m; vu.ldc = m;
+        if ((rc = launch_dgemm_tn_acc(ctx, vu))) return rc;
     }
     {
         const dim3 tg((m + 31) / 32, (n + 31) / 32), tb(32, 8);

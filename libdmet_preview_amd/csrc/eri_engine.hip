@@ -92,7 +92,6 @@ struct dmk_eri {
     dmk_eri_cache *cache = nullptr;
     bool inv_warm = false, inv_save = false;
     int inv_A = 0;
-    uint64_t inv_key = 0;
     // invariant block of the result (dmk_eri_attach_cache_block): blk_S > 0 -- armed, the corner of blk_S x blk_S tiles of every spin
     // block is a function of columns [0, blk_ne) of C alone.  slot_keys: what the planes resident in each stack slot were begun
     // with (keyed: by dmk_eri_begin_kL_cached with the cache attached) -- the block's key is made of them.
@@ -426,18 +425,30 @@ static ZGemm half2_desc(const dmk_eri *h, const double2 *ut, int nl, const doubl
     return g2;
 }
 
+// hot step 1 of `nl` auxiliary rows from row l0 of one AO block (or of a queue of them: the caller sets the slot fields) into queue
+// slot `slot`, both spin channels in one launch
+static Half1Launch half1_hot_desc(const dmk_eri *h, const double2 *L, int l0, int nl, int slot) {
+    Half1Launch q;
+    q.Lpq = L + (size_t)l0 * h->nao * h->nao; q.C = h->Ch;
+    q.Ut = h->Ut + (size_t)slot * h->slot_elems() + (size_t)l0 * h->nao * h->nemb;
+    q.nL = nl; q.nao = h->nao; q.nemb = h->nemb; q.nspin = h->spin; q.kdim = h->kdim;
+    q.ci_spin_stride = h->c_spin_stride(); q.ut_spin_stride = (long long)h->group * (long long)h->slot_elems();
+    return q;
+}
+
 static int eri_ring_step1(dmk_eri *h) {
     dmk_ctx *ctx = h->ctx;
     if (h->ring_pending == 0) return DMK_OK;
-    const int nao = h->nao, naux = h->naux, nemb = h->nemb;
+    const int nao = h->nao, naux = h->naux;
     const bool resident = h->resident_src != nullptr;
     const double2 *src = resident ? h->resident_src : h->ring + (size_t)h->fill_half * h->group * naux * nao * nao;
     if (!resident && h->gen_pending) DMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, h->ev_gen[h->fill_half], 0));      // the producers of this group
     for (int l0 = 0; l0 < naux; l0 += h->hot_rows) {         // (one launch unless an AO block reaches 4 GiB)
         const int nl = std::min(h->hot_rows, naux - l0);
-        int rc = launch_half1_hot_multi(ctx, src + (size_t)l0 * nao * nao, (long long)naux * nao * nao, h->ring_pending, h->pend_ki, h->Ch,
-                                        h->Ut + (size_t)l0 * nao * nemb, (long long)h->slot_elems(), nl, nao, nemb, h->spin,
-                                        h->c_spin_stride(), (long long)h->group * (long long)h->slot_elems(), h->kdim);
+        Half1Launch q = half1_hot_desc(h, src, l0, nl, 0);
+        q.nslot = h->ring_pending; q.ki = h->pend_ki;
+        q.a_slot_stride = (long long)naux * nao * nao; q.ut_slot_stride = (long long)h->slot_elems();
+        int rc = launch_half1_hot(ctx, q);
         if (rc < 0) return rc;
         if (rc == 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri ring: hot step-1 kernel unavailable for the queued blocks");
     }
@@ -457,27 +468,32 @@ static int eri_flush(dmk_eri *h) {
         if (rc1) return rc1;
     }
     const int nao = h->nao, naux = h->naux, nemb = h->nemb;
-    const long long slot_elems = (long long)h->slot_elems(), ut_spin_stride = (long long)h->group * slot_elems;
     // one launch for both spin channels: C, Ut and the planes of spin 1 sit at constant offsets from those of spin 0
     const void *cj[16];
     for (int i = 0; i < h->pending; ++i)
         cj[i] = h->Ch + (size_t)h->pend_kj[i] * h->kdim * nemb;
+    Half2Launch q;
+    q.Ut = h->Ut; q.slot_stride = (long long)h->slot_elems(); q.nslot = h->pending; q.Cj = cj; q.sym = h->pend_sym;
+    q.planes = h->slot_planes(h->cur_slot, 0); q.plane_rows = h->pr; q.row_len = h->pl;
+    q.nL = naux; q.nao = nao; q.nemb = nemb; q.nspin = h->spin; q.kdim = h->kdim;
+    q.ut_spin_stride = (long long)h->group * q.slot_stride; q.cj_spin_stride = h->c_spin_stride();
+    q.planes_spin_stride = h->planes_spin_stride(); q.re_only = h->re_only;
     int rc;
     if (h->hot256) {
-        rc = launch_half2_hot(ctx, h->Ut, slot_elems, h->pending, cj, h->pend_sym, h->slot_planes(h->cur_slot, 0), h->pr, h->pl,
-                              naux, nao, nemb, h->spin, ut_spin_stride, h->c_spin_stride(), h->planes_spin_stride(), h->kdim,
-                              h->re_only ? 1 : 0, h->inv_warm ? 1 : 0);
+        q.skip_invariant = h->inv_warm;
+        rc = launch_half2_hot(ctx, q);
         if (rc == 0 && h->inv_warm)
             return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the nemb = 256 step-2 kernel declined a kL whose invariant planes came from the cache");
     } else {
-        const int nsub = h->sub_planes ? half2_tab_subgroups(ctx, naux, nao, nemb, h->spin, h->pending, h->nsub_max) : 1;
-        rc = launch_half2_tab(ctx, h->Ut, slot_elems, h->pending, cj, h->pend_sym, h->slot_planes(h->cur_slot, 0), h->pr, h->pl,
-                              naux, nao, nemb, h->spin, ut_spin_stride, h->c_spin_stride(), h->planes_spin_stride(), nsub,
-                              h->sub_planes, (long long)h->spin * 2LL * h->pr * h->pl, h->kdim, h->re_only ? 1 : 0,
-                              h->inv_warm ? h->inv_A / 16 : 0);
+        q.first_row_block = h->inv_warm ? h->inv_A / 16 : 0;
+        if (h->sub_planes) {
+            q.nsub = half2_tab_subgroups(ctx, naux, nao, nemb, h->spin, h->pending, h->nsub_max);
+            q.planes_sub = h->sub_planes; q.sub_stride = (long long)h->spin * 2LL * h->pr * h->pl;
+        }
+        rc = launch_half2_tab(ctx, q);
         if (rc == 0 && h->inv_warm)      // (the generic fallback below would add the cached region a second time)
             return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the table-driven step-2 kernel declined a kL whose invariant planes came from the cache");
-        if (rc == 1) h->sub_used = std::max(h->sub_used, nsub);
+        if (rc == 1) h->sub_used = std::max(h->sub_used, q.nsub);
     }
     if (rc < 0) return rc;
     if (rc == 0) {
@@ -533,9 +549,9 @@ int dmk_eri_push_block(dmk_eri *h, int ki, int kj, int symmetrise, const void *L
         int rc_hot = 1;
         for (int l0 = 0; l0 < naux && rc_hot == 1; l0 += h->hot_rows) {
             const int nl = std::min(h->hot_rows, naux - l0);
-            rc_hot = launch_half1_hot(ctx, L + (size_t)l0 * nao * nao, h->Ch + (size_t)ki * h->kdim * nemb,
-                                      h->Ut + (size_t)slot * h->slot_elems() + (size_t)l0 * nao * nemb, nl, nao, nemb, h->spin,
-                                      h->c_spin_stride(), (long long)h->group * (long long)h->slot_elems(), h->kdim);
+            Half1Launch q = half1_hot_desc(h, L, l0, nl, slot);
+            q.C = h->Ch + (size_t)ki * h->kdim * nemb;
+            rc_hot = launch_half1_hot(ctx, q);
             if (rc_hot == 0 && l0 > 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_push_block: hot step-1 kernel declined a later range of L");
         }
         if (rc_hot < 0) return rc_hot;
@@ -562,7 +578,10 @@ int dmk_eri_push_block(dmk_eri *h, int ki, int kj, int symmetrise, const void *L
         for (int l0 = 0; l0 < naux; l0 += h->lchunk) {
             const int nl = std::min(h->lchunk, naux - l0);
             const double2 *Ll = L + (size_t)l0 * nao * nao;
-            int rc = launch_half1_hot(ctx, Ll, h->Ch + ((size_t)s * h->mesh.nk + ki) * h->kdim * nemb, h->Ut, nl, nao, nemb, 1, 0, 0, h->kdim);
+            Half1Launch q;                          // one spin channel and one range of L at a time
+            q.Lpq = Ll; q.C = h->Ch + ((size_t)s * h->mesh.nk + ki) * h->kdim * nemb; q.Ut = h->Ut;
+            q.nL = nl; q.nao = nao; q.nemb = nemb; q.kdim = h->kdim;
+            int rc = launch_half1_hot(ctx, q);
             if (rc < 0) return rc;
             if (rc == 0) {
                 rc = launch_zgemm(ctx, half1_desc(h, Ll, nl, Ci, h->Ut), DMK_FAM_ZGEMM_HALF1);
@@ -791,24 +810,33 @@ static int eri_probe_slot(dmk_eri *h, int slot, int nrows, double w) {
                                  w, h->probe_x, h->probe_y, reinterpret_cast<double *>(tw));
 }
 
-// The spin blocks aa (, ab, bb) of alpha X^T X over K plane rows starting at `slot`: C[b] += alpha X_a[:, row0 : row0 + M]^T X_b,
-// blocks `blk` doubles apart.  Mp: columns of X_a that may be loaded (M, or up to the padding column); seg_rows / seg_stride: K in
-// segments of seg_rows rows, seg_stride doubles apart (0: one contiguous range); [band_lo, band_hi): tile band of the pair index.
-// skip: the corner of skip x skip tiles of every block is left out (the invariant block of the result; full products only).
-static int eri_spin_products(dmk_eri *h, int slot, int64_t row0, int M, int Mp, int K, double alpha, double *C, size_t blk, int seg_rows,
-                             int64_t seg_stride, int band_lo, int band_hi, int skip = 0) {
-    const int64_t np = h->npair, pl = h->pl;
-    auto gemm = [&](const double *A, const double *B, double *Cb) {
-        return launch_dgemm_tn_acc_seg(h->ctx, M, (int)np, K, alpha, A + row0, pl, B, pl, Cb, np, seg_rows, seg_stride, seg_stride, band_lo,
-                                       band_hi, Mp, (int)pl, skip);
-    };
-    const double *X0 = h->slot_planes(slot, 0);
-    int rc = gemm(X0, X0, C);
-    if (rc || h->spin != 2) return rc;
-    const double *X1 = h->slot_planes(slot, 1);
-    rc = gemm(X0, X1, C + blk);
-    if (rc) return rc;
-    return gemm(X1, X1, C + 2 * blk);
+// A contraction of plane slots: C (npair x npair) += alpha X_a^T X_b over K plane rows from the first row of `slot`, X_a / X_b the
+// planes of spin channel spin_a / spin_b.  Both operands may be loaded up to the padding column.  stacked_rows > 0: K runs over
+// several slots, stacked_rows rows from the start of each.  Callers narrow it by name: rows of C (X, M, Mp), a tile band, a corner.
+static DgemmTn planes_gemm(const dmk_eri *h, int slot, int spin_a, int spin_b, int K, double alpha, double *C, int stacked_rows = 0) {
+    DgemmTn g;
+    g.M = g.N = (int)h->npair; g.K = K; g.alpha = alpha;
+    g.X = h->slot_planes(slot, spin_a); g.Y = h->slot_planes(slot, spin_b); g.ldx = g.ldy = h->pl;
+    g.C = C; g.ldc = h->npair;
+    g.Mp = g.Np = (int)h->pl;
+    g.seg_rows = stacked_rows;
+    g.seg_stride_x = g.seg_stride_y = stacked_rows > 0 ? 2LL * h->pr * h->pl : 0;
+    return g;
+}
+
+// The spin blocks aa (, ab, bb) of one contraction: `aa` is planes_gemm of spin channels (0, 0) as the caller narrowed it; ab and
+// bb read spin channel 1 of the same slot in its place and write `blk` doubles further on each.
+static int eri_spin_products(dmk_eri *h, const DgemmTn &aa, size_t blk) {
+    const long long spin1 = h->planes_spin_stride();
+    for (int b = 0; b < h->spin_blocks(); ++b) {
+        DgemmTn g = aa;
+        if (b == 2) g.X += spin1;
+        if (b >= 1) g.Y += spin1;
+        g.C += b * blk;
+        int rc = launch_dgemm_tn_acc(h->ctx, g);
+        if (rc) return rc;
+    }
+    return DMK_OK;
 }
 
 // What dmk_eri_end_kL and dmk_eri_end_kL_gso (`gso`) share: the queue is flushed, the sub-group copies are folded in (and the
@@ -849,7 +877,7 @@ int dmk_eri_end_kL(dmk_eri *h, int weight) {
     double alpha;
     int rc = eri_kl_close(h, weight, false, &K, &Kalg, &alpha);
     if (rc) return rc;
-    const int64_t np = h->npair, pl = h->pl;
+    const int64_t np = h->npair;
     if (h->nslots > 1) {
         // deferred: the planes stay in their slot until the stack is contracted
         if (!h->tr) return dmk_fail(ctx, DMK_ERR_STATE, "eri_end_kL: the plane stack needs time-reversal symmetry");
@@ -866,18 +894,17 @@ int dmk_eri_end_kL(dmk_eri *h, int weight) {
             rc = eri_probe_slot(h, 0, K, alpha);
             if (rc) return rc;
         }
-        rc = eri_spin_products(h, 0, 0, (int)np, (int)pl, K, alpha, h->eri, (size_t)np * np, 0, 0, -1, -1);
+        rc = eri_spin_products(h, planes_gemm(h, 0, 0, 0, K, alpha, h->eri), (size_t)np * np);
         if (rc) return rc;
         // Im (L_a^H L_b) = Re_a^T Im_b - Im_a^T Re_b  (the part eri.real drops, eri_transform.py:385-394)
-        const double *X0 = h->slot_planes(0, 0), *X1 = h->slot_planes(0, h->spin - 1);
         const int nimag = h->imag ? h->spin_blocks() : 0;
+        const size_t im = (size_t)h->pr * h->pl;         // Re plane -> Im plane
         for (int b = 0; b < nimag; ++b) {
-            const double *A = (b == 2) ? X1 : X0, *B = (b == 0) ? X0 : X1;
-            const double *Are = A, *Aim = A + (size_t)h->pr * pl, *Bre = B, *Bim = B + (size_t)h->pr * pl;
-            double *Cb = h->imag + (size_t)b * np * np;
-            rc = launch_dgemm_tn_acc_seg(ctx, (int)np, (int)np, (int)h->pr, 1.0, Are, pl, Bim, pl, Cb, np, 0, 0, 0, -1, -1, (int)pl, (int)pl);
+            DgemmTn re_im = planes_gemm(h, 0, b == 2, b >= 1, (int)h->pr, 1.0, h->imag + (size_t)b * np * np), im_re = re_im;
+            re_im.Y += im; im_re.X += im; im_re.alpha = -1.0;
+            rc = launch_dgemm_tn_acc(ctx, re_im);
             if (rc) return rc;
-            rc = launch_dgemm_tn_acc_seg(ctx, (int)np, (int)np, (int)h->pr, -1.0, Aim, pl, Bre, pl, Cb, np, 0, 0, 0, -1, -1, (int)pl, (int)pl);
+            rc = launch_dgemm_tn_acc(ctx, im_re);
             if (rc) return rc;
         }
     }
@@ -891,8 +918,7 @@ int dmk_eri_end_kL(dmk_eri *h, int weight) {
 static int eri_contract_stack(dmk_eri *h, int band_lo, int band_hi) {
     dmk_ctx *ctx = h->ctx;
     if (!h->eri) return dmk_fail(ctx, DMK_ERR_STATE, "eri contraction: this pipeline was opened without an ERI of its own (flags bit 2)");
-    const int64_t np = h->npair, pl = h->pl;
-    const int64_t slot_stride = 2LL * h->pr * pl;
+    const int64_t np = h->npair;
     // slots per launch.  Measured at C5 (13 weight-2 kL resident): 1, 2, 4 or all 13 kL per launch run at the same 69.3-69.6 TF on
     // the matrix pipe -- there the contraction is not sensitive to K -- but the HBM traffic is not the same: with K = 1600 the
     // operand panels of the eight XCDs' super-blocks (8 x 16 panels x K x 128 x 8 B = 210 MB) still fit the 256 MB Infinity Cache
@@ -932,8 +958,9 @@ static int eri_contract_stack(dmk_eri *h, int band_lo, int band_hi) {
         const int kchunk = kchunk_for(wc.seg_rows);
         for (int s0 = 0; s0 < wc.n; s0 += kchunk) {
             const int K = std::min(kchunk, wc.n - s0) * wc.seg_rows;
-            int rc = eri_spin_products(h, wc.first + s0, 0, (int)np, (int)pl, K, wc.weight, h->eri, (size_t)np * np, wc.seg_rows, slot_stride,
-                                       band_lo, band_hi, skip);
+            DgemmTn g = planes_gemm(h, wc.first + s0, 0, 0, K, wc.weight, h->eri, wc.seg_rows);
+            g.band_lo = band_lo; g.band_hi = band_hi; g.skip_tiles = skip;
+            int rc = eri_spin_products(h, g, (size_t)np * np);
             if (rc) return rc;
         }
     }
@@ -1007,8 +1034,9 @@ int dmk_eri_contract_rows(dmk_eri *h, int64_t row_lo, int64_t row_hi, double *ou
     for (int w = 2; w >= 1; --w) {
         const dmk_eri::WeightClass wc = h->weight_class(w);
         if (wc.n == 0) continue;
-        int rc = eri_spin_products(h, wc.first, row_lo, rows, rows_p, wc.n * wc.seg_rows, wc.weight, out, (size_t)rows * np, wc.seg_rows,
-                                   2LL * h->pr * pl, -1, -1);
+        DgemmTn g = planes_gemm(h, wc.first, 0, 0, wc.n * wc.seg_rows, wc.weight, out, wc.seg_rows);
+        g.X += row_lo; g.M = rows; g.Mp = rows_p;
+        int rc = eri_spin_products(h, g, (size_t)rows * np);
         if (rc) return rc;
     }
     return DMK_OK;
@@ -1087,7 +1115,7 @@ int dmk_eri_end_kL_gso(dmk_eri *h, int weight) {
         hipLaunchKernelGGL(planes_acc_kernel<-1>, dim3(8192), dim3(256), 0, ctx->stream, nel, X0, X1);
         DMK_CHECK_LAUNCH(ctx);
     }
-    rc = launch_dgemm_tn_acc_seg(ctx, (int)np, (int)np, K, alpha, X0, pl, X0, pl, h->eri, np, 0, 0, 0, -1, -1, (int)pl, (int)pl);
+    rc = launch_dgemm_tn_acc(ctx, planes_gemm(h, 0, 0, 0, K, alpha, h->eri));
     if (rc) return rc;
     h->flops_contract += 2.0 * (double)Kalg * (double)np * (double)np;
     h->cur_kL = -1;
@@ -1197,6 +1225,35 @@ __global__ void blk_corner_kernel(double *__restrict__ eri, double *__restrict__
 
 // doubles per auxiliary row and plane of a cache entry of this pipeline's region
 int inv_row_len(const dmk_eri *h) { return h->inv_A ? h->inv_A * (h->inv_A + 1) / 2 : INV_ROW; }
+
+// One verdict of a device-side check: the cache's flag is zeroed, `launch` enqueues a kernel that sets it, and the flag is read
+// back (the one synchronisation of the check).
+template <class Launch> int device_flag(dmk_ctx *ctx, dmk_eri_cache *c, int *flag, Launch &&launch) {
+    DMK_HIP(ctx, hipMemsetAsync(c->flag, 0, sizeof(int), ctx->stream));
+    {
+        FamScope fs(ctx, DMK_FAM_MISC);
+        launch();
+        DMK_CHECK_LAUNCH(ctx);
+    }
+    *flag = 1;
+    DMK_HIP(ctx, hipMemcpyAsync(flag, c->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DMK_OK;
+}
+
+// Are columns [col0, col0 + ncols) of the pipeline's C_ao_emb `stored` ([rows of the cache][ncols]) bit for bit?  The bit patterns
+// of every (spin, k, AO row) are reduced to one flag on the device and read back once.
+int cols_same(dmk_eri *h, dmk_eri_cache *c, const double2 *stored, int col0, int ncols, bool *same) {
+    const long long n = (long long)c->cols_rows * ncols;
+    int diff = 1;
+    int rc = device_flag(h->ctx, c, &diff, [&] {
+        const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, h->ctx->stream, n, h->nemb, ncols, col0,
+                           reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(stored), c->flag);
+    });
+    *same = diff == 0;
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -1228,7 +1285,7 @@ static int inv_save_entry(dmk_eri *h) {
     }
     int rc = inv_region_copy(h, buf, false);
     if (rc) { (void)hipFree(buf); return rc; }
-    c->entries.push_back({h->cur_kL, h->inv_key, h->re_only ? 1 : 0, buf, bytes});
+    c->entries.push_back({h->cur_kL, h->cur_key, h->re_only ? 1 : 0, buf, bytes});
     c->held += bytes;
     return DMK_OK;
 }
@@ -1307,20 +1364,7 @@ static int inv_attach(dmk_eri *h, dmk_eri_cache *cache, int tab_A, int ncols, in
     bool same = cache->have_cols && cache->cols_rows == rows && cache->tab_A == tab_A && cache->ncols == ncols;
     for (int i = 0; i < 7 && same; ++i) same = cache->shape[i] == shape[i];
     if (same) {
-        // bit patterns of columns [0, ncols) of every (spin, k, AO row), reduced to one flag on the device and read back once
-        const long long n = (long long)rows * ncols;
-        DMK_HIP(ctx, hipMemsetAsync(cache->flag, 0, sizeof(int), ctx->stream));
-        {
-            FamScope fs(ctx, DMK_FAM_MISC);
-            const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, n, h->nemb, ncols, 0,
-                               reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(cache->cols), cache->flag);
-            DMK_CHECK_LAUNCH(ctx);
-        }
-        int diff = 1;
-        DMK_HIP(ctx, hipMemcpyAsync(&diff, cache->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        same = diff == 0;
+        if (int rc = cols_same(h, cache, cache->cols, 0, ncols, &same)) return rc;
     }
     if (!same) {
         inv_cache_clear(cache, true);
@@ -1393,14 +1437,10 @@ int dmk_eri_cache_block_stats(const dmk_eri_cache *cache, int64_t stats[4]) {
 // Would every launch of the stacked contraction run on the kernel that can leave tiles out?  Both weight classes (a class differs
 // in its segment length) and both spin operands (a launch of a later K chunk starts whole slots further on: the same alignment).
 static bool blk_can_skip(const dmk_eri *h) {
-    const int np = (int)h->npair, pl = (int)h->pl;
-    const int64_t slot_stride = 2LL * h->pr * h->pl;
     for (int w = 2; w >= 1; --w) {
         const dmk_eri::WeightClass wc = h->weight_class(w);
-        for (int s = 0; s < h->spin; ++s) {
-            const double *X = h->slot_planes(0, s);
-            if (!dgemm_tn_can_skip(np, np, wc.seg_rows, X, pl, X, pl, wc.seg_rows, slot_stride, slot_stride, pl, pl)) return false;
-        }
+        for (int s = 0; s < h->spin; ++s)
+            if (!dgemm_tn_can_skip(planes_gemm(h, 0, s, s, wc.seg_rows, wc.weight, h->eri, wc.seg_rows))) return false;
     }
     return true;
 }
@@ -1432,19 +1472,7 @@ int dmk_eri_attach_cache_block(dmk_eri *h, dmk_eri_cache *cache, int ninv, int *
     const size_t rows = cache->cols_rows;
     bool same = cache->blk_ne == n_e && cache->blk_lo == lo && (extra == 0 || cache->blk_cols);
     if (same && extra > 0) {
-        const long long cnt = (long long)rows * extra;
-        DMK_HIP(ctx, hipMemsetAsync(cache->flag, 0, sizeof(int), ctx->stream));
-        {
-            FamScope fs(ctx, DMK_FAM_MISC);
-            const unsigned grid = (unsigned)std::min<long long>((cnt + 255) / 256, 4096);
-            hipLaunchKernelGGL(inv_cols_compare_kernel, dim3(grid), dim3(256), 0, ctx->stream, cnt, h->nemb, extra, lo,
-                               reinterpret_cast<const ulonglong2 *>(h->C), reinterpret_cast<const ulonglong2 *>(cache->blk_cols), cache->flag);
-            DMK_CHECK_LAUNCH(ctx);
-        }
-        int diff = 1;
-        DMK_HIP(ctx, hipMemcpyAsync(&diff, cache->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        same = diff == 0;
+        if (int rc = cols_same(h, cache, cache->blk_cols, lo, extra, &same)) return rc;
     }
     if (!same) {
         blk_drop(cache);
@@ -1511,16 +1539,12 @@ static int blk_decide(dmk_eri *h, int kchunk_w2, int kchunk_w1, int *skip, bool 
     }
     int cpr;
     const unsigned grid = blk_grid(h, n, &cpr);
-    DMK_HIP(ctx, hipMemsetAsync(c->flag, 0, sizeof(int), ctx->stream));
-    {
-        FamScope fs(ctx, DMK_FAM_MISC);
+    int nonzero = 1;
+    int rc = device_flag(ctx, c, &nonzero, [&] {
         hipLaunchKernelGGL(blk_corner_kernel<2>, dim3(grid), dim3(256), 0, ctx->stream, h->eri, (double *)nullptr, n, (long long)h->npair,
                            (long long)h->npair * h->npair, cpr, c->flag);
-        DMK_CHECK_LAUNCH(ctx);
-    }
-    int nonzero = 1;
-    DMK_HIP(ctx, hipMemcpyAsync(&nonzero, c->flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    });
+    if (rc) return rc;
     if (nonzero) {
         c->blk_misses += 1;
         return DMK_OK;
@@ -1597,7 +1621,6 @@ int dmk_eri_begin_kL_cached(dmk_eri *h, int kL, int weight, uint64_t key64) {
         }
     c->misses += 1;
     h->inv_save = true;
-    h->inv_key = key64;
     return DMK_OK;
 }
 

@@ -47,9 +47,9 @@ namespace {
 // =============================================================================================
 constexpr int H1_BM = 128, H1_BN = 64, H1_BK = 8, H1_D = 3;
 
-// out[L][m][n] = sum_k A[L][k][m] * op(B[k][n]),  op = conj (step 1: B = C_i) or identity (step 2 of general nemb: B = C_j).
-// A is K-major: element (k, m) of batch L at L * (nao * mrows) + k * mrows + m  (step 1: Lpq, mrows = nao; step 2: Ut,
-// mrows = nemb).  The batch index is folded into M in 16-row blocks.
+// out[L][m][n] = sum_k A[L][k][m] * op(B[k][n]),  op = conj (CONJB; step 1: B = C_i -- the only form the library launches) or
+// identity.  A is K-major: element (k, m) of batch L at L * (nao * mrows) + k * mrows + m  (step 1: Lpq, mrows = nao).
+// The batch index is folded into M in 16-row blocks.
 struct H1Args {
     const double2 *Lpq;    // A
     const double2 *Ci;     // B [nao][nemb]
@@ -248,16 +248,6 @@ struct H2Args {
     // those two workgroups own, eri_engine.hip dmk_eri_cache): only types 1 and 3 run, two workgroups per (L, spin)
     int skip_invariant;
 };
-
-// Kernel-argument arrays must only be indexed with compile-time constants, and the argument struct must
-// never be passed by reference: either makes hipcc copy the whole struct to scratch (private memory), whose
-// loads need s_waitcnt vmcnt(0) -- draining the LDS-DMA ring -- and whose per-dispatch scratch set-up cost
-// ~17 ms per launch when this kernel first did it.
-#define H2_PICK_CJ(G, SLOT)                                                                        \
-    ((SLOT) == 0 ? (G).Cj[0] : (SLOT) == 1 ? (G).Cj[1] : (SLOT) == 2 ? (G).Cj[2] : (SLOT) == 3 ? (G).Cj[3]      \
-     : (SLOT) == 4 ? (G).Cj[4] : (SLOT) == 5 ? (G).Cj[5] : (SLOT) == 6 ? (G).Cj[6] : (SLOT) == 7 ? (G).Cj[7]    \
-     : (SLOT) == 8 ? (G).Cj[8] : (SLOT) == 9 ? (G).Cj[9] : (SLOT) == 10 ? (G).Cj[10] : (SLOT) == 11 ? (G).Cj[11] \
-     : (SLOT) == 12 ? (G).Cj[12] : (SLOT) == 13 ? (G).Cj[13] : (SLOT) == 14 ? (G).Cj[14] : (G).Cj[15])
 
 // LAB: ablation bits of tools/zhot_lab.hip, as in half1_kernel (1: no plane atomics, 2: no LDS-DMA after the prologue, 4: no
 // s_barrier); the product instantiates LAB = 0.
@@ -535,108 +525,61 @@ int half1_hot_max_rows(int nao) {
 int hot_kdim(int nao) { return (nao + H1_BK - 1) / H1_BK * H1_BK; }
 
 // Returns 1 if the hot path handled the launch, 0 if the caller must use the generic kernel, < 0 on error.
-// kdim: K loop bound (0: K itself, which must then be a multiple of the K tile); B holds kdim rows, zero beyond K.
-static int launch_flat_hot(dmk_ctx *ctx, const void *A, const void *B, void *out, int nL, int K, int mrows, int N, bool conjB,
-                           int fam, int nspin = 1, long long b_spin_stride = 0, long long out_spin_stride = 0, int nslot = 1,
-                           long long a_slot_stride = 0, long long out_slot_stride = 0, long long b_k_stride = 0,
-                           const int *bk = nullptr, int kdim = 0) {
-    if (kdim == 0) kdim = K;
-    if (kdim < K || (kdim % H1_BK) != 0) return 0;
-    if (!half1_hot_usable(nL, K, N) || (long long)nL * mrows < 4 * H1_BM) return 0;
-    if ((long long)nL * K * mrows * 16 >= (1LL << 32)) return 0;           // see half1_hot_usable
+int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q) {
+    const int nL = q.nL, nao = q.nao, N = q.nemb, nslot = q.nslot;
+    const int kdim = q.kdim ? q.kdim : nao;             // B holds kdim rows, zero beyond nao
+    if (q.nspin < 1 || q.nspin > 2 || nslot < 1 || nslot > 16 || kdim < nao || (kdim % H1_BK) != 0) return 0;
+    if (!half1_hot_usable(nL, nao, N)) return 0;
     static const int bm = [] { const char *e = getenv("DMK_ERI_H1_BM"); return (e && atoi(e) == 64) ? 64 : 128; }();
-    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(out)) & 15) return 0;
+    if ((reinterpret_cast<uintptr_t>(q.Lpq) | reinterpret_cast<uintptr_t>(q.C) | reinterpret_cast<uintptr_t>(q.Ut)) & 15) return 0;
     H1Args a;
-    a.Lpq = reinterpret_cast<const double2 *>(A);
-    a.Ci = reinterpret_cast<const double2 *>(B);
-    a.Ut = reinterpret_cast<double2 *>(out);
-    a.nL = nL; a.nao = K; a.nemb = N; a.mrows = mrows; a.kdim = kdim;
-    a.nblk = (mrows + 15) / 16;
-    a.tiles_m = (int)(((long long)nL * mrows + bm - 1) / bm);        // flat rows: no padding between the nL batches
+    a.Lpq = reinterpret_cast<const double2 *>(q.Lpq);
+    a.Ci = reinterpret_cast<const double2 *>(q.C);
+    a.Ut = reinterpret_cast<double2 *>(q.Ut);
+    a.nL = nL; a.nao = nao; a.nemb = N; a.mrows = nao; a.kdim = kdim;
+    a.nblk = (nao + 15) / 16;
+    a.tiles_m = (int)(((long long)nL * nao + bm - 1) / bm);          // flat rows: no padding between the nL batches
     // output tile width: 64 columns (2 x 2 waves) or 48 (4 x 1 waves), whichever pads N less; DMK_ERI_H1_BN = 64 | 48 overrides
     int bn = (((N + 47) / 48) * 48 < ((N + 63) / 64) * 64) ? 48 : 64;
     if (const char *e = getenv("DMK_ERI_H1_BN")) { const int v = atoi(e); if (v == 48 || v == 64) bn = v; }
     if (bm != 128) bn = 64;
     a.tiles_n = (N + bn - 1) / bn;
-    a.nspin = nspin; a.b_spin_stride = b_spin_stride; a.out_spin_stride = out_spin_stride;
-    if (nslot < 1 || nslot > 16) return 0;
-    a.nslot = nslot; a.a_slot_stride = a_slot_stride; a.out_slot_stride = out_slot_stride; a.b_k_stride = b_k_stride;
-    for (int i = 0; i < 16; ++i) a.bk[i] = (bk && i < nslot) ? bk[i] : 0;
-    a.per_slot = (unsigned)(a.tiles_m * a.tiles_n * nspin);
+    a.nspin = q.nspin; a.b_spin_stride = q.ci_spin_stride; a.out_spin_stride = q.ut_spin_stride;
+    a.nslot = nslot; a.a_slot_stride = q.a_slot_stride; a.out_slot_stride = q.ut_slot_stride;
+    a.b_k_stride = q.ki ? (long long)kdim * N : 0;
+    for (int i = 0; i < 16; ++i) a.bk[i] = (q.ki && i < nslot) ? q.ki[i] : 0;
+    a.per_slot = (unsigned)(a.tiles_m * a.tiles_n * q.nspin);
     if ((unsigned long long)a.per_slot * (unsigned)nslot > 0x7fffffffull) return 0;
     a.nblocks = a.per_slot * (unsigned)nslot;
-    FamScope fs(ctx, fam);
+    FamScope fs(ctx, DMK_FAM_ZGEMM_HALF1);
     fs.mfma_flops(6.0 * (double)a.nblocks * bm * bn * (double)kdim);
-    const bool kp = kdim != K;
+    const bool kp = kdim != nao;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a); };
-    if (bm == 128 && bn == 48) {
-        if (conjB) kp ? go(half1_kernel<true, 128, 2, true, 0, true>) : go(half1_kernel<true, 128, 2, true>);
-        else kp ? go(half1_kernel<false, 128, 2, true, 0, true>) : go(half1_kernel<false, 128, 2, true>);
-    } else if (bm == 128) {
-        if (conjB) kp ? go(half1_kernel<true, 128, 2, false, 0, true>) : go(half1_kernel<true, 128, 2, false>);
-        else kp ? go(half1_kernel<false, 128, 2, false, 0, true>) : go(half1_kernel<false, 128, 2, false>);
-    } else {
-        if (conjB) kp ? go(half1_kernel<true, 64, 3, false, 0, true>) : go(half1_kernel<true, 64, 3, false>);
-        else kp ? go(half1_kernel<false, 64, 3, false, 0, true>) : go(half1_kernel<false, 64, 3, false>);
-    }
+    if (bm == 128 && bn == 48) kp ? go(half1_kernel<true, 128, 2, true, 0, true>) : go(half1_kernel<true, 128, 2, true>);
+    else if (bm == 128) kp ? go(half1_kernel<true, 128, 2, false, 0, true>) : go(half1_kernel<true, 128, 2, false>);
+    else kp ? go(half1_kernel<true, 64, 3, false, 0, true>) : go(half1_kernel<true, 64, 3, false>);
     DMK_CHECK_LAUNCH(ctx);
     return 1;
 }
 
-int launch_half1_hot(dmk_ctx *ctx, const void *Lpq, const void *Ci, void *Ut, int nL, int nao, int nemb, int nspin,
-                     long long ci_spin_stride, long long ut_spin_stride, int kdim) {
-    if (nspin < 1 || nspin > 2) return 0;
-    return launch_flat_hot(ctx, Lpq, Ci, Ut, nL, nao, nao, nemb, true, DMK_FAM_ZGEMM_HALF1, nspin, ci_spin_stride, ut_spin_stride,
-                           1, 0, 0, 0, nullptr, kdim);
-}
-
-// Step 1 of `nslot` queued AO blocks in one launch: block s at Lpq + s * a_slot_stride, transformed with
-// C[spin][ki[s]] (C: [spin][nk][nao][nemb], spin stride ci_spin_stride) into Ut + s * ut_slot_stride (+ spin stride).
-int launch_half1_hot_multi(dmk_ctx *ctx, const void *Lpq, long long a_slot_stride, int nslot, const int *ki, const void *C,
-                           void *Ut, long long ut_slot_stride, int nL, int nao, int nemb, int nspin, long long ci_spin_stride,
-                           long long ut_spin_stride, int kdim) {
-    if (nspin < 1 || nspin > 2) return 0;
-    if (kdim == 0) kdim = nao;
-    return launch_flat_hot(ctx, Lpq, C, Ut, nL, nao, nao, nemb, true, DMK_FAM_ZGEMM_HALF1, nspin, ci_spin_stride, ut_spin_stride,
-                           nslot, a_slot_stride, ut_slot_stride, (long long)kdim * nemb, ki, kdim);
-}
-
-int launch_half2_hot(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj,
-                     const int *sym, double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
-                     long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int kdim, int re_only, int skip_invariant) {
-    if (kdim == 0) kdim = nao;
-    if (!hot_enabled() || nemb != H2_N || kdim < nao || (kdim % H2_BK) != 0 || nao < 3 * H2_BK || nslot < 1 || nslot > H2_MAXSLOT ||
-        nspin < 1 || nspin > 2)
-        return 0;
-    if (reinterpret_cast<uintptr_t>(Ut) & 15) return 0;
+int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q) {
+    if (q.first_row_block != 0 || q.nsub != 1 || q.planes_sub || q.sub_stride != 0)
+        return dmk_fail(ctx, DMK_ERR_INVALID, "half2_hot: first_row_block, nsub, planes_sub and sub_stride belong to the table kernel");
+    if (!half2_hot_usable(q.nao, q.nemb)) return 0;
     H2Args a;
-    a.Ut = reinterpret_cast<const double2 *>(Ut);
-    a.symmask = 0;
-    for (int i = 0; i < H2_MAXSLOT; ++i) {
-        a.Cj[i] = reinterpret_cast<const double2 *>(Cj[i < nslot ? i : 0]);
-        if (i < nslot && sym[i]) a.symmask |= 1u << i;
-        if (reinterpret_cast<uintptr_t>(a.Cj[i]) & 15) return 0;
-    }
-    a.slot_stride = slot_stride;
-    a.planes = planes; a.naux = naux; a.npair = npair;
-    a.nL = nL; a.nao = nao; a.nslot = nslot; a.kdim = kdim;
-    a.nspin = nspin;
-    a.ut_spin_stride = ut_spin_stride; a.cj_spin_stride = cj_spin_stride; a.planes_spin_stride = planes_spin_stride;
-    a.skip_invariant = skip_invariant ? 1 : 0;
-    a.nblocks = (unsigned)((skip_invariant ? 2 : 4) * nL * nspin);
-    a.fold_diag = (a.symmask == (nslot >= 32 ? 0xffffffffu : ((1u << nslot) - 1u))) ? 1 : 0;
+    if (!fill_half2_queue(a, q, H2_BK)) return 0;
+    a.skip_invariant = q.skip_invariant ? 1 : 0;
+    a.nblocks = (unsigned)((q.skip_invariant ? 2 : 4) * q.nL * q.nspin);
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
     {   // 136 of the 256 16 x 16 blocks per L and spin; a block with the time-reversal partner term runs a second segment
         // (without the 16 diagonal blocks when the whole group is symmetrised: they are folded in the epilogue)
         // skip_invariant: types 1 and 3 only -- 32 + 36 = 68 blocks, the partner term without the 8 diagonal blocks of type 3 when folded
-        double blocks = 0.0;
-        for (int i = 0; i < nslot; ++i) {
-            if (skip_invariant) blocks += 68.0 + (sym[i] ? (a.fold_diag ? 60.0 : 68.0) : 0.0);
-            else blocks += 136.0 + (sym[i] ? (a.fold_diag ? 120.0 : 136.0) : 0.0);
-        }
-        fs.mfma_flops((re_only ? 4.0 : 6.0) * blocks * 256.0 * (double)kdim * (double)nL * (double)nspin);
+        const double nsym = (double)__builtin_popcount(a.symmask);
+        const double blocks = q.skip_invariant ? 68.0 * q.nslot + (a.fold_diag ? 60.0 : 68.0) * nsym
+                                               : 136.0 * q.nslot + (a.fold_diag ? 120.0 : 136.0) * nsym;
+        fs.mfma_flops((q.re_only ? 4.0 : 6.0) * blocks * 256.0 * (double)a.kdim * (double)q.nL * (double)q.nspin);
     }
-    if (re_only) hipLaunchKernelGGL((half2_kernel<0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
+    if (q.re_only) hipLaunchKernelGGL((half2_kernel<0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
     else hipLaunchKernelGGL((half2_kernel<0, false>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
     DMK_CHECK_LAUNCH(ctx);
     return 1;

@@ -1,5 +1,5 @@
 // Shared pieces of the hot half-transform kernels (zhot.hip, zhot_tab.hip): the complex 16 x 16 x 4 tile step on the
-// real f64 MFMA and the tril-pack accumulate epilogue.
+// real f64 MFMA, the tril-pack accumulate epilogue and the queue part of the step-2 kernel arguments.
 #pragma once
 #include "common.h"
 
@@ -69,6 +69,38 @@ template <bool RE> __device__ __forceinline__ void pack_acc_t(double *planes, lo
     } else {
         pack_acc(planes, naux, npair, L, row, col, cacc_re(c, r), cacc_im(c, r), nrows);
     }
+}
+
+// Kernel-argument arrays must only be indexed with compile-time constants, and the argument struct must
+// never be passed by reference: either makes hipcc copy the whole struct to scratch (private memory), whose
+// loads need s_waitcnt vmcnt(0) -- draining the LDS-DMA ring -- and whose per-dispatch scratch set-up cost
+// ~17 ms per launch when a step-2 kernel first did it.
+#define H2_PICK_CJ(G, SLOT)                                                                        \
+    ((SLOT) == 0 ? (G).Cj[0] : (SLOT) == 1 ? (G).Cj[1] : (SLOT) == 2 ? (G).Cj[2] : (SLOT) == 3 ? (G).Cj[3]      \
+     : (SLOT) == 4 ? (G).Cj[4] : (SLOT) == 5 ? (G).Cj[5] : (SLOT) == 6 ? (G).Cj[6] : (SLOT) == 7 ? (G).Cj[7]    \
+     : (SLOT) == 8 ? (G).Cj[8] : (SLOT) == 9 ? (G).Cj[9] : (SLOT) == 10 ? (G).Cj[10] : (SLOT) == 11 ? (G).Cj[11] \
+     : (SLOT) == 12 ? (G).Cj[12] : (SLOT) == 13 ? (G).Cj[13] : (SLOT) == 14 ? (G).Cj[14] : (G).Cj[15])
+
+// Host side, what the kernel arguments of both step-2 kernels (H2Args, H2TArgs) share: the queue of a Half2Launch -- operands,
+// partner-term mask, strides, sizes and the K loop bound on a K tile of `bk` rows.  False where the launcher declines: a queue
+// length, spin count or K bound the kernels do not cover, or an operand off the 16 bytes of an LDS-DMA piece.
+template <class Args> bool fill_half2_queue(Args &a, const Half2Launch &q, int bk) {
+    constexpr int MAXSLOT = (int)(sizeof(a.Cj) / sizeof(a.Cj[0]));
+    const int kdim = q.kdim ? q.kdim : q.nao;
+    if (kdim < q.nao || (kdim % bk) != 0 || q.nslot < 1 || q.nslot > MAXSLOT || q.nspin < 1 || q.nspin > 2) return false;
+    if (reinterpret_cast<uintptr_t>(q.Ut) & 15) return false;
+    a.Ut = reinterpret_cast<const double2 *>(q.Ut); a.symmask = 0;
+    for (int i = 0; i < MAXSLOT; ++i) {
+        a.Cj[i] = reinterpret_cast<const double2 *>(q.Cj[i < q.nslot ? i : 0]);
+        if (i < q.nslot && q.sym[i]) a.symmask |= 1u << i;
+        if (reinterpret_cast<uintptr_t>(a.Cj[i]) & 15) return false;
+    }
+    a.slot_stride = q.slot_stride; a.planes = q.planes; a.naux = q.plane_rows; a.npair = q.row_len;
+    a.nL = q.nL; a.nao = q.nao; a.nslot = q.nslot; a.kdim = kdim; a.nspin = q.nspin;
+    a.ut_spin_stride = q.ut_spin_stride; a.cj_spin_stride = q.cj_spin_stride; a.planes_spin_stride = q.planes_spin_stride;
+    // every queued block carries the partner term: the diagonal blocks run one segment and are folded in the epilogue
+    a.fold_diag = (a.symmask == (1u << q.nslot) - 1u) ? 1 : 0;
+    return true;
 }
 
 }  // namespace

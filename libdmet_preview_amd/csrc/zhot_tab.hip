@@ -76,13 +76,6 @@ struct H2TArgs {
     unsigned per_sub;                // workgroups per run = nitems * nL * nspin
 };
 
-// kernel-argument arrays are only ever indexed by constants (see zhot.hip)
-#define T_PICK_CJ(G, SLOT)                                                                         \
-    ((SLOT) == 0 ? (G).Cj[0] : (SLOT) == 1 ? (G).Cj[1] : (SLOT) == 2 ? (G).Cj[2] : (SLOT) == 3 ? (G).Cj[3]      \
-     : (SLOT) == 4 ? (G).Cj[4] : (SLOT) == 5 ? (G).Cj[5] : (SLOT) == 6 ? (G).Cj[6] : (SLOT) == 7 ? (G).Cj[7]    \
-     : (SLOT) == 8 ? (G).Cj[8] : (SLOT) == 9 ? (G).Cj[9] : (SLOT) == 10 ? (G).Cj[10] : (SLOT) == 11 ? (G).Cj[11] \
-     : (SLOT) == 12 ? (G).Cj[12] : (SLOT) == 13 ? (G).Cj[13] : (SLOT) == 14 ? (G).Cj[14] : (G).Cj[15])
-
 // LAB: ablation bits of tools/zhot_lab.hip as in zhot.hip (1: no plane atomics, 2: no LDS-DMA after the prologue, 4: no
 // s_barrier); the product instantiates LAB = 0.
 template <class CFG, int LAB = 0, bool RE = false>
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(HNT, CFG::OCC) void half2_tab_kernel(const H2TArgs 
             voff[h] = (unsigned)((row * (int)nemb + clampcol(col)) * 16);
         }
         int is_t = 0, is_slot = slot0, is_stage = 0;
-        const double2 *is_ub = Ubase, *is_cb = T_PICK_CJ(g, slot0) + cj_off;
+        const double2 *is_ub = Ubase, *is_cb = H2_PICK_CJ(g, slot0) + cj_off;
         auto issue = [&]() {
             double2 *st = lds + is_stage * STAGE;
             // which operand piece wave + 4 h belongs to depends on h only (diagonal: U U C C; rectangle: Ua Cb Cb Ca Ub Ub; wide:
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(HNT, CFG::OCC) void half2_tab_kernel(const H2TArgs 
                 is_t = 0;
                 ++is_slot;
                 is_ub = Ubase + (long long)(is_slot - slot0) * g_slot_stride;
-                is_cb = T_PICK_CJ(g, is_slot) + cj_off;
+                is_cb = H2_PICK_CJ(g, is_slot) + cj_off;
             } else {
                 is_ub += T_BK * nemb;
                 is_cb += T_BK * nemb;
@@ -445,16 +438,12 @@ extern "C" int dmk_half2_tab_table(int nemb, int occ, int first_row_block, int *
     return DMK_OK;
 }
 
-// Returns 1 if handled, 0 if the caller must use the generic kernel, < 0 on error.  Arguments as launch_half2_hot (zhot.hip);
-// first_row_block: the launch leaves out the block rows below it (build_table), 1 without a launch when none is left.
-int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int nslot, const void *const *Cj, const int *sym,
-                     double *planes, long long naux, long long npair, int nL, int nao, int nemb, int nspin,
-                     long long ut_spin_stride, long long cj_spin_stride, long long planes_spin_stride, int nsub,
-                     double *planes_sub, long long sub_stride, int kdim, int re_only, int first_row_block) {
-    if (kdim == 0) kdim = nao;
-    if (kdim < nao || (kdim % T_BK) != 0) return 0;
-    if (!half2_tab_usable(nao, nemb) || nslot < 1 || nslot > T_MAXSLOT || nspin < 1 || nspin > 2) return 0;
-    if (reinterpret_cast<uintptr_t>(Ut) & 15) return 0;
+// Returns 1 if handled (also without a launch, when first_row_block leaves no block row: build_table), 0 if the caller must use
+// the generic kernel, < 0 on error.
+int launch_half2_tab(dmk_ctx *ctx, const Half2Launch &q) {
+    if (q.skip_invariant) return dmk_fail(ctx, DMK_ERR_INVALID, "half2_tab: skip_invariant belongs to the nemb = 256 kernel");
+    const int nemb = q.nemb, nL = q.nL, nslot = q.nslot, nspin = q.nspin;
+    if (!half2_tab_usable(q.nao, nemb)) return 0;
     // occupancy point (see Cfg2 / Cfg3).  Measured (MI355X, executed TF of this kernel): the evenly dealt WIDE items of small
     // embedding spaces gain from the third wave per SIMD (C4, nemb 136: 45.6 -> 54.8), the segment items of larger ones
     // lose more from their shorter block lists than they gain (nemb 256 routed here: 56.9 vs 50.4; its specialised
@@ -463,9 +452,9 @@ int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int ns
     if (const char *e = getenv("DMK_ERI_TAB_DECLINE")) if (atoi(e) != 0) return 0;
     const char *occ_e = getenv("DMK_ERI_TAB_OCC");          // read per launch (a handful per second): tests toggle it
     const int occ_env = occ_e ? atoi(occ_e) : 0;
-    const int occ = (occ_env == 2 || occ_env == 3) ? occ_env : ((nemb + 15) / 16 <= T_WIDE_MAXNB ? 3 : 2);
     const int nb = (nemb + 15) / 16;
-    if (first_row_block < 0) first_row_block = 0;
+    const int occ = (occ_env == 2 || occ_env == 3) ? occ_env : (nb <= T_WIDE_MAXNB ? 3 : 2);
+    const int first_row_block = std::max(q.first_row_block, 0);
     if (first_row_block >= nb) return 1;                   // every block row is already in the planes: nothing to launch
     const dmk_ctx::StepTable *tb = nullptr;
     for (auto &t : ctx->step2_tables)
@@ -486,26 +475,13 @@ int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int ns
         tb = &ctx->step2_tables.back();
     }
     H2TArgs a;
-    a.Ut = reinterpret_cast<const double2 *>(Ut);
-    a.symmask = 0;
-    double segs = 0.0;
-    for (int i = 0; i < T_MAXSLOT; ++i) {
-        a.Cj[i] = reinterpret_cast<const double2 *>(Cj[i < nslot ? i : 0]);
-        if (i < nslot && sym[i]) a.symmask |= 1u << i;
-        if (i < nslot) segs += sym[i] ? 2.0 : 1.0;
-        if (reinterpret_cast<uintptr_t>(a.Cj[i]) & 15) return 0;
-    }
-    a.slot_stride = slot_stride;
-    a.planes = planes; a.naux = naux; a.npair = npair;
-    a.nL = nL; a.nao = nao; a.nslot = nslot; a.nemb = nemb; a.kdim = kdim;
-    a.nspin = nspin;
-    a.ut_spin_stride = ut_spin_stride; a.cj_spin_stride = cj_spin_stride; a.planes_spin_stride = planes_spin_stride;
+    if (!fill_half2_queue(a, q, T_BK)) return 0;
+    a.nemb = nemb;
     a.table = tb->dev; a.nitems = tb->nitems;
-    a.fold_diag = (a.symmask == (nslot >= 32 ? 0xffffffffu : ((1u << nslot) - 1u))) ? 1 : 0;
-    if (nsub < 1 || !planes_sub) nsub = 1;
+    const int nsub = (q.nsub < 1 || !q.planes_sub) ? 1 : q.nsub;
     a.sub_slots = (nslot + nsub - 1) / nsub;
     a.nsub = (nslot + a.sub_slots - 1) / a.sub_slots;                 // runs that actually hold blocks
-    a.planes_sub = planes_sub; a.sub_stride = sub_stride;
+    a.planes_sub = q.planes_sub; a.sub_stride = q.sub_stride;
     const unsigned long long per_sub = (unsigned long long)tb->nitems * (unsigned)nL * (unsigned)nspin;
     const unsigned long long nblocks = per_sub * (unsigned)a.nsub;
     if (nblocks > 0x7fffffffull) return 0;
@@ -513,13 +489,13 @@ int launch_half2_tab(dmk_ctx *ctx, const void *Ut, long long slot_stride, int ns
     a.nblocks = (unsigned)nblocks;
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
     // a symmetrised block runs a second segment -- without the folded diagonal blocks when the whole group is symmetrised
-    const double seg2 = (segs - (double)nslot) * (tb->useful_blocks - (a.fold_diag ? tb->folded_blocks : 0.0));
-    fs.mfma_flops((re_only ? 4.0 : 6.0) * ((double)nslot * tb->useful_blocks + seg2) * 256.0 * (double)kdim * (double)nL * (double)nspin);
+    const double seg2 = (double)__builtin_popcount(a.symmask) * (tb->useful_blocks - (a.fold_diag ? tb->folded_blocks : 0.0));
+    fs.mfma_flops((q.re_only ? 4.0 : 6.0) * ((double)nslot * tb->useful_blocks + seg2) * 256.0 * (double)a.kdim * (double)nL * (double)nspin);
     if (occ == 2) {
-        if (re_only) hipLaunchKernelGGL((half2_tab_kernel<Cfg2, 0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
+        if (q.re_only) hipLaunchKernelGGL((half2_tab_kernel<Cfg2, 0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
         else hipLaunchKernelGGL((half2_tab_kernel<Cfg2, 0, false>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
     } else {
-        if (re_only) hipLaunchKernelGGL((half2_tab_kernel<Cfg3, 0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
+        if (q.re_only) hipLaunchKernelGGL((half2_tab_kernel<Cfg3, 0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
         else hipLaunchKernelGGL((half2_tab_kernel<Cfg3, 0, false>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
     }
     DMK_CHECK_LAUNCH(ctx);

@@ -93,7 +93,7 @@ def _run(ctx, Ce, df, eri_dev, cache=None, inv_cols=None, prefill=None, nslots=N
 
 
 def _flops(run, skip):
-    """Executed flop of one stacked contraction over all kL as launch_dgemm_tn_acc_seg counts it: tiles of the table x 128 x 128 x
+    """Executed flop of one stacked contraction over all kL as launch_dgemm_tn_acc counts it: tiles of the table x 128 x 128 x
     2 K per launch; the K of the launches of a spin block add up to 48 rows per weight-2 kL (Re and Im planes) and 24 per
     weight-1 kL; blocks aa and bb run the symmetric table, ab the rectangular one."""
     K = sum(48 if run["weights"][k] == 2 else 24 for k in run["kL"])

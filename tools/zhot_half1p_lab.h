@@ -39,7 +39,7 @@ __global__ __launch_bounds__(HNT, OCC) void half1p_kernel(const H1Args g) {
     const unsigned last = (unsigned)((unsigned long long)(blockIdx.x + 1) * g.nblocks / gridDim.x);
     if (first >= last) return;
     const unsigned nao = (unsigned)g.nao, mrows = (unsigned)g.mrows;
-    const unsigned rows_total = (unsigned)g.nL * mrows;              // < 2^31 (launch_flat_hot)
+    const unsigned rows_total = (unsigned)g.nL * mrows;              // < 2^31 (launch_half1_hot)
     const long long nemb = g.nemb;
     const int T = g.nao / H1_BK;
 

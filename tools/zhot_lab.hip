@@ -58,7 +58,7 @@ int main() {
     double *planes = (double *)dalloc((size_t)nspin * 2 * nL * npair * 8, 0.0);
     hipDeviceSynchronize();
 
-    // ---- step 1: as launch_flat_hot (BM 128, BN 64, both spins, 8 slots) ---------------------------------------------------
+    // ---- step 1: as launch_half1_hot (BM 128, BN 64, both spins, 8 slots) ---------------------------------------------------
     H1Args a;
     a.Lpq = Lpq; a.Ci = C; a.Ut = Ut;
     a.nL = nL; a.nao = nao; a.kdim = nao; a.nemb = nemb; a.mrows = nao; a.nblk = (nao + 15) / 16;
@@ -151,7 +151,7 @@ int main() {
         const size_t ut4 = (size_t)nL4 * nao4 * nemb4;
         std::vector<int> tab;
         double useful, slots, folded;
-        build_table(nemb4, Cfg3::MAXBLK, Cfg3::SEG, tab, useful, slots, folded);
+        build_table(nemb4, Cfg3::MAXBLK, Cfg3::SEG, 0, tab, useful, slots, folded);
         int *dtab = nullptr;
         hipMalloc(&dtab, tab.size() * sizeof(int));
         hipMemcpy(dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice);
