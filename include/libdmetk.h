@@ -308,7 +308,8 @@ int dmk_eri_push_ring_slot(dmk_eri *h, int ki, int kj, int symmetrise);
 int dmk_eri_ring_slot(dmk_eri *h, int slot, void **ptr_out, void **stream_out);
 /* Transform the blocks queued so far NOW (one step-1 and one step-2 launch) instead of when the queue is full: a caller that
  * knows how many blocks a kL has cuts them into launches of equal length (33 blocks: 11 + 11 + 11, not 16 + 16 + 1).  The next
- * ring slot to fill is slot 0 again. */
+ * ring slot to fill is slot 0 again.  (With fused launches, dmk_eri_fused_launches, step 1 is enqueued by this call and step 2 with
+ * the next group's step 1 -- at the latest when the kL ends or dmk_eri_planes is called.) */
 int dmk_eri_flush(dmk_eri *h);
 /* AO blocks that are already RESIDENT in device memory -- a DF tensor (or the part of it this rank's kL shard reads) kept in HBM
  * across the DMET iterations instead of being re-read from the cderi file for every transform (eri_transform.py:358-366 reads each
@@ -448,6 +449,12 @@ int dmk_eri_finish(dmk_eri *h);
 /* ALGORITHMIC flop counters of the work pushed so far:
  * [0] half transform, [1] contraction. */
 int dmk_eri_flops(const dmk_eri *h, double flops_host[2]);
+/* Fused launches so far.  Inside a kL the nemb = 256 path does not launch step 2 of a group fed through the ring (or read in place,
+ * dmk_eri_push_resident) at its flush: it goes out in ONE launch with step 1 of the next group, whose workgroups fill the slots
+ * the last, partly empty round of step-2 workgroups leaves idle (the first step 1 and the last step 2 of a kL stay launches of
+ * their own).  Results are bit-identical either way.  Ut then holds two halves; where that memory is not to be had, or with
+ * DMK_ERI_FUSE=0, every group runs its two launches as before and the count stays 0. */
+int dmk_eri_fused_launches(const dmk_eri *h, int64_t *count);
 /* Without time reversal (dmk_eri_begin flags bit 0 clear) and with flags bit 1 set, the pipeline also accumulates the
  * IMAGINARY part of every contraction, Re_a^T Im_b - Im_a^T Re_b; this returns its max-abs so far -- the
  * `eri_imag_norm = max_abs(eri.imag)` diagnostic of eri_transform.py:385-394 (compared with ERI_IMAG_TOL by the

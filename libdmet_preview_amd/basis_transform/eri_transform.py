@@ -1241,6 +1241,14 @@ class EriEngine(object):
         self.ctx.check(lib.dmk_eri_flops(self.h, f))
         return float(f[0]), float(f[1])
 
+    @property
+    def fused_launches(self):
+        """Launches so far that ran step 2 of one group and step 1 of the next together (dmk_eri_fused_launches; 0 with
+        DMK_ERI_FUSE=0 and on every path but the grouped nemb = 256 one)."""
+        n = C.c_int64(0)
+        self.ctx.check(lib.dmk_eri_fused_launches(self.h, C.byref(n)))
+        return int(n.value)
+
     def planes(self):
         p = C.c_void_p()
         n = C.c_int64()

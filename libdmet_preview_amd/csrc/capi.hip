@@ -47,7 +47,7 @@ void FamScope::begin() {
 FamScope::~FamScope() {
     if (ctx && ctx->profile && a && b) {
         (void)hipEventRecord(b, on_set ? on : ctx->stream);
-        ctx->pending.push_back({fam, a, b});
+        ctx->pending.push_back({fam, a, b, fam2, share});
     }
 }
 
@@ -55,7 +55,10 @@ static void drain_pending(dmk_ctx *ctx) {
     for (auto &p : ctx->pending) {
         float ms = 0.f;
         if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess)
-            ctx->fam_ms[p.fam] += ms;
+        {
+            ctx->fam_ms[p.fam] += p.fam2 >= 0 ? ms * p.share : ms;
+            if (p.fam2 >= 0) ctx->fam_ms[p.fam2] += ms * (1.0 - p.share);
+        }
         ctx->event_pool.push_back(p.a);
         ctx->event_pool.push_back(p.b);
     }

@@ -21,7 +21,7 @@ struct dmk_ctx {
     double fam_ms[DMK_FAM_COUNT] = {0};
     int64_t fam_launches[DMK_FAM_COUNT] = {0};
     double fam_mfma_flops[DMK_FAM_COUNT] = {0};   // flop ISSUED to the matrix pipe (tiles launched x MFMAs per tile x 512)
-    struct Pending { int fam; hipEvent_t a, b; };
+    struct Pending { int fam; hipEvent_t a, b; int fam2; double share; };    // fam2 >= 0: `share` of the interval is fam's, the rest fam2's
     std::vector<Pending> pending;
     std::vector<hipEvent_t> event_pool;
     // scratch owned by the context (grown on demand)
@@ -86,6 +86,17 @@ struct FamScope {
     // flop this launch issues to the f64 matrix pipe (executed, not algorithmic: 3M complex products, padded tiles,
     // the lower tile triangle of a symmetric contraction); read back by dmk_profile_read_flops
     void mfma_flops(double f) { if (ctx) ctx->fam_mfma_flops[fam] += f; }
+    // one launch that does the work of two families (zhot.hip half12_kernel): `flops` / `flops2` are what each side issues; the
+    // event interval is split between the families in that proportion and the second family counts a launch of its own
+    int fam2 = -1; double share = 1.0;
+    void share_with(int f2, double flops, double flops2) {
+        if (!ctx) return;
+        fam2 = f2;
+        share = flops + flops2 > 0.0 ? flops / (flops + flops2) : 0.5;
+        ctx->fam_mfma_flops[fam] += flops;
+        ctx->fam_mfma_flops[f2] += flops2;
+        ctx->fam_launches[f2] += 1;
+    }
 };
 
 int dmk_scratch(dmk_ctx *ctx, size_t bytes, void **out);
@@ -344,6 +355,10 @@ struct Half2Launch {
     double *planes_sub = nullptr; long long sub_stride = 0;
 };
 int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q);
+// Step 2 of `q2` and step 1 of `q1` (the NEXT group: it must not write what q2 reads) in one launch.  1: launched, 0: declined and
+// nothing launched (the caller runs q2, then q1), < 0: error.  half12_hot_usable: could a group of this shape be fused at all?
+int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1);
+int half12_hot_usable(int nL, int nao, int nemb);
 int launch_half2_tab(dmk_ctx *ctx, const Half2Launch &q);
 int half2_hot_usable(int nao, int nemb);
 int half2_hot_maxslot();

@@ -100,7 +100,27 @@ struct dmk_eri {
     std::vector<SlotKey> slot_keys;
     uint64_t cur_key = 0;
     bool cur_keyed = false;
+    // FUSED LAUNCHES (zhot.hip half12_kernel): inside a kL, step 2 of a group whose step 1 runs at its flush (ring
+    // slots, resident blocks) is not launched at once but kept in `deferred` and goes out in ONE launch with step 1 of the next
+    // group; eri_drain launches it alone where there is no next group.  Ut then has two halves, ut_half_elems apart, each with
+    // the rows of the K padding behind it, and consecutive deferred groups alternate between them: step 1 of group g + 1 never
+    // writes what step 2 of group g reads.  Everything step 2 of a group needs is held by value.
+    struct Step2Group {
+        Half2Launch q;              // (Cj and sym stay unset here: desc() points them at the arrays below)
+        const void *cj[16]; int sym[16], kj[16];
+        const double2 *ut = nullptr;
+        int n = 0, slot = 0;
+        bool inv_warm = false, live = false;
+        Half2Launch desc() const { Half2Launch r = q; r.Cj = cj; r.sym = sym; return r; }
+    };
+    bool fuse = false;            // DMK_ERI_FUSE (default on), the nemb = 256 kernel, one range of L per block, memory for both halves
+    int ut_half = 0;              // the half the group being queued is transformed into
+    size_t ut_half_elems = 0;
+    Step2Group deferred;
+    int64_t fused_launches = 0;
     dmk_eri(dmk_ctx *c, const int m[3]) : ctx(c), mesh(m) {}
+
+    double2 *ut_cur() const { return Ut + (size_t)ut_half * ut_half_elems; }
 
     double *slot_planes(int slot, int spin_idx) const {
         return planes + ((size_t)spin_idx * nslots + slot) * 2 * (size_t)pr * pl;
@@ -120,6 +140,8 @@ struct dmk_eri {
         return w == 2 ? WeightClass{0, n_w2, (int)(2 * pr), 2.0} : WeightClass{nslots - n_w1, n_w1, (int)pr, 1.0};
     }
 };
+
+extern "C" { static int eri_drain(dmk_eri *h); }
 
 namespace {
 
@@ -193,6 +215,7 @@ void ws_park(dmk_ctx *ctx, int slot, void *p, size_t capacity, bool park) {
 // the context for the next pipeline (dmk_eri_finish); a dmk_eri_begin that fails frees them.
 void eri_release(dmk_eri *h, bool park) {
     dmk_ctx *ctx = h->ctx;
+    (void)eri_drain(h);
     (void)hipStreamSynchronize(ctx->stream);
     if (h->copy_stream) {
         (void)hipStreamSynchronize(h->copy_stream);
@@ -288,17 +311,31 @@ int dmk_eri_begin(dmk_ctx *ctx, const int mesh[3], int nao, int naux, int nemb, 
     const bool kpad = half1_hot_usable(h->hot_rows, nao, nemb) && hot_kdim(nao) != nao;
     if (kpad) h->kdim = hot_kdim(nao);
     const size_t plane_bytes = (size_t)spin * 2 * h->pr * h->pl * sizeof(double);
-    const size_t ut_bytes = (size_t)h->lchunk * nao * nemb * sizeof(double2) * (h->group > 1 ? (size_t)h->group * spin : 1) +
-                            (size_t)(h->kdim - nao) * nemb * sizeof(double2);
+    const size_t half_bytes = (size_t)h->lchunk * nao * nemb * sizeof(double2) * (h->group > 1 ? (size_t)h->group * spin : 1) +
+                              (size_t)(h->kdim - nao) * nemb * sizeof(double2);
+    // fused launches: a second half of Ut (C5: + 10.5 GB) where a group can be fused at all -- the grouped nemb = 256 path, step 1
+    // of a block in one range of L and on the tile of half12_kernel; DMK_ERI_FUSE=0 keeps the launch sequence without them
+    {
+        const char *e = getenv("DMK_ERI_FUSE");
+        h->fuse = !(e && atoi(e) == 0) && h->hot256 && h->group > 1 && h->hot_rows >= naux && half12_hot_usable(naux, nao, nemb) != 0;
+    }
+    size_t ut_bytes = half_bytes * (h->fuse ? 2 : 1);
     h->planes = reinterpret_cast<double *>(ws_take(ctx, 0, plane_bytes, &h->ws_bytes[0]));
     h->Ut = reinterpret_cast<double2 *>(ws_take(ctx, 1, ut_bytes, &h->ws_bytes[1]));
+    if (h->planes && !h->Ut && h->fuse) {          // no room for the second half: one half, separate launches
+        (void)hipGetLastError();
+        h->fuse = false;
+        ut_bytes = half_bytes;
+        h->Ut = reinterpret_cast<double2 *>(ws_take(ctx, 1, ut_bytes, &h->ws_bytes[1]));
+    }
+    h->ut_half_elems = half_bytes / sizeof(double2);
     if (!h->planes || !h->Ut) {
         eri_release(h, false);
         return dmk_fail(ctx, DMK_ERR_NOMEM, "eri_begin: workspace allocation failed (%zu + %zu bytes)", plane_bytes, ut_bytes);
     }
     if (kpad) {
         // Step 2 reads kdim - nao rows past every L of Ut against the zero rows of Ch: whatever is there must be FINITE (a queue
-        // slot that step 1 has not written yet, the tail of a parked workspace) -- the buffer is zeroed once.
+        // slot that step 1 has not written yet, the tail of a parked workspace) -- the buffer, both halves, is zeroed once.
         const size_t cb = (size_t)spin * m.nk * h->kdim * nemb * sizeof(double2);
         bool ok = dmk_dev_alloc(ctx, reinterpret_cast<void **>(&h->Cpad), cb) == hipSuccess;
         ok = ok && hipMemsetAsync(h->Cpad, 0, cb, ctx->stream) == hipSuccess;
@@ -327,9 +364,9 @@ int dmk_eri_begin(dmk_ctx *ctx, const int mesh[3], int nao, int naux, int nemb, 
 
 int dmk_eri_finish(dmk_eri *h) {
     if (!h) return DMK_OK;
-    int rc_stack = DMK_OK;
+    int rc_stack = eri_drain(h);
     // planes still waiting for their contraction (a rows-only pipeline just drops them: its caller took the rows it wanted)
-    if (h->eri && h->nslots > 1 && h->cur_kL < 0 && h->n_w2 + h->n_w1 > 0) {
+    if (rc_stack == DMK_OK && h->eri && h->nslots > 1 && h->cur_kL < 0 && h->n_w2 + h->n_w1 > 0) {
         rc_stack = eri_contract_stack(h, -1, -1);
         h->n_w2 = h->n_w1 = 0;
     }
@@ -344,6 +381,12 @@ int dmk_eri_flops(const dmk_eri *h, double f[2]) {
     return DMK_OK;
 }
 
+int dmk_eri_fused_launches(const dmk_eri *h, int64_t *count) {
+    if (!h || !count) return DMK_ERR_INVALID;
+    *count = h->fused_launches;
+    return DMK_OK;
+}
+
 // =============================================================================================
 // begin of a kL
 // =============================================================================================
@@ -352,6 +395,7 @@ static int eri_begin_kL_impl(dmk_eri *h, int kL, int weight) {
     dmk_ctx *ctx = h->ctx;
     if (kL < 0 || kL >= h->mesh.nk) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_begin_kL: kL out of range");
     if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_begin_kL: previous kL not ended");
+    if (int rcd = eri_drain(h)) return rcd;           // (a deferred step 2 never outlives its kL: nothing to do here)
     h->cur_slot = 0;
     const char *re_env = getenv("DMK_ERI_RE_ONLY");             // read per kL (a handful per second): tests toggle it
     h->re_only = !(re_env && atoi(re_env) == 0) && h->tr && weight == 1 && !h->imag;
@@ -430,13 +474,80 @@ static ZGemm half2_desc(const dmk_eri *h, const double2 *ut, int nl, const doubl
 static Half1Launch half1_hot_desc(const dmk_eri *h, const double2 *L, int l0, int nl, int slot) {
     Half1Launch q;
     q.Lpq = L + (size_t)l0 * h->nao * h->nao; q.C = h->Ch;
-    q.Ut = h->Ut + (size_t)slot * h->slot_elems() + (size_t)l0 * h->nao * h->nemb;
+    q.Ut = h->ut_cur() + (size_t)slot * h->slot_elems() + (size_t)l0 * h->nao * h->nemb;
     q.nL = nl; q.nao = h->nao; q.nemb = h->nemb; q.nspin = h->spin; q.kdim = h->kdim;
     q.ci_spin_stride = h->c_spin_stride(); q.ut_spin_stride = (long long)h->group * (long long)h->slot_elems();
     return q;
 }
 
-static int eri_ring_step1(dmk_eri *h) {
+// Step 2 of the queued group as the queue stands now: operands, planes and flags by value
+static void eri_step2_group(const dmk_eri *h, dmk_eri::Step2Group &g) {
+    const int nao = h->nao, naux = h->naux, nemb = h->nemb;
+    g.n = h->pending; g.slot = h->cur_slot; g.ut = h->ut_cur(); g.inv_warm = h->inv_warm; g.live = false;
+    for (int i = 0; i < g.n; ++i) {
+        g.kj[i] = h->pend_kj[i];
+        g.sym[i] = h->pend_sym[i];
+        g.cj[i] = h->Ch + (size_t)h->pend_kj[i] * h->kdim * nemb;
+    }
+    // one launch for both spin channels: C, Ut and the planes of spin 1 sit at constant offsets from those of spin 0
+    Half2Launch q;
+    q.Ut = g.ut; q.slot_stride = (long long)h->slot_elems(); q.nslot = g.n;
+    q.planes = h->slot_planes(g.slot, 0); q.plane_rows = h->pr; q.row_len = h->pl;
+    q.nL = naux; q.nao = nao; q.nemb = nemb; q.nspin = h->spin; q.kdim = h->kdim;
+    q.ut_spin_stride = (long long)h->group * q.slot_stride; q.cj_spin_stride = h->c_spin_stride();
+    q.planes_spin_stride = h->planes_spin_stride(); q.re_only = h->re_only;
+    q.skip_invariant = h->hot256 && g.inv_warm;
+    g.q = q;
+}
+
+// Step 2 of a group in a launch of its own
+static int eri_step2_launch(dmk_eri *h, const dmk_eri::Step2Group &g) {
+    dmk_ctx *ctx = h->ctx;
+    const int nao = h->nao, naux = h->naux, nemb = h->nemb;
+    Half2Launch q = g.desc();
+    int rc;
+    if (h->hot256) {
+        rc = launch_half2_hot(ctx, q);
+        if (rc == 0 && g.inv_warm)
+            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the nemb = 256 step-2 kernel declined a kL whose invariant planes came from the cache");
+    } else {
+        q.first_row_block = g.inv_warm ? h->inv_A / 16 : 0;
+        if (h->sub_planes) {
+            q.nsub = half2_tab_subgroups(ctx, naux, nao, nemb, h->spin, g.n, h->nsub_max);
+            q.planes_sub = h->sub_planes; q.sub_stride = (long long)h->spin * 2LL * h->pr * h->pl;
+        }
+        rc = launch_half2_tab(ctx, q);
+        if (rc == 0 && g.inv_warm)      // (the generic fallback below would add the cached region a second time)
+            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the table-driven step-2 kernel declined a kL whose invariant planes came from the cache");
+        if (rc == 1) h->sub_used = std::max(h->sub_used, q.nsub);
+    }
+    if (rc < 0) return rc;
+    if (rc == 0) {
+        // the grouped kernel declined (misaligned buffer, a table it cannot build): step 2 of every queued block through the
+        // generic c128 GEMM with the same tril-pack epilogue -- slower (one launch per block and spin), never wrong
+        for (int i = 0; i < g.n; ++i)
+            for (int s = 0; s < h->spin; ++s) {
+                const double2 *ut = g.ut + ((size_t)s * h->group + i) * h->slot_elems();
+                const double2 *Cj = h->C + ((size_t)s * h->mesh.nk + g.kj[i]) * nao * nemb;
+                int rg = launch_zgemm(ctx, half2_desc(h, ut, naux, Cj, g.sym[i], h->slot_planes(g.slot, s)), DMK_FAM_ZGEMM_HALF2);
+                if (rg) return rg;
+            }
+    }
+    return DMK_OK;
+}
+
+// The deferred step 2, if there is one, in a launch of its own: wherever something reads or finalises the planes or Ut and no
+// later group of the kL will carry it
+static int eri_drain(dmk_eri *h) {
+    if (!h->deferred.live) return DMK_OK;
+    h->deferred.live = false;
+    return eri_step2_launch(h, h->deferred);
+}
+
+// Step 1 of the queued ring slots / resident blocks into the current half of Ut.  `with`: a deferred step 2 that goes out in the
+// same launch (half12_kernel), or first and on its own where the fused launcher declines.  With a producer stream the event wait
+// and record stay where they are: around the launch that runs this step 1.
+static int eri_ring_step1(dmk_eri *h, dmk_eri::Step2Group *with = nullptr) {
     dmk_ctx *ctx = h->ctx;
     if (h->ring_pending == 0) return DMK_OK;
     const int nao = h->nao, naux = h->naux;
@@ -448,7 +559,15 @@ static int eri_ring_step1(dmk_eri *h) {
         Half1Launch q = half1_hot_desc(h, src, l0, nl, 0);
         q.nslot = h->ring_pending; q.ki = h->pend_ki;
         q.a_slot_stride = (long long)naux * nao * nao; q.ut_slot_stride = (long long)h->slot_elems();
-        int rc = launch_half1_hot(ctx, q);
+        int rc = 0;
+        if (with && with->live) {
+            with->live = false;
+            rc = launch_half12_hot(ctx, with->desc(), q);
+            if (rc < 0) return rc;
+            if (rc == 1) h->fused_launches += 1;
+            else if (int r2 = eri_step2_launch(h, *with)) return r2;
+        }
+        if (rc == 0) rc = launch_half1_hot(ctx, q);
         if (rc < 0) return rc;
         if (rc == 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri ring: hot step-1 kernel unavailable for the queued blocks");
     }
@@ -461,52 +580,26 @@ static int eri_ring_step1(dmk_eri *h) {
 }
 
 static int eri_flush(dmk_eri *h) {
-    dmk_ctx *ctx = h->ctx;
     if (h->pending == 0) return DMK_OK;
-    {
-        int rc1 = eri_ring_step1(h);
+    dmk_eri::Step2Group g;
+    eri_step2_group(h, g);
+    // A group whose step 1 runs here is deferred: its step 1 goes out with the step 2 deferred before it (alone for the first
+    // group of a kL) and its own step 2 waits for the next group or the drain.  Blocks pushed directly ran step 1 at the push.
+    if (h->fuse && h->ring_pending == h->pending) {
+        int rc1 = eri_ring_step1(h, &h->deferred);
         if (rc1) return rc1;
+        h->deferred = g;
+        h->deferred.live = true;
+        h->ut_half ^= 1;
+        h->pending = 0;
+        return DMK_OK;
     }
-    const int nao = h->nao, naux = h->naux, nemb = h->nemb;
-    // one launch for both spin channels: C, Ut and the planes of spin 1 sit at constant offsets from those of spin 0
-    const void *cj[16];
-    for (int i = 0; i < h->pending; ++i)
-        cj[i] = h->Ch + (size_t)h->pend_kj[i] * h->kdim * nemb;
-    Half2Launch q;
-    q.Ut = h->Ut; q.slot_stride = (long long)h->slot_elems(); q.nslot = h->pending; q.Cj = cj; q.sym = h->pend_sym;
-    q.planes = h->slot_planes(h->cur_slot, 0); q.plane_rows = h->pr; q.row_len = h->pl;
-    q.nL = naux; q.nao = nao; q.nemb = nemb; q.nspin = h->spin; q.kdim = h->kdim;
-    q.ut_spin_stride = (long long)h->group * q.slot_stride; q.cj_spin_stride = h->c_spin_stride();
-    q.planes_spin_stride = h->planes_spin_stride(); q.re_only = h->re_only;
-    int rc;
-    if (h->hot256) {
-        q.skip_invariant = h->inv_warm;
-        rc = launch_half2_hot(ctx, q);
-        if (rc == 0 && h->inv_warm)
-            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the nemb = 256 step-2 kernel declined a kL whose invariant planes came from the cache");
-    } else {
-        q.first_row_block = h->inv_warm ? h->inv_A / 16 : 0;
-        if (h->sub_planes) {
-            q.nsub = half2_tab_subgroups(ctx, naux, nao, nemb, h->spin, h->pending, h->nsub_max);
-            q.planes_sub = h->sub_planes; q.sub_stride = (long long)h->spin * 2LL * h->pr * h->pl;
-        }
-        rc = launch_half2_tab(ctx, q);
-        if (rc == 0 && h->inv_warm)      // (the generic fallback below would add the cached region a second time)
-            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the table-driven step-2 kernel declined a kL whose invariant planes came from the cache");
-        if (rc == 1) h->sub_used = std::max(h->sub_used, q.nsub);
-    }
-    if (rc < 0) return rc;
-    if (rc == 0) {
-        // the grouped kernel declined (misaligned buffer, a table it cannot build): step 2 of every queued block through the
-        // generic c128 GEMM with the same tril-pack epilogue -- slower (one launch per block and spin), never wrong
-        for (int i = 0; i < h->pending; ++i)
-            for (int s = 0; s < h->spin; ++s) {
-                const double2 *ut = h->Ut + ((size_t)s * h->group + i) * h->slot_elems();
-                const double2 *Cj = h->C + ((size_t)s * h->mesh.nk + h->pend_kj[i]) * nao * nemb;
-                int rg = launch_zgemm(ctx, half2_desc(h, ut, naux, Cj, h->pend_sym[i], h->slot_planes(h->cur_slot, s)), DMK_FAM_ZGEMM_HALF2);
-                if (rg) return rg;
-            }
-    }
+    int rc = eri_drain(h);
+    if (rc) return rc;
+    rc = eri_ring_step1(h);
+    if (rc) return rc;
+    rc = eri_step2_launch(h, g);
+    if (rc) return rc;
     h->pending = 0;
     return DMK_OK;
 }
@@ -538,6 +631,7 @@ int dmk_eri_push_block(dmk_eri *h, int ki, int kj, int symmetrise, const void *L
         return dmk_fail(ctx, DMK_ERR_INVALID, "eri_push_block: bad arguments");
     const int nao = h->nao, naux = h->naux, nemb = h->nemb;
     const double2 *L = reinterpret_cast<const double2 *>(Lpq);
+    if (int rcd = eri_drain(h)) return rcd;        // step 1 runs at the push here: nothing is deferred across it
     if (h->group > 1) {
         // hot path: step 1 now (it consumes the caller's block buffer), step 2 when the queue is full
         if (h->ring_pending) {
@@ -557,7 +651,7 @@ int dmk_eri_push_block(dmk_eri *h, int ki, int kj, int symmetrise, const void *L
         if (rc_hot < 0) return rc_hot;
         for (int s = 0; s < h->spin && rc_hot == 0; ++s) {
             const double2 *Ci = h->C + ((size_t)s * h->mesh.nk + ki) * nao * nemb;
-            double2 *ut = h->Ut + ((size_t)s * h->group + slot) * h->slot_elems();
+            double2 *ut = h->ut_cur() + ((size_t)s * h->group + slot) * h->slot_elems();
             int rc = launch_zgemm(ctx, half1_desc(h, L, naux, Ci, ut), DMK_FAM_ZGEMM_HALF1);
             if (rc) return rc;
         }
@@ -710,6 +804,8 @@ int dmk_eri_push_resident(dmk_eri *h, const void *blocks, int nblk, const int32_
 int dmk_eri_flush(dmk_eri *h) {
     if (!h) return DMK_ERR_INVALID;
     if (h->cur_kL < 0) return dmk_fail(h->ctx, DMK_ERR_STATE, "eri_flush: no kL in progress");
+    // (no drain: this is how a caller cuts a kL into groups -- step 1 of the group is enqueued now, so its ring slots may be
+    // rewritten; its step 2 goes out with the next group's step 1, or when the kL ends or the planes are asked for)
     return eri_flush(h);
 }
 
@@ -765,6 +861,8 @@ int dmk_eri_planes(dmk_eri *h, double **planes_out, int64_t *elems_out) {
     if (!h || !planes_out) return DMK_ERR_INVALID;
     {
         int rcf = eri_flush(h);      // queued blocks must land before anyone looks at the planes
+        if (rcf) return rcf;
+        rcf = eri_drain(h);
         if (rcf) return rcf;
         if (h->cur_kL >= 0) {
             rcf = eri_fold_subplanes(h, true);
@@ -846,6 +944,8 @@ static int eri_kl_close(dmk_eri *h, int weight, bool gso, int *K, int *Kalg, dou
     dmk_ctx *ctx = h->ctx;
     const char *who = gso ? "eri_end_kL_gso" : "eri_end_kL";
     int rc = eri_flush(h);
+    if (rc) return rc;
+    rc = eri_drain(h);
     if (rc) return rc;
     rc = eri_fold_subplanes(h);
     if (rc) return rc;
@@ -972,6 +1072,7 @@ int dmk_eri_stack(dmk_eri *h, int nslots_wanted, int *nslots_granted) {
     if (!h) return DMK_ERR_INVALID;
     dmk_ctx *ctx = h->ctx;
     if (nslots_wanted < 1) return dmk_fail(ctx, DMK_ERR_INVALID, "eri_stack: needs at least one slot");
+    if (int rcd = eri_drain(h)) return rcd;
     if (h->cur_kL >= 0 || h->n_w2 + h->n_w1 > 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_stack: a kL is in progress or the stack is not empty");
     if ((h->imag || !h->tr) && nslots_wanted > 1) nslots_wanted = 1;          // the non-time-reversal branch contracts per kL
     const size_t slot_bytes = (size_t)h->spin * 2 * h->pr * h->pl * sizeof(double);
@@ -996,6 +1097,7 @@ int dmk_eri_stack(dmk_eri *h, int nslots_wanted, int *nslots_granted) {
 
 int dmk_eri_probe(dmk_eri *h, const double *x, double *yref) {
     if (!h) return DMK_ERR_INVALID;
+    if (int rcd = eri_drain(h)) return rcd;
     if ((x == nullptr) != (yref == nullptr)) return dmk_fail(h->ctx, DMK_ERR_INVALID, "eri_probe: x and yref go together (both NULL: off)");
     if (x && !h->eri) return dmk_fail(h->ctx, DMK_ERR_STATE, "eri_probe: a rows-only pipeline contracts nothing to probe");
     if (h->n_w2 + h->n_w1 > 0 || h->cur_kL >= 0) return dmk_fail(h->ctx, DMK_ERR_STATE, "eri_probe: set it before the first kL of a plane set");
@@ -1008,6 +1110,7 @@ int dmk_eri_probe(dmk_eri *h, const double *x, double *yref) {
 int dmk_eri_contract(dmk_eri *h, int band_lo, int band_hi, int done) {
     if (!h) return DMK_ERR_INVALID;
     dmk_ctx *ctx = h->ctx;
+    if (int rcd = eri_drain(h)) return rcd;
     if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_contract: a kL is in progress");
     if (h->nslots > 1) {
         int rc = eri_contract_stack(h, band_lo, band_hi);
@@ -1024,6 +1127,7 @@ int dmk_eri_contract_rows(dmk_eri *h, int64_t row_lo, int64_t row_hi, double *ou
     if (!h) return DMK_ERR_INVALID;
     dmk_ctx *ctx = h->ctx;
     const int64_t np = h->npair;
+    if (int rcd = eri_drain(h)) return rcd;
     if (h->cur_kL >= 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_contract_rows: a kL is in progress");
     if (h->nslots <= 1) return dmk_fail(ctx, DMK_ERR_STATE, "eri_contract_rows: needs a plane stack (dmk_eri_stack)");
     if (!out || row_lo < 0 || row_hi > np || row_lo >= row_hi || (row_lo & 1))

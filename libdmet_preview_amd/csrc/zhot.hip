@@ -94,122 +94,20 @@ struct H1Args {
 // for dimensions on the tile is the kernel of rounds 2 - 5, instruction for instruction (the clamp measured 2.4 % on it).
 template <bool CONJB, int BM, int OCC, bool NARROW, int LAB = 0, bool KPAD = false>
 __global__ __launch_bounds__(HNT, OCC) void half1_kernel(const H1Args g) {
-    constexpr int MI = NARROW ? BM / 64 : BM / 32;       // 16-row blocks per wave
-    constexpr int NJ = NARROW ? 3 : 2;                   // 16-column blocks per wave
-    constexpr int BN = NARROW ? 48 : H1_BN;              // columns of the output tile
-    constexpr int AH = BM / 64;                          // 1 KiB pieces per K row of the A panel
-    constexpr int STAGE = H1_BK * (BM + H1_BN);
-    __shared__ __attribute__((aligned(16))) double2 lds[H1_D * STAGE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keeps the LDS-DMA addressing scalar
-    // 2 (M) x 2 (N) waves with wave tile (BM / 2) x 32, or 4 (M) x 1 waves with wave tile (BM / 4) x 48
-    const int wm = NARROW ? wave : wave >> 1, wn = NARROW ? 0 : wave & 1;
-    const int frag_k = lane >> 4, frag_x = lane & 15;
+    __shared__ __attribute__((aligned(16))) double2 lds[H1_D * H1_BK * (BM + H1_BN)];
+#define ZH_BLOCK_ID blockIdx.x
+#include "zhot_half1_body.inc"
+#undef ZH_BLOCK_ID
+}
 
-    const unsigned lid_all = xcd_remap(blockIdx.x, g.nblocks);
-    const int slot = (int)(lid_all / g.per_slot);
-    const unsigned lid = lid_all - (unsigned)slot * g.per_slot;
-    const unsigned per_m = (unsigned)(g.tiles_n * g.nspin);
-    const int tile_m = (int)(lid / per_m);
-    const unsigned rest = lid - (unsigned)tile_m * per_m;
-    const int sp = (int)(rest / (unsigned)g.tiles_n), tile_n = (int)(rest - (unsigned)sp * (unsigned)g.tiles_n);
-    const int n0 = tile_n * BN;
-    const long long nao = g.nao, nemb = g.nemb, mrows = g.mrows;
-    const long long rows_total = (long long)g.nL * mrows;
-    const double2 *const Asl = g.Lpq + (long long)slot * g.a_slot_stride;
-    const double2 *const Bsp = g.Ci + (long long)sp * g.b_spin_stride + (long long)H1_PICK_BK(g, slot) * g.b_k_stride;
-    double2 *const Osp = g.Ut + (long long)sp * g.out_spin_stride + (long long)slot * g.out_slot_stride;
-
-    // ---- LDS-DMA sources: wave w streams K rows 2w, 2w+1 (A: 2 x 1 KiB per row, B: 1 KiB).  Per lane only a loop-invariant byte
-    //      offset from the block's base (one VGPR per piece; a block is <= 512 MB); the K-row part of the address is scalar ----
-    unsigned voffA[AH], voffB;
-#pragma unroll
-    for (int h = 0; h < AH; ++h) {
-        long long r = (long long)tile_m * BM + 64 * h + lane;
-        if (r >= rows_total) r = rows_total - 1;         // clamped lanes only ever feed masked outputs
-        const long long L = r / mrows, q = r - L * mrows;
-        voffA[h] = (unsigned)((L * nao * mrows + q) * 16);
-    }
-    {
-        int col = n0 + lane;
-        if (col >= g.nemb) col = g.nemb - 1;
-        voffB = (unsigned)(col * 16);
-    }
-    auto issue = [&](int t) {
-        double2 *st = lds + (t % H1_D) * STAGE;
-        const int k0 = wave * 2;
-        const long long kg = (long long)t * H1_BK + k0;
-        const double2 *a0 = Asl + kg * mrows, *a1 = a0 + mrows, *b0 = Bsp + kg * nemb, *b1 = b0 + nemb;      // wave-uniform
-        if constexpr (KPAD) {                                // rows of the padding: the block's last row (see H1Args::kdim)
-            const int last = (int)nao - 1, k32 = t * H1_BK + k0;
-            a0 = Asl + (long long)(k32 < last ? k32 : last) * mrows;
-            a1 = Asl + (long long)(k32 + 1 < last ? k32 + 1 : last) * mrows;
-        }
-        if constexpr (AH == 2) {
-            glds16s_x6(voffA[0], voffA[1], voffB, voffA[0], voffA[1], voffB, a0, a0, b0, a1, a1, b1, lds_addr_of(st + k0 * BM),
-                       lds_addr_of(st + k0 * BM + 64), lds_addr_of(st + H1_BK * BM + k0 * H1_BN), lds_addr_of(st + (k0 + 1) * BM),
-                       lds_addr_of(st + (k0 + 1) * BM + 64), lds_addr_of(st + H1_BK * BM + (k0 + 1) * H1_BN));
-        } else {
-            glds16s_x4(voffA[0], voffB, voffA[0], voffB, a0, b0, a1, b1, lds_addr_of(st + k0 * BM),
-                       lds_addr_of(st + H1_BK * BM + k0 * H1_BN), lds_addr_of(st + (k0 + 1) * BM),
-                       lds_addr_of(st + H1_BK * BM + (k0 + 1) * H1_BN));
-        }
-    };
-
-    cacc acc[MI][NJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) cacc_zero(acc[i][j]);
-
-    const int T = (KPAD ? g.kdim : g.nao) / H1_BK;
-    issue(0);
-    if (T > 1) issue(1);
-    for (int t = 0; t < T; ++t) {
-        if (t + 1 < T) {                                                     // tile t landed; tile t+1 may be in flight
-            if (AH == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        if constexpr (!(LAB & 4)) __builtin_amdgcn_s_barrier();
-        if constexpr (LAB & 2) { if (t + 2 < T && g.nslot < 0) issue(t + 2); }
-        else { if (t + 2 < T) issue(t + 2); }
-        const double2 *Ab = lds + (t % H1_D) * STAGE + wm * (MI * 16) + frag_x;
-        const double2 *Bb = lds + (t % H1_D) * STAGE + H1_BK * BM + wn * 32 + frag_x;
-#pragma unroll
-        for (int kk = 0; kk < H1_BK / 4; ++kk) {
-            cfrag a[MI], b[NJ];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) a[i] = cfrag_of(lds_frag(&Ab[(kk * 4 + frag_k) * BM + i * 16]));
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                double2 v = lds_frag(&Bb[(kk * 4 + frag_k) * H1_BN + j * 16]);
-                if (CONJB) v.y = -v.y;                  // conj(C_i)
-                b[j] = cfrag_of(v);
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) cmfma(acc[i][j], a[i], b[j]);
-        }
-    }
-
-    // ---- epilogue: Ut[L][q][a] = row (L * mrows + q) of one contiguous (nL * mrows) x nemb array ----------------------
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long rr = (long long)tile_m * BM + (wm * MI + i) * 16 + frag_k + 4 * r;
-            if (rr >= rows_total) continue;
-            if constexpr (LAB & 1) { if (g.nslot >= 0) continue; }
-            double2 *row = Osp + rr * nemb;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int col = n0 + wn * 32 + j * 16 + frag_x;
-                if (col < g.nemb) row[col] = make_double2(cacc_re(acc[i][j], r), cacc_im(acc[i][j], r));
-            }
-        }
-    }
+// The same body as a device function: block `bid` of a step-1 grid of g.nblocks, on an LDS ring the caller owns (half12_kernel).
+// half1_kernel includes the text instead of calling this: behind a call, even an inlined one, hipcc schedules the body differently,
+// and the kernels of the separate launches are kept instruction for instruction.
+template <bool CONJB, int BM, bool NARROW, int LAB, bool KPAD>
+__device__ __forceinline__ void half1_body(const H1Args &g, const unsigned bid, double2 *const lds) {
+#define ZH_BLOCK_ID bid
+#include "zhot_half1_body.inc"
+#undef ZH_BLOCK_ID
 }
 
 // =============================================================================================
@@ -254,246 +152,35 @@ struct H2Args {
 template <int LAB = 0, bool RE = false>
 __global__ __launch_bounds__(HNT, 2) void half2_kernel(const H2Args g) {
     __shared__ __attribute__((aligned(16))) double2 lds[H2_LDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar LDS-DMA addressing
-    const int frag_k = lane >> 4, frag_x = lane & 15;
-    const unsigned lid = xcd_remap(blockIdx.x, g.nblocks);
-    // (blockIdx and kernel arguments only: wave-uniform either way)
-    const int Lall = g.skip_invariant ? (int)(lid >> 1) : (int)(lid >> 2);
-    const int type = g.skip_invariant ? 1 + 2 * (int)(lid & 1) : (int)(lid & 3);
-    const int sp = Lall >= g.nL ? 1 : 0;     // nspin <= 2
-    const int L = Lall - sp * g.nL;
-    const long long nemb = H2_N;
-    const int Tb = g.kdim / H2_BK;           // K-tiles per AO block
-    const int T = Tb * g.nslot;              // the ring runs straight through all queued blocks
-    const double2 *Ubase = g.Ut + (long long)sp * g.ut_spin_stride + (long long)L * g.nao * nemb;
-    double *const g_planes = g.planes + (long long)sp * g.planes_spin_stride;
-    const long long cj_off = (long long)sp * g.cj_spin_stride;
-    const long long g_naux = g.naux, g_npair = g.npair, g_slot_stride = g.slot_stride;
-    const unsigned g_symmask = g.symmask;
-    const bool fold = g.fold_diag != 0;
+#define ZH_BLOCK_ID blockIdx.x
+#include "zhot_half2_body.inc"
+#undef ZH_BLOCK_ID
+}
 
-    if (type >= 2) {
-        // ---------------- diagonal triangle [d0, d0+128)^2 ----------------------------------------
-        const int d0 = (type - 2) * 128;
-        // stage = 16 pieces of 64 complex: piece p < 8 -> U row p/2, half p%2 ; p >= 8 -> C likewise; 4 pieces per wave
-        unsigned voff[4];                      // byte offset of this lane's 16 B inside a K-tile of the operand
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int piece = wave + 4 * h;
-            voff[h] = (unsigned)((((piece & 7) >> 1) * (int)nemb + d0 + (piece & 1) * 64 + lane) * 16);
-        }
-        // running issue state (wave-uniform, SGPRs): no division and no kernel-argument load per K-tile
-        int is_t = 0, is_slot = 0, is_stage = 0;
-        const double2 *is_ub = Ubase, *is_cb = H2_PICK_CJ(g, 0) + cj_off;
-        // (spreading the four pieces of a tile over the MFMA stream of a K step, instead of a burst after the barrier,
-        // measured 2.5 % slower: the inline-asm DMA statements pin the compiler's MFMA / ds_read schedule)
-        auto issue_advance = [&]() {
-            is_stage = is_stage + 1 == H2T_D ? 0 : is_stage + 1;
-            if (++is_t == Tb) {
-                is_t = 0;
-                ++is_slot;
-                is_ub = Ubase + (long long)is_slot * g_slot_stride;
-                is_cb = H2_PICK_CJ(g, is_slot) + cj_off;
-            } else {
-                is_ub += H2_BK * nemb;
-                is_cb += H2_BK * nemb;
-            }
-        };
-        auto issue = [&]() {
-            double2 *st = lds + is_stage * H2T_STAGE;
-            // scalar tile bases + loop-invariant per-lane byte offsets: no vector ALU work per piece (common.h glds16s_x4)
-            glds16s_x4(voff[0], voff[1], voff[2], voff[3], is_ub, is_ub, is_cb, is_cb, lds_addr_of(st + wave * 64),
-                       lds_addr_of(st + (wave + 4) * 64), lds_addr_of(st + (wave + 8) * 64), lds_addr_of(st + (wave + 12) * 64));
-            issue_advance();
-        };
-        auto run = [&](auto tag) {
-            constexpr int R1 = decltype(tag)::value;
-            constexpr int R2 = 7 - R1;
-            cacc acc1[R1 + 1], acc2[R2 + 1];
-#pragma unroll
-            for (int c = 0; c <= R1; ++c) cacc_zero(acc1[c]);
-#pragma unroll
-            for (int c = 0; c <= R2; ++c) cacc_zero(acc2[c]);
-            issue();
-            if (T > 1) issue();
-            if (T > 2) issue();
-            int c_t = 0, c_stage = 0;
-            unsigned c_sym = g_symmask & 1u, c_mask = g_symmask;
-            for (int t = 0; t < T; ++t) {
-                const int later = T - 1 - t;
-                if (later >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else if (later == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if constexpr (!(LAB & 4)) __builtin_amdgcn_s_barrier();
-                if constexpr (LAB & 2) { if (t + 3 < T && g.nslot < 0) issue(); }
-                else { if (t + 3 < T) issue(); }
-                const double2 *U = lds + c_stage * H2T_STAGE + frag_k * 128 + frag_x;
-                c_stage = c_stage + 1 == H2T_D ? 0 : c_stage + 1;
-                const double2 *C = U + H2_BK * 128;
-                {   // segment 1: S[a][b] += U[q][a] C[q][b]   (one B fragment live at a time)
-                    const cfrag a1 = cfrag_of_t<RE>(lds_frag(&U[R1 * 16])), a2 = cfrag_of_t<RE>(lds_frag(&U[R2 * 16]));
-#pragma unroll
-                    for (int c = 0; c <= R2; ++c) {
-                        const cfrag b = cfrag_of_t<RE>(lds_frag(&C[c * 16]));
-                        if (c <= R1) cmfma_t<RE>(acc1[c <= R1 ? c : 0], a1, b);
-                        cmfma_t<RE>(acc2[c], a2, b);
-                    }
-                }
-                if (c_sym) {   // segment 2: S[a][b] += C[q][a] U[q][b]   (same two panels)
-                    const cfrag a1 = cfrag_of_t<RE>(lds_frag(&C[R1 * 16])), a2 = cfrag_of_t<RE>(lds_frag(&C[R2 * 16]));
-#pragma unroll
-                    for (int c = 0; c <= R2; ++c) {
-                        const cfrag b = cfrag_of_t<RE>(lds_frag(&U[c * 16]));
-                        if (c < R1 || (c == R1 && !fold)) cmfma_t<RE>(acc1[c <= R1 ? c : 0], a1, b);
-                        if (c < R2 || !fold) cmfma_t<RE>(acc2[c], a2, b);
-                    }
-                }
-                if (++c_t == Tb) {
-                    c_t = 0;
-                    c_mask >>= 1;
-                    c_sym = c_mask & 1u;
-                }
-            }
-            if (fold) {
-                // diagonal blocks hold P = U_r^T C_r only: add P^T through a wave-private LDS tile (the ring is idle now)
-                __syncthreads();
-                double *tr = reinterpret_cast<double *>(lds) + wave * (2 * 16 * 17);
-                auto fold_block = [&](cacc &acc) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        tr[(frag_k + 4 * r) * 17 + frag_x] = cacc_re(acc, r);
-                        if constexpr (!RE) tr[272 + (frag_k + 4 * r) * 17 + frag_x] = cacc_im(acc, r);
-                    }
-                    double tre[4], tim[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {                      // the LDS pipe keeps a wave's own accesses in order
-                        tre[r] = tr[frag_x * 17 + frag_k + 4 * r];
-                        tim[r] = RE ? 0.0 : tr[272 + frag_x * 17 + frag_k + 4 * r];
-                    }
-                    // fold into the T1 / T2 / T3 representation: Re += tre, Im += tim  (T1 += tre, T3 += tre + tim)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        acc.p[r] += tre[r];
-                        if constexpr (!RE) acc.t[r] += tre[r] + tim[r];
-                    }
-                };
-                fold_block(acc1[R1]);
-                fold_block(acc2[R2]);
-            }
-            if constexpr (LAB & 1) { if (g.nslot >= 0) return; }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row1 = d0 + R1 * 16 + frag_k + 4 * r, row2 = d0 + R2 * 16 + frag_k + 4 * r;
-#pragma unroll
-                for (int c = 0; c <= R1; ++c)
-                    pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row1, d0 + c * 16 + frag_x, acc1[c], r);
-#pragma unroll
-                for (int c = 0; c <= R2; ++c)
-                    pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row2, d0 + c * 16 + frag_x, acc2[c], r);
-            }
-        };
-        switch (wave) {
-            case 0: run(std::integral_constant<int, 0>{}); break;
-            case 1: run(std::integral_constant<int, 1>{}); break;
-            case 2: run(std::integral_constant<int, 2>{}); break;
-            default: run(std::integral_constant<int, 3>{}); break;
-        }
-        return;
-    }
+// (as half1_body: the device function of the same text, for half12_kernel)
+template <int LAB, bool RE>
+__device__ __forceinline__ void half2_body(const H2Args &g, const unsigned bid, double2 *const lds) {
+#define ZH_BLOCK_ID bid
+#include "zhot_half2_body.inc"
+#undef ZH_BLOCK_ID
+}
 
-    // ---------------- off-diagonal half square: rows [r0, r0+64) x cols [0,128) -------------------------
-    const int r0 = 128 + 64 * type;
-    const int wm = wave >> 1, wn = wave & 1;            // wave tile 32 x 64
-    // stage = 24 pieces of 64 complex: 0-3 Ua rows, 4-11 Cb (row*2+half), 12-15 Ca rows, 16-23 Ub (row*2+half)
-    unsigned voff[6];
-#pragma unroll
-    for (int h = 0; h < 6; ++h) {
-        const int piece = wave + 4 * h;
-        int row, col;
-        if (piece < 4) { row = piece; col = r0; }
-        else if (piece < 12) { row = (piece - 4) >> 1; col = ((piece - 4) & 1) * 64; }
-        else if (piece < 16) { row = piece - 12; col = r0; }
-        else { row = (piece - 16) >> 1; col = ((piece - 16) & 1) * 64; }
-        voff[h] = (unsigned)((row * (int)nemb + col + lane) * 16);
-    }
-    int is_t = 0, is_slot = 0, is_stage = 0;
-    const double2 *is_ub = Ubase, *is_cb = H2_PICK_CJ(g, 0) + cj_off;
-    auto issue = [&]() {
-        double2 *st = lds + is_stage * H2S_STAGE;
-        // pieces wave + 4 h: h = 0 Ua, 1-2 Cb, 3 Ca, 4-5 Ub -- which operand a piece belongs to does not depend on the wave, so the
-        // bases are the two scalar tile pointers and the per-lane part is a loop-invariant byte offset (common.h glds16s_x6)
-        glds16s_x6(voff[0], voff[1], voff[2], voff[3], voff[4], voff[5], is_ub, is_cb, is_cb, is_cb, is_ub, is_ub, lds_addr_of(st + wave * 64),
-                   lds_addr_of(st + (wave + 4) * 64), lds_addr_of(st + (wave + 8) * 64), lds_addr_of(st + (wave + 12) * 64),
-                   lds_addr_of(st + (wave + 16) * 64), lds_addr_of(st + (wave + 20) * 64));
-        is_stage = is_stage + 1 == H2S_D ? 0 : is_stage + 1;
-        if (++is_t == Tb) {
-            is_t = 0;
-            ++is_slot;
-            is_ub = Ubase + (long long)is_slot * g_slot_stride;
-            is_cb = H2_PICK_CJ(g, is_slot) + cj_off;
-        } else {
-            is_ub += H2_BK * nemb;
-            is_cb += H2_BK * nemb;
-        }
-    };
-    cacc acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cacc_zero(acc[i][j]);
-    issue();
-    if (T > 1) issue();
-    int c_t = 0, c_stage = 0;
-    unsigned c_sym = g_symmask & 1u, c_mask = g_symmask;
-    for (int t = 0; t < T; ++t) {
-        if (t + 1 < T) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (!(LAB & 4)) __builtin_amdgcn_s_barrier();
-        if constexpr (LAB & 2) { if (t + 2 < T && g.nslot < 0) issue(); }
-        else { if (t + 2 < T) issue(); }
-        const double2 *Ua = lds + c_stage * H2S_STAGE + frag_k * 64 + wm * 32 + frag_x;
-        const double2 *Cb = lds + c_stage * H2S_STAGE + 256 + frag_k * 128 + wn * 64 + frag_x;
-        c_stage = c_stage + 1 == H2S_D ? 0 : c_stage + 1;
-        const double2 *Ca = Ua + 768;
-        const double2 *Ub = Cb + 768;
-        {
-            cfrag a[2], b[4];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = cfrag_of_t<RE>(lds_frag(&Ua[i * 16]));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = cfrag_of_t<RE>(lds_frag(&Cb[j * 16]));
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) cmfma_t<RE>(acc[i][j], a[i], b[j]);
-        }
-        if (c_sym) {
-            cfrag a[2], b[4];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = cfrag_of_t<RE>(lds_frag(&Ca[i * 16]));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = cfrag_of_t<RE>(lds_frag(&Ub[j * 16]));
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) cmfma_t<RE>(acc[i][j], a[i], b[j]);
-        }
-        if (++c_t == Tb) {
-            c_t = 0;
-            c_mask >>= 1;
-            c_sym = c_mask & 1u;
-        }
-    }
-    if constexpr (LAB & 1) { if (g.nslot >= 0) return; }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = r0 + wm * 32 + i * 16 + frag_k + 4 * r;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row, wn * 64 + j * 16 + frag_x, acc[i][j], r);
-        }
+// =============================================================================================
+// steps 2 and 1 in ONE launch: step 2 of a queued group and, behind it, step 1 of the NEXT group
+// =============================================================================================
+// A step-2 launch is a few thousand workgroups of equal length on 512 resident slots (256 CUs x 2): C5 warm 3200 -> 6.25 rounds,
+// paid as 7 with 3/4 of the slots empty in the last one.  Step 1 of the next group (tens of thousands of short workgroups, the
+// same 256 threads, 2 workgroups per CU and 73 728 B of LDS) does not depend on it once Ut has two halves, but an in-order stream
+// never overlaps two launches.  Here the step-2 workgroups take the low block ids and the step-1 workgroups follow: as step-2
+// workgroups retire, their slots go to step 1 at once.  Every workgroup does what it does in the separate launches -- the same
+// body, the same arguments, its block id within its own grid (XCD remap over its own count) -- so results are bit-identical.
+// One LDS array serves whichever body runs (two would halve the occupancy).  Step-1 side: the 128 x 64 tile only.
+constexpr int H12_LDS = (H1_D * H1_BK * (H1_BM + H1_BN) > H2_LDS) ? H1_D * H1_BK * (H1_BM + H1_BN) : H2_LDS;
+template <bool RE, bool KPAD>
+__global__ __launch_bounds__(HNT, 2) void half12_kernel(const H2Args g2, const H1Args g1) {
+    __shared__ __attribute__((aligned(16))) double2 lds[H12_LDS];
+    if (blockIdx.x < g2.nblocks) half2_body<0, RE>(g2, blockIdx.x, lds);
+    else half1_body<true, H1_BM, false, 0, KPAD>(g1, blockIdx.x - g2.nblocks, lds);
 }
 
 bool hot_enabled() {
@@ -524,36 +211,75 @@ int half1_hot_max_rows(int nao) {
 // K loop bound of the hot kernels for an AO dimension: the next multiple of the step-1 K tile (8; the step-2 tiles are 4)
 int hot_kdim(int nao) { return (nao + H1_BK - 1) / H1_BK * H1_BK; }
 
-// Returns 1 if the hot path handled the launch, 0 if the caller must use the generic kernel, < 0 on error.
-int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q) {
+namespace {
+
+// Output tile of a step-1 launch for embedding dimension N: BM rows (128; DMK_ERI_H1_BM=64 asks for 64) by 64 columns (2 x 2 waves)
+// or 48 (4 x 1 waves), whichever pads N less; DMK_ERI_H1_BN = 64 | 48 overrides
+void half1_hot_tile(int N, int &bm, int &bn) {
+    static const int bm_env = [] { const char *e = getenv("DMK_ERI_H1_BM"); return (e && atoi(e) == 64) ? 64 : 128; }();
+    bm = bm_env;
+    bn = (((N + 47) / 48) * 48 < ((N + 63) / 64) * 64) ? 48 : 64;
+    if (const char *e = getenv("DMK_ERI_H1_BN")) { const int v = atoi(e); if (v == 48 || v == 64) bn = v; }
+    if (bm != 128) bn = 64;
+}
+
+// What launch_half1_hot and launch_half12_hot share: the launch of `q` as the step-1 kernel sees it -- arguments, tile and the flop
+// it issues -- or false where the hot kernel declines it.
+bool half1_hot_plan(const Half1Launch &q, H1Args &a, int &bm, int &bn, double &flops) {
     const int nL = q.nL, nao = q.nao, N = q.nemb, nslot = q.nslot;
     const int kdim = q.kdim ? q.kdim : nao;             // B holds kdim rows, zero beyond nao
-    if (q.nspin < 1 || q.nspin > 2 || nslot < 1 || nslot > 16 || kdim < nao || (kdim % H1_BK) != 0) return 0;
-    if (!half1_hot_usable(nL, nao, N)) return 0;
-    static const int bm = [] { const char *e = getenv("DMK_ERI_H1_BM"); return (e && atoi(e) == 64) ? 64 : 128; }();
-    if ((reinterpret_cast<uintptr_t>(q.Lpq) | reinterpret_cast<uintptr_t>(q.C) | reinterpret_cast<uintptr_t>(q.Ut)) & 15) return 0;
-    H1Args a;
+    if (q.nspin < 1 || q.nspin > 2 || nslot < 1 || nslot > 16 || kdim < nao || (kdim % H1_BK) != 0) return false;
+    if (!half1_hot_usable(nL, nao, N)) return false;
+    if ((reinterpret_cast<uintptr_t>(q.Lpq) | reinterpret_cast<uintptr_t>(q.C) | reinterpret_cast<uintptr_t>(q.Ut)) & 15) return false;
+    half1_hot_tile(N, bm, bn);
     a.Lpq = reinterpret_cast<const double2 *>(q.Lpq);
     a.Ci = reinterpret_cast<const double2 *>(q.C);
     a.Ut = reinterpret_cast<double2 *>(q.Ut);
     a.nL = nL; a.nao = nao; a.nemb = N; a.mrows = nao; a.kdim = kdim;
     a.nblk = (nao + 15) / 16;
     a.tiles_m = (int)(((long long)nL * nao + bm - 1) / bm);          // flat rows: no padding between the nL batches
-    // output tile width: 64 columns (2 x 2 waves) or 48 (4 x 1 waves), whichever pads N less; DMK_ERI_H1_BN = 64 | 48 overrides
-    int bn = (((N + 47) / 48) * 48 < ((N + 63) / 64) * 64) ? 48 : 64;
-    if (const char *e = getenv("DMK_ERI_H1_BN")) { const int v = atoi(e); if (v == 48 || v == 64) bn = v; }
-    if (bm != 128) bn = 64;
     a.tiles_n = (N + bn - 1) / bn;
     a.nspin = q.nspin; a.b_spin_stride = q.ci_spin_stride; a.out_spin_stride = q.ut_spin_stride;
     a.nslot = nslot; a.a_slot_stride = q.a_slot_stride; a.out_slot_stride = q.ut_slot_stride;
     a.b_k_stride = q.ki ? (long long)kdim * N : 0;
     for (int i = 0; i < 16; ++i) a.bk[i] = (q.ki && i < nslot) ? q.ki[i] : 0;
     a.per_slot = (unsigned)(a.tiles_m * a.tiles_n * q.nspin);
-    if ((unsigned long long)a.per_slot * (unsigned)nslot > 0x7fffffffull) return 0;
+    if ((unsigned long long)a.per_slot * (unsigned)nslot > 0x7fffffffull) return false;
     a.nblocks = a.per_slot * (unsigned)nslot;
+    flops = 6.0 * (double)a.nblocks * bm * bn * (double)kdim;
+    return true;
+}
+
+// The same for step 2 on the nemb = 256 kernel: 1 with `a` and `flops` set, 0 where the kernel declines, < 0 for a launch that
+// carries fields of the table kernel.
+int half2_hot_plan(dmk_ctx *ctx, const Half2Launch &q, H2Args &a, double &flops) {
+    if (q.first_row_block != 0 || q.nsub != 1 || q.planes_sub || q.sub_stride != 0)
+        return dmk_fail(ctx, DMK_ERR_INVALID, "half2_hot: first_row_block, nsub, planes_sub and sub_stride belong to the table kernel");
+    if (!half2_hot_usable(q.nao, q.nemb)) return 0;
+    if (!fill_half2_queue(a, q, H2_BK)) return 0;
+    a.skip_invariant = q.skip_invariant ? 1 : 0;
+    a.nblocks = (unsigned)((q.skip_invariant ? 2 : 4) * q.nL * q.nspin);
+    // 136 of the 256 16 x 16 blocks per L and spin; a block with the time-reversal partner term runs a second segment
+    // (without the 16 diagonal blocks when the whole group is symmetrised: they are folded in the epilogue)
+    // skip_invariant: types 1 and 3 only -- 32 + 36 = 68 blocks, the partner term without the 8 diagonal blocks of type 3 when folded
+    const double nsym = (double)__builtin_popcount(a.symmask);
+    const double blocks = q.skip_invariant ? 68.0 * q.nslot + (a.fold_diag ? 60.0 : 68.0) * nsym
+                                           : 136.0 * q.nslot + (a.fold_diag ? 120.0 : 136.0) * nsym;
+    flops = (q.re_only ? 4.0 : 6.0) * blocks * 256.0 * (double)a.kdim * (double)q.nL * (double)q.nspin;
+    return 1;
+}
+
+}  // namespace
+
+// Returns 1 if the hot path handled the launch, 0 if the caller must use the generic kernel, < 0 on error.
+int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q) {
+    H1Args a;
+    int bm, bn;
+    double flops;
+    if (!half1_hot_plan(q, a, bm, bn, flops)) return 0;
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF1);
-    fs.mfma_flops(6.0 * (double)a.nblocks * bm * bn * (double)kdim);
-    const bool kp = kdim != nao;
+    fs.mfma_flops(flops);
+    const bool kp = a.kdim != a.nao;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a); };
     if (bm == 128 && bn == 48) kp ? go(half1_kernel<true, 128, 2, true, 0, true>) : go(half1_kernel<true, 128, 2, true>);
     else if (bm == 128) kp ? go(half1_kernel<true, 128, 2, false, 0, true>) : go(half1_kernel<true, 128, 2, false>);
@@ -563,24 +289,48 @@ int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q) {
 }
 
 int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q) {
-    if (q.first_row_block != 0 || q.nsub != 1 || q.planes_sub || q.sub_stride != 0)
-        return dmk_fail(ctx, DMK_ERR_INVALID, "half2_hot: first_row_block, nsub, planes_sub and sub_stride belong to the table kernel");
-    if (!half2_hot_usable(q.nao, q.nemb)) return 0;
     H2Args a;
-    if (!fill_half2_queue(a, q, H2_BK)) return 0;
-    a.skip_invariant = q.skip_invariant ? 1 : 0;
-    a.nblocks = (unsigned)((q.skip_invariant ? 2 : 4) * q.nL * q.nspin);
+    double flops;
+    const int rc = half2_hot_plan(ctx, q, a, flops);
+    if (rc != 1) return rc;
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
-    {   // 136 of the 256 16 x 16 blocks per L and spin; a block with the time-reversal partner term runs a second segment
-        // (without the 16 diagonal blocks when the whole group is symmetrised: they are folded in the epilogue)
-        // skip_invariant: types 1 and 3 only -- 32 + 36 = 68 blocks, the partner term without the 8 diagonal blocks of type 3 when folded
-        const double nsym = (double)__builtin_popcount(a.symmask);
-        const double blocks = q.skip_invariant ? 68.0 * q.nslot + (a.fold_diag ? 60.0 : 68.0) * nsym
-                                               : 136.0 * q.nslot + (a.fold_diag ? 120.0 : 136.0) * nsym;
-        fs.mfma_flops((q.re_only ? 4.0 : 6.0) * blocks * 256.0 * (double)a.kdim * (double)q.nL * (double)q.nspin);
-    }
+    fs.mfma_flops(flops);
     if (q.re_only) hipLaunchKernelGGL((half2_kernel<0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
     else hipLaunchKernelGGL((half2_kernel<0, false>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
+    DMK_CHECK_LAUNCH(ctx);
+    return 1;
+}
+
+// Would a group of this shape go through the fused launch at all?  (dmk_eri_begin: whether Ut gets its second half.)  The tile rule
+// is the one half1_hot_plan applies; launch_half12_hot still decides every launch.
+int half12_hot_usable(int nL, int nao, int nemb) {
+    if (!half1_hot_usable(nL, nao, nemb) || !half2_hot_usable(nao, nemb)) return 0;
+    int bm, bn;
+    half1_hot_tile(nemb, bm, bn);
+    return bm == H1_BM && bn == H1_BN;
+}
+
+// Step 2 of one queued group and step 1 of the next one in ONE launch (half12_kernel).  1: launched; 0: declined -- one of the two
+// separate launchers would decline, or step 1 would not run the 128 x 64 tile -- and nothing was launched; < 0: error.
+int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1) {
+    H2Args a2;
+    H1Args a1;
+    int bm, bn;
+    double f1, f2;
+    const int rc = half2_hot_plan(ctx, q2, a2, f2);
+    if (rc != 1) return rc;
+    if (!half1_hot_plan(q1, a1, bm, bn, f1) || bm != H1_BM || bn != H1_BN) return 0;
+    const bool kp = a1.kdim != a1.nao;
+    const unsigned long long nb = (unsigned long long)a2.nblocks + a1.nblocks;
+    if (nb > 0x7fffffffull) return 0;
+    // One event interval for both families: it is split between them in proportion to the flop each side
+    // issues, so both show the combined rate of the launch -- a true fraction of the peak -- and their sum is the launch's time;
+    // each family counts one launch and the flop its separate launch would have reported.
+    FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
+    fs.share_with(DMK_FAM_ZGEMM_HALF1, f2, f1);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(HNT), 0, ctx->stream, a2, a1); };
+    if (q2.re_only) kp ? go(half12_kernel<true, true>) : go(half12_kernel<true, false>);
+    else kp ? go(half12_kernel<false, true>) : go(half12_kernel<false, false>);
     DMK_CHECK_LAUNCH(ctx);
     return 1;
 }
