@@ -275,7 +275,8 @@ typedef struct dmk_eri dmk_eri;
  * imaginary part of the contraction when bit0 is clear (dmk_eri_imag_norm), bit2 = ROWS-ONLY pipeline: eri_out is ignored
  * (may be NULL), the planes are only taken through dmk_eri_contract_rows, and everything that would contract into an
  * internal ERI (dmk_eri_end_kL without a stack, dmk_eri_contract, a full stack at dmk_eri_begin_kL) returns
- * DMK_ERR_STATE; dmk_eri_finish drops planes still resident (eri_transform.py:486-521, the out-of-core branch).
+ * DMK_ERR_STATE; dmk_eri_finish drops planes still resident (eri_transform.py:486-521, the out-of-core branch);
+ * bit3 = SPLIT STEP 1 (dmk_eri_split_step1): for a caller whose kL can come from the invariant-planes cache.
  * Dimensions are free: an nao off the K tile of the hot kernels (8) makes the pipeline keep a zero-padded COPY of C_ao_emb, taken
  * here (change C afterwards and it is not seen; on the tile C is read in place as before); naux off the contraction's K tile and
  * an odd pair count are padded inside the pipeline's own plane buffers; AO blocks of 4 GiB and more are transformed in ranges of
@@ -455,6 +456,14 @@ int dmk_eri_flops(const dmk_eri *h, double flops_host[2]);
  * their own).  Results are bit-identical either way.  Ut then holds two halves; where that memory is not to be had, or with
  * DMK_ERI_FUSE=0, every group runs its two launches as before and the count stays 0. */
 int dmk_eri_fused_launches(const dmk_eri *h, int64_t *count);
+/* Is the pipeline in the split step-1 mode (dmk_eri_begin flags bit 3)?  In it the time-reversal partner term of plane rows
+ * [192,256) x columns [0,128) is summed over p of W[L][p][a] conj(C_i[p][b]), W[L][p][a] = sum_q Lpq[L][p][q] C_j[q][a] (64 columns
+ * per block), instead of over q of C_j[q][a] Ut[L][q][b] -- for every kL of the transform, so dense and cached runs agree bit for
+ * bit with each other; against a pipeline without the flag those entries differ in the last bits and all others not at all.  A kL
+ * whose invariant region came from the cache then runs step 1 over columns [128,256) only: 3/4 of the step-1 flop with W, against
+ * 5/4 on a dense kL.  Granted only where the cache of the nemb = 256 region may attach (grouped path, time reversal, no imaginary
+ * part tracking), with nao a multiple of 8 and memory for W; otherwise *on = 0 and the transform runs the old order throughout. */
+int dmk_eri_split_step1(const dmk_eri *h, int *on);
 /* Without time reversal (dmk_eri_begin flags bit 0 clear) and with flags bit 1 set, the pipeline also accumulates the
  * IMAGINARY part of every contraction, Re_a^T Im_b - Im_a^T Re_b; this returns its max-abs so far -- the
  * `eri_imag_norm = max_abs(eri.imag)` diagnostic of eri_transform.py:385-394 (compared with ERI_IMAG_TOL by the

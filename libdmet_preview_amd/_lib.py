@@ -108,6 +108,7 @@ PROTOTYPES = {
     "dmk_eri_finish": (c_int, [c_vp]),
     "dmk_eri_flops": (c_int, [c_vp, P(c_dbl)]),
     "dmk_eri_fused_launches": (c_int, [c_vp, P(c_i64)]),
+    "dmk_eri_split_step1": (c_int, [c_vp, P(c_int)]),
     "dmk_eri_imag_norm": (c_int, [c_vp, P(c_dbl)]),
     "dmk_eri_imag_buffer": (c_int, [c_vp, P(c_vp), P(c_i64)]),
     "dmk_df_block_philox": (c_int, [c_vp, C.c_uint64, c_int, c_int, c_int, c_int, c_vp]),

@@ -981,11 +981,22 @@ class EriInvariantCache(object):
             pass
 
 
+def split_step1_wanted(nemb, can_go_warm, inv_cols=None):
+    """Should a caller ask the engine for the split step 1?  Only where a kL could ever come from the invariant-planes
+    cache of the nemb = 256 region: `can_go_warm` -- the caller's own static test that a cache may exist for it (a DF provider with a
+    `df_token`, and whatever else decides whether it would create one) -- and, where the caller knows how many leading columns of
+    C_ao_emb stay the same (`inv_cols`), all 192 columns of the region.  A caller that can never go warm must not pay the 5/4 of
+    step 1 of a dense call in the mode.  Deliberately NOT a function of DMK_ERI_INV: the uncached A/B run of a caller that can go warm
+    sums in the same order as its cached runs.  DMK_ERI_SPLIT1=0 switches the request off."""
+    return bool(int(nemb) == 256 and can_go_warm and (inv_cols is None or int(inv_cols) >= 192)
+                and os.environ.get("DMK_ERI_SPLIT1", "1") != "0")
+
+
 class EriEngine(object):
     """Owns a dmk_eri pipeline: plan -> (begin_kL, push_block*, end_kL)* on one GPU."""
 
     def __init__(self, ctx, kmesh, nao, naux, nemb, spin, C_ao_emb_dev, eri_dev, t_reversal_symm=True, gso=False, plan=None,
-                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None, inv_block=True):
+                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None, inv_block=True, split_step1=False):
         """`plan` = (weights, records) of `general_plan` for k lists that are not the np.fft-ordered Gamma-centred mesh
         (then `kmesh` only carries the number of k-points, [nk, 1, 1]); default: the integer-mesh plan of libdmetk.
         `inv_cache`: an EriInvariantCache; the library attaches it only where the invariant region exists (the grouped
@@ -997,6 +1008,9 @@ class EriEngine(object):
         `inv_block`: with an attached cache also arm the invariant block of the result for the stacked contraction
         (dmk_eri_attach_cache_block) over `inv_cols` columns, or the compared columns of the region when no hint is given;
         `self.inv_block_tiles` tells its size in tiles of 128 pair indices (0: not armed).
+        `split_step1`: ask for the split step-1 mode (dmk_eri_begin flag 8): the partner term of plane rows
+        [192,256) x columns [0,128) from W, step 1 of a warm kL over columns [128,256) only; for callers whose kL can come from
+        the cache (a dense kL pays 5/4 of step 1).  `self.split_step1` tells whether the library granted it.
         `rows_only`: a pipeline WITHOUT an ERI of its own (`eri_dev` may be None): its planes are only ever taken slab-wise
         with `contract_rows_into`; every path that would contract into an internal ERI refuses instead (dmk_eri_begin flag 4).
         `track_imag`: without time reversal also accumulate the imaginary part of the contraction for the reference's
@@ -1011,9 +1025,13 @@ class EriEngine(object):
         h = C.c_void_p()
         self.track_imag = bool(track_imag) and not self.tr
         ctx.check(lib.dmk_eri_begin(ctx.h, mesh3(self.kmesh), self.nao, self.naux, self.nemb, self.spin,
-                                    (1 if self.tr else 0) | (2 if self.track_imag else 0) | (4 if rows_only else 0),
+                                    (1 if self.tr else 0) | (2 if self.track_imag else 0) | (4 if rows_only else 0) |
+                                    (8 if (split_step1 and not self.gso) else 0),
                                     C_ao_emb_dev.ptr, None if eri_dev is None else eri_dev.ptr, C.byref(h)))
         self.h = h
+        on = C.c_int(0)
+        ctx.check(lib.dmk_eri_split_step1(self.h, C.byref(on)))
+        self.split_step1 = bool(on.value)
         self.weights, self.records = eri_plan(self.kmesh, self.tr) if plan is None else plan
         self.nslots = 1
         self.block_buf = ctx.empty((self.naux, self.nao, self.nao), np.complex128)
@@ -1540,18 +1558,20 @@ def _emb_eri_fast_gdf(cell, mydf, C_ao_lo, basis, kscaled_center, symmetry, C_ao
 
     eri_dev = ctx.zeros((spin_pair, npair, npair), np.float64)
     inv, inv_cols = None, None
-    if (INVARIANT_PLANES and t_reversal_symm and any(r is mydf for _, r in _resident_cache.values())
-            and os.environ.get("DMK_ERI_INV", "1") != "0"):
+    # could a cache ever serve this caller?  (the static part of the decision: everything but the DMK_ERI_INV switch)
+    can_cache = bool(INVARIANT_PLANES and t_reversal_symm and any(r is mydf for _, r in _resident_cache.values()))
+    if can_cache:
         if basis is not None and C_ao_eo is None and not unit_eri:
             inv_cols = leading_identity_columns(basis)
             if inv_cols < 16:
                 inv_cols = None
-        if nemb == 256 or inv_cols is not None:
+        if (nemb == 256 or inv_cols is not None) and os.environ.get("DMK_ERI_INV", "1") != "0":
             if getattr(mydf, "inv_cache", None) is None:
                 mydf.inv_cache = EriInvariantCache(ctx)
             inv = mydf.inv_cache
+    split1 = split_step1_wanted(nemb, can_cache and getattr(mydf, "df_token", None) is not None, inv_cols)
     eng = EriEngine(ctx, kmesh, nao, naux, nemb, spin, C_dev, eri_dev, t_reversal_symm, plan=plan,
-                    track_imag=not t_reversal_symm, inv_cache=inv, inv_cols=inv_cols)
+                    track_imag=not t_reversal_symm, inv_cache=inv, inv_cols=inv_cols, split_step1=split1)
     try:
         kL_list = None
         dist = None

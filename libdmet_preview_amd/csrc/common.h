@@ -332,8 +332,21 @@ struct Half1Launch {
     int nL = 0, nao = 0, nemb = 0, nspin = 1;
     long long ci_spin_stride = 0, ut_spin_stride = 0;   // elements between the spin channels
     int kdim = 0;                        // K loop bound (see above)
+    int first_col_tile = 0;              // the launch transforms the columns from this tile of the step-1 kernel (64 wide) on
 };
-int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q);
+// The W operand of the split partner term (zhot.hip) for the same queued blocks: W[L][p][n] = sum_q Lpq[L][p][q]
+// C_j[q][192 + n] of every slot with sym set, [spin][slot][nL nao][64].  nemb = 256 and nao on the K tile only.
+struct HalfWLaunch {
+    const void *Lpq = nullptr;           // [nslot][nL][nao][nao]
+    const void *C = nullptr;             // [spin][nk][nao][nemb]
+    void *W = nullptr;
+    int nslot = 1; const int *kj = nullptr, *sym = nullptr;     // k_j and partner flag of every slot
+    long long a_slot_stride = 0, w_slot_stride = 0;
+    int nL = 0, nao = 0, nemb = 0, nspin = 1;
+    long long c_spin_stride = 0, w_spin_stride = 0;
+};
+// (w: the W tiles of the same blocks ride behind the step-1 workgroups of the launch; declined as a whole where either side is)
+int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q, const HalfWLaunch *w = nullptr);
 // Step 2 of `nslot` queued blocks in one launch, by the nemb = 256 kernel (zhot.hip) or the table-driven one for a general
 // embedding dimension (zhot_tab.hip).  A launcher refuses (DMK_ERR_INVALID) a field of the other kernel that is not at its default.
 struct Half2Launch {
@@ -353,11 +366,15 @@ struct Half2Launch {
     // planes_sub + (p - 1) * sub_stride ([spin][2 plane_rows][row_len] each), which the caller adds to `planes` afterwards
     int first_row_block = 0, nsub = 1;
     double *planes_sub = nullptr; long long sub_stride = 0;
+    // nemb = 256 kernel only, the split partner term (W set): type 1 computes its partner segment as sum_p W[p][a] conj(C_i[p][b])
+    const void *W = nullptr;             // [spin][slot][nL][nao][64] (HalfWLaunch)
+    const void *C = nullptr; const int *ki = nullptr, *kj = nullptr;    // C_i / C_j of block s: C + k[s] * nao * nemb (+ cj_spin_stride)
+    long long w_slot_stride = 0, w_spin_stride = 0;
 };
 int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q);
 // Step 2 of `q2` and step 1 of `q1` (the NEXT group: it must not write what q2 reads) in one launch.  1: launched, 0: declined and
 // nothing launched (the caller runs q2, then q1), < 0: error.  half12_hot_usable: could a group of this shape be fused at all?
-int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1);
+int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1, const HalfWLaunch *w1 = nullptr);
 int half12_hot_usable(int nL, int nao, int nemb);
 int launch_half2_tab(dmk_ctx *ctx, const Half2Launch &q);
 int half2_hot_usable(int nao, int nemb);

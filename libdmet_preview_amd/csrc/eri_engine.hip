@@ -107,20 +107,29 @@ struct dmk_eri {
     // writes what step 2 of group g reads.  Everything step 2 of a group needs is held by value.
     struct Step2Group {
         Half2Launch q;              // (Cj and sym stay unset here: desc() points them at the arrays below)
-        const void *cj[16]; int sym[16], kj[16];
+        const void *cj[16]; int sym[16], kj[16], ki[16];
         const double2 *ut = nullptr;
         int n = 0, slot = 0;
         bool inv_warm = false, live = false;
-        Half2Launch desc() const { Half2Launch r = q; r.Cj = cj; r.sym = sym; return r; }
+        Half2Launch desc() const { Half2Launch r = q; r.Cj = cj; r.sym = sym; if (r.W) { r.ki = ki; r.kj = kj; } return r; }
     };
     bool fuse = false;            // DMK_ERI_FUSE (default on), the nemb = 256 kernel, one range of L per block, memory for both halves
     int ut_half = 0;              // the half the group being queued is transformed into
     size_t ut_half_elems = 0;
     Step2Group deferred;
     int64_t fused_launches = 0;
+    // SPLIT STEP 1 (dmk_eri_begin flags bit 3): the partner term of the type-1 workgroups of step 2 is computed from
+    // W[L][p][n] = sum_q Lpq[L][p][q] C_j[q][192 + n] and conj(C_i) -- for EVERY kL of the transform, warm or dense, so that the two
+    // stay bit-identical -- and a warm kL runs step 1 over columns [128,256) only.  W sits behind the halves of Ut in the same
+    // workspace, one half per half of Ut, [spin][group][naux nao][64] each.
+    bool split1 = false;
+    double2 *Wbuf = nullptr;
+    size_t w_half_elems = 0;
     dmk_eri(dmk_ctx *c, const int m[3]) : ctx(c), mesh(m) {}
 
     double2 *ut_cur() const { return Ut + (size_t)ut_half * ut_half_elems; }
+    double2 *w_cur() const { return Wbuf + (size_t)ut_half * w_half_elems; }
+    size_t w_slot_elems() const { return (size_t)naux * nao * 64; }                             // W of one queued block and spin
 
     double *slot_planes(int slot, int spin_idx) const {
         return planes + ((size_t)spin_idx * nslots + slot) * 2 * (size_t)pr * pl;
@@ -319,9 +328,21 @@ int dmk_eri_begin(dmk_ctx *ctx, const int mesh[3], int nao, int naux, int nemb, 
         const char *e = getenv("DMK_ERI_FUSE");
         h->fuse = !(e && atoi(e) == 0) && h->hot256 && h->group > 1 && h->hot_rows >= naux && half12_hot_usable(naux, nao, nemb) != 0;
     }
-    size_t ut_bytes = half_bytes * (h->fuse ? 2 : 1);
+    // split step 1 (flags bit 3): where the invariant planes may attach -- the grouped nemb = 256 path with time reversal and no
+    // imaginary-part tracking -- with nao on the K tile, a block in one range of L and step 1 on the tile the W kernel shares;
+    // anything else, or no memory for W (C5: + 2.6 GB per half), runs the old order for the whole transform
+    h->split1 = (flags & 8) && h->hot256 && h->group > 1 && h->tr && !h->imag && nemb == 256 && !kpad && h->hot_rows >= naux &&
+                half12_hot_usable(naux, nao, nemb) != 0 && m.nk <= 0x10000;
+    const size_t w_half_bytes = (size_t)spin * h->group * h->w_slot_elems() * sizeof(double2);
+    size_t ut_bytes = (half_bytes + (h->split1 ? w_half_bytes : 0)) * (h->fuse ? 2 : 1);
     h->planes = reinterpret_cast<double *>(ws_take(ctx, 0, plane_bytes, &h->ws_bytes[0]));
     h->Ut = reinterpret_cast<double2 *>(ws_take(ctx, 1, ut_bytes, &h->ws_bytes[1]));
+    if (h->planes && !h->Ut && h->split1) {        // no room for W: the old order
+        (void)hipGetLastError();
+        h->split1 = false;
+        ut_bytes = half_bytes * (h->fuse ? 2 : 1);
+        h->Ut = reinterpret_cast<double2 *>(ws_take(ctx, 1, ut_bytes, &h->ws_bytes[1]));
+    }
     if (h->planes && !h->Ut && h->fuse) {          // no room for the second half: one half, separate launches
         (void)hipGetLastError();
         h->fuse = false;
@@ -329,6 +350,10 @@ int dmk_eri_begin(dmk_ctx *ctx, const int mesh[3], int nao, int naux, int nemb, 
         h->Ut = reinterpret_cast<double2 *>(ws_take(ctx, 1, ut_bytes, &h->ws_bytes[1]));
     }
     h->ut_half_elems = half_bytes / sizeof(double2);
+    if (h->split1 && h->Ut) {
+        h->Wbuf = h->Ut + (size_t)(h->fuse ? 2 : 1) * h->ut_half_elems;
+        h->w_half_elems = w_half_bytes / sizeof(double2);
+    }
     if (!h->planes || !h->Ut) {
         eri_release(h, false);
         return dmk_fail(ctx, DMK_ERR_NOMEM, "eri_begin: workspace allocation failed (%zu + %zu bytes)", plane_bytes, ut_bytes);
@@ -378,6 +403,12 @@ int dmk_eri_flops(const dmk_eri *h, double f[2]) {
     if (!h || !f) return DMK_ERR_INVALID;
     f[0] = h->flops_half;
     f[1] = h->flops_contract;
+    return DMK_OK;
+}
+
+int dmk_eri_split_step1(const dmk_eri *h, int *on) {
+    if (!h || !on) return DMK_ERR_INVALID;
+    *on = h->split1 ? 1 : 0;
     return DMK_OK;
 }
 
@@ -477,7 +508,20 @@ static Half1Launch half1_hot_desc(const dmk_eri *h, const double2 *L, int l0, in
     q.Ut = h->ut_cur() + (size_t)slot * h->slot_elems() + (size_t)l0 * h->nao * h->nemb;
     q.nL = nl; q.nao = h->nao; q.nemb = h->nemb; q.nspin = h->spin; q.kdim = h->kdim;
     q.ci_spin_stride = h->c_spin_stride(); q.ut_spin_stride = (long long)h->group * (long long)h->slot_elems();
+    // split step 1, warm kL: types 1 and 3 of step 2 read columns [128,256) of Ut only (tiles 2 and 3 of four)
+    if (h->split1 && h->inv_warm) q.first_col_tile = 2;
     return q;
+}
+
+// The W launch of `nslot` queued blocks from `L` into queue slot `slot` on (split step 1): k_j and the partner flag of every block
+static HalfWLaunch halfw_hot_desc(const dmk_eri *h, const double2 *L, int slot, int nslot, const int *kj, const int *sym) {
+    HalfWLaunch w;
+    w.Lpq = L; w.C = h->Ch; w.W = h->w_cur() + (size_t)slot * h->w_slot_elems();
+    w.nslot = nslot; w.kj = kj; w.sym = sym;
+    w.a_slot_stride = (long long)h->naux * h->nao * h->nao; w.w_slot_stride = (long long)h->w_slot_elems();
+    w.nL = h->naux; w.nao = h->nao; w.nemb = h->nemb; w.nspin = h->spin;
+    w.c_spin_stride = h->c_spin_stride(); w.w_spin_stride = (long long)h->group * (long long)h->w_slot_elems();
+    return w;
 }
 
 // Step 2 of the queued group as the queue stands now: operands, planes and flags by value
@@ -486,6 +530,7 @@ static void eri_step2_group(const dmk_eri *h, dmk_eri::Step2Group &g) {
     g.n = h->pending; g.slot = h->cur_slot; g.ut = h->ut_cur(); g.inv_warm = h->inv_warm; g.live = false;
     for (int i = 0; i < g.n; ++i) {
         g.kj[i] = h->pend_kj[i];
+        g.ki[i] = h->pend_ki[i];
         g.sym[i] = h->pend_sym[i];
         g.cj[i] = h->Ch + (size_t)h->pend_kj[i] * h->kdim * nemb;
     }
@@ -497,6 +542,10 @@ static void eri_step2_group(const dmk_eri *h, dmk_eri::Step2Group &g) {
     q.ut_spin_stride = (long long)h->group * q.slot_stride; q.cj_spin_stride = h->c_spin_stride();
     q.planes_spin_stride = h->planes_spin_stride(); q.re_only = h->re_only;
     q.skip_invariant = h->hot256 && g.inv_warm;
+    if (h->split1) {
+        q.W = h->w_cur(); q.C = h->Ch;
+        q.w_slot_stride = (long long)h->w_slot_elems(); q.w_spin_stride = (long long)h->group * q.w_slot_stride;
+    }
     g.q = q;
 }
 
@@ -508,6 +557,8 @@ static int eri_step2_launch(dmk_eri *h, const dmk_eri::Step2Group &g) {
     int rc;
     if (h->hot256) {
         rc = launch_half2_hot(ctx, q);
+        if (rc == 0 && h->split1)
+            return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the split step-2 kernel declined a launch (one partner order per transform)");
         if (rc == 0 && g.inv_warm)
             return dmk_fail(ctx, DMK_ERR_STATE, "eri flush: the nemb = 256 step-2 kernel declined a kL whose invariant planes came from the cache");
     } else {
@@ -559,15 +610,18 @@ static int eri_ring_step1(dmk_eri *h, dmk_eri::Step2Group *with = nullptr) {
         Half1Launch q = half1_hot_desc(h, src, l0, nl, 0);
         q.nslot = h->ring_pending; q.ki = h->pend_ki;
         q.a_slot_stride = (long long)naux * nao * nao; q.ut_slot_stride = (long long)h->slot_elems();
+        HalfWLaunch w;
+        if (h->split1) w = halfw_hot_desc(h, src, 0, h->ring_pending, h->pend_kj, h->pend_sym);
+        const HalfWLaunch *wp = h->split1 ? &w : nullptr;
         int rc = 0;
         if (with && with->live) {
             with->live = false;
-            rc = launch_half12_hot(ctx, with->desc(), q);
+            rc = launch_half12_hot(ctx, with->desc(), q, wp);
             if (rc < 0) return rc;
             if (rc == 1) h->fused_launches += 1;
             else if (int r2 = eri_step2_launch(h, *with)) return r2;
         }
-        if (rc == 0) rc = launch_half1_hot(ctx, q);
+        if (rc == 0) rc = launch_half1_hot(ctx, q, wp);
         if (rc < 0) return rc;
         if (rc == 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri ring: hot step-1 kernel unavailable for the queued blocks");
     }
@@ -645,7 +699,12 @@ int dmk_eri_push_block(dmk_eri *h, int ki, int kj, int symmetrise, const void *L
             const int nl = std::min(h->hot_rows, naux - l0);
             Half1Launch q = half1_hot_desc(h, L, l0, nl, slot);
             q.C = h->Ch + (size_t)ki * h->kdim * nemb;
-            rc_hot = launch_half1_hot(ctx, q);
+            const int sym1 = symmetrise ? 1 : 0;
+            HalfWLaunch w;
+            if (h->split1) w = halfw_hot_desc(h, L, slot, 1, &kj, &sym1);
+            rc_hot = launch_half1_hot(ctx, q, h->split1 ? &w : nullptr);
+            if (rc_hot == 0 && h->split1)
+                return dmk_fail(ctx, DMK_ERR_STATE, "eri_push_block: the split step-1 launch was declined (one partner order per transform)");
             if (rc_hot == 0 && l0 > 0) return dmk_fail(ctx, DMK_ERR_STATE, "eri_push_block: hot step-1 kernel declined a later range of L");
         }
         if (rc_hot < 0) return rc_hot;
@@ -656,6 +715,7 @@ int dmk_eri_push_block(dmk_eri *h, int ki, int kj, int symmetrise, const void *L
             if (rc) return rc;
         }
         h->pend_kj[slot] = kj;
+        h->pend_ki[slot] = ki;
         h->pend_sym[slot] = symmetrise ? 1 : 0;
         h->pending += 1;
         if (h->pending == h->group) {
@@ -1247,7 +1307,7 @@ struct dmk_eri_cache {
     // what the entries were built from: the shape, the region (tab_A: 0 = that of the nemb = 256 kernel, else A of the table path)
     // and columns [0, ncols) of C_ao_emb ([spin nk nao][ncols] c128; ncols = INV_COLS or A)
     bool have_cols = false;
-    int shape[7] = {0, 0, 0, 0, 0, 0, 0};       // mesh, nao, naux, nemb, spin
+    int shape[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // mesh, nao, naux, nemb, spin, partner order of type 1 (split step 1)
     int tab_A = 0, ncols = 0;
     double2 *cols = nullptr;
     size_t cols_rows = 0;
@@ -1463,10 +1523,10 @@ int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]) {
 // or a single bit drops every entry.
 static int inv_attach(dmk_eri *h, dmk_eri_cache *cache, int tab_A, int ncols, int *attached) {
     dmk_ctx *ctx = h->ctx;
-    const int shape[7] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin};
+    const int shape[8] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin, h->split1 ? 1 : 0};
     const size_t rows = (size_t)h->spin * h->mesh.nk * h->nao;
     bool same = cache->have_cols && cache->cols_rows == rows && cache->tab_A == tab_A && cache->ncols == ncols;
-    for (int i = 0; i < 7 && same; ++i) same = cache->shape[i] == shape[i];
+    for (int i = 0; i < 8 && same; ++i) same = cache->shape[i] == shape[i];
     if (same) {
         if (int rc = cols_same(h, cache, cache->cols, 0, ncols, &same)) return rc;
     }
@@ -1479,7 +1539,7 @@ static int inv_attach(dmk_eri *h, dmk_eri_cache *cache, int tab_A, int ncols, in
         }
         DMK_HIP(ctx, hipMemcpy2DAsync(cache->cols, (size_t)ncols * sizeof(double2), h->C, (size_t)h->nemb * sizeof(double2),
                                       (size_t)ncols * sizeof(double2), rows, hipMemcpyDeviceToDevice, ctx->stream));
-        for (int i = 0; i < 7; ++i) cache->shape[i] = shape[i];
+        for (int i = 0; i < 8; ++i) cache->shape[i] = shape[i];
         cache->tab_A = tab_A;
         cache->ncols = ncols;
         cache->cols_rows = rows;
@@ -1623,6 +1683,7 @@ static int blk_decide(dmk_eri *h, int kchunk_w2, int kchunk_w1, int *skip, bool 
     uint64_t k = 0xcbf29ce484222325ULL;
     const int64_t head[] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin, h->pr, h->pl, h->blk_ne, S,
                             kchunk_w2, kchunk_w1, h->n_w2, h->n_w1};
+    if (h->split1) k = blk_mix(k, 0x73706c6974ULL);          // the other partner order of type 1: never the same entry
     for (int64_t v : head) k = blk_mix(k, (uint64_t)v);
     for (int w = 2; w >= 1; --w) {
         const dmk_eri::WeightClass wc = h->weight_class(w);

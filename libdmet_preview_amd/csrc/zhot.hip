@@ -111,6 +111,37 @@ __device__ __forceinline__ void half1_body(const H1Args &g, const unsigned bid, 
 }
 
 // =============================================================================================
+// W (K6l): the partner term of step-2 type 1 from the other side
+// =============================================================================================
+// W[L][p][n] = sum_q Lpq[L][p][q] C_j[q][col0 + n], n < 64, of every queued block that carries the partner term: with it the partner
+// segment of the type-1 workgroups is sum_p W[p][a] conj(C_i[p][b]) and no longer reads columns [0,128) of Ut, so a warm call
+// transforms columns [128,256) only in step 1.  Same tile and ring as half1_kernel<true, 128, 2, false>.
+struct HWArgs {
+    const double2 *Lpq;    // A [nslot][nL][nao][nao], read K-contiguous: row (L, p) at (L nao + p) nao
+    const double2 *C;      // B: C_j of slot s at C + bk[s] * c_k_stride (+ spin), [nao][nemb]
+    double2 *W;            // out [spin][slot][nL nao][64]
+    int nL, nao, nemb, col0;
+    int nspin, nslot;
+    unsigned per_slot, nblocks;   // workgroups per block = tiles_m * nspin
+    unsigned symmask;      // bit s: block s carries the partner term (the others are skipped)
+    long long a_slot_stride, w_slot_stride, w_spin_stride, c_spin_stride, c_k_stride;
+    int bk[16];            // k_j of every slot
+};
+
+__device__ __forceinline__ void halfw_body(const HWArgs &g, const unsigned bid, double2 *const lds) {
+#define ZH_BLOCK_ID bid
+#include "zhot_halfw_body.inc"
+#undef ZH_BLOCK_ID
+}
+
+// step 1 of a queued group and, behind its workgroups, the W tiles of the same group
+__global__ __launch_bounds__(HNT, 2) void half1w_kernel(const H1Args g, const HWArgs gw) {
+    __shared__ __attribute__((aligned(16))) double2 lds[H1_D * H1_BK * (H1_BM + H1_BN)];
+    if (blockIdx.x < g.nblocks) half1_body<true, H1_BM, false, 0, false>(g, blockIdx.x, lds);
+    else halfw_body(gw, blockIdx.x - g.nblocks, lds);
+}
+
+// =============================================================================================
 // step 2 (nemb == 256): per L four workgroups
 //   type 0 / 1 : rows [128,192) / [192,256) x cols [0,128) of the off-diagonal square (8 blocks / wave)
 //   type 2 / 3 : diagonal triangle [0,128)^2 / [128,256)^2, block rows (w, 7-w) per wave (9 blocks / wave)
@@ -147,11 +178,34 @@ struct H2Args {
     int skip_invariant;
 };
 
+// K6l, the split instantiations (SPL in zhot_half2_body.inc): type 1 takes the A fragments of its partner segment from the W panel of
+// the block and the B fragments from conj(C_i) columns [0,128) -- the same number of LDS-DMA pieces and MFMAs per K tile.
+struct H2WArgs {
+    const double2 *W;                 // [spin][slot][nL][nao][64], dense: block s of spin sp at ((sp nslot_max + s) nL nao) 64
+    const double2 *C;                 // [spin][nk][nao][256]: C_i / C_j of block s at C + k(s) * nao * 256 (+ the spin stride of Cj)
+    // k_i and k_j of the blocks, 16 bits each: the split kernels address BOTH operands through them and never read H2Args::Cj -- a
+    // second pointer per block on top of Cj[16] does not fit the scalar registers of the fused kernel
+    unsigned ki2[H2_MAXSLOT / 2], kj2[H2_MAXSLOT / 2];
+    long long w_spin_stride;
+};
+
 // LAB: ablation bits of tools/zhot_lab.hip, as in half1_kernel (1: no plane atomics, 2: no LDS-DMA after the prologue, 4: no
 // s_barrier); the product instantiates LAB = 0.
 template <int LAB = 0, bool RE = false>
 __global__ __launch_bounds__(HNT, 2) void half2_kernel(const H2Args g) {
     __shared__ __attribute__((aligned(16))) double2 lds[H2_LDS];
+    constexpr bool SPL = false;
+    const H2WArgs gw{};
+#define ZH_BLOCK_ID blockIdx.x
+#include "zhot_half2_body.inc"
+#undef ZH_BLOCK_ID
+}
+
+template <bool RE>
+__global__ __launch_bounds__(HNT, 2) void half2w_kernel(const H2Args g, const H2WArgs gw) {
+    __shared__ __attribute__((aligned(16))) double2 lds[H2_LDS];
+    constexpr int LAB = 0;
+    constexpr bool SPL = true;
 #define ZH_BLOCK_ID blockIdx.x
 #include "zhot_half2_body.inc"
 #undef ZH_BLOCK_ID
@@ -160,6 +214,16 @@ __global__ __launch_bounds__(HNT, 2) void half2_kernel(const H2Args g) {
 // (as half1_body: the device function of the same text, for half12_kernel)
 template <int LAB, bool RE>
 __device__ __forceinline__ void half2_body(const H2Args &g, const unsigned bid, double2 *const lds) {
+    constexpr bool SPL = false;
+    const H2WArgs gw{};
+#define ZH_BLOCK_ID bid
+#include "zhot_half2_body.inc"
+#undef ZH_BLOCK_ID
+}
+template <bool RE>
+__device__ __forceinline__ void half2w_body(const H2Args &g, const H2WArgs &gw, const unsigned bid, double2 *const lds) {
+    constexpr int LAB = 0;
+    constexpr bool SPL = true;
 #define ZH_BLOCK_ID bid
 #include "zhot_half2_body.inc"
 #undef ZH_BLOCK_ID
@@ -181,6 +245,15 @@ __global__ __launch_bounds__(HNT, 2) void half12_kernel(const H2Args g2, const H
     __shared__ __attribute__((aligned(16))) double2 lds[H12_LDS];
     if (blockIdx.x < g2.nblocks) half2_body<0, RE>(g2, blockIdx.x, lds);
     else half1_body<true, H1_BM, false, 0, KPAD>(g1, blockIdx.x - g2.nblocks, lds);
+}
+
+// The split form (K6l): [step 2 with the W partner | Ut tiles of the next group | W tiles of the next group]
+template <bool RE>
+__global__ __launch_bounds__(HNT, 2) void half12w_kernel(const H2Args g2, const H2WArgs gw2, const H1Args g1, const HWArgs gw1) {
+    __shared__ __attribute__((aligned(16))) double2 lds[H12_LDS];
+    if (blockIdx.x < g2.nblocks) half2w_body<RE>(g2, gw2, blockIdx.x, lds);
+    else if (blockIdx.x - g2.nblocks < g1.nblocks) half1_body<true, H1_BM, false, 0, false>(g1, blockIdx.x - g2.nblocks, lds);
+    else halfw_body(gw1, blockIdx.x - g2.nblocks - g1.nblocks, lds);
 }
 
 bool hot_enabled() {
@@ -232,13 +305,17 @@ bool half1_hot_plan(const Half1Launch &q, H1Args &a, int &bm, int &bn, double &f
     if (!half1_hot_usable(nL, nao, N)) return false;
     if ((reinterpret_cast<uintptr_t>(q.Lpq) | reinterpret_cast<uintptr_t>(q.C) | reinterpret_cast<uintptr_t>(q.Ut)) & 15) return false;
     half1_hot_tile(N, bm, bn);
+    // a launch from column tile first_col_tile on: the operand and the output are entered at that column and the tile count shrinks;
+    // the kernel keeps the row pitch N and sees tiles 0 .. of a narrower matrix (its column guards compare against N: never taken)
+    const int c0 = q.first_col_tile * bn;
+    if (q.first_col_tile < 0 || (q.first_col_tile > 0 && (N % bn != 0 || c0 >= N))) return false;
     a.Lpq = reinterpret_cast<const double2 *>(q.Lpq);
-    a.Ci = reinterpret_cast<const double2 *>(q.C);
-    a.Ut = reinterpret_cast<double2 *>(q.Ut);
+    a.Ci = reinterpret_cast<const double2 *>(q.C) + c0;
+    a.Ut = reinterpret_cast<double2 *>(q.Ut) + c0;
     a.nL = nL; a.nao = nao; a.nemb = N; a.mrows = nao; a.kdim = kdim;
     a.nblk = (nao + 15) / 16;
     a.tiles_m = (int)(((long long)nL * nao + bm - 1) / bm);          // flat rows: no padding between the nL batches
-    a.tiles_n = (N + bn - 1) / bn;
+    a.tiles_n = (N - c0 + bn - 1) / bn;
     a.nspin = q.nspin; a.b_spin_stride = q.ci_spin_stride; a.out_spin_stride = q.ut_spin_stride;
     a.nslot = nslot; a.a_slot_stride = q.a_slot_stride; a.out_slot_stride = q.ut_slot_stride;
     a.b_k_stride = q.ki ? (long long)kdim * N : 0;
@@ -247,6 +324,49 @@ bool half1_hot_plan(const Half1Launch &q, H1Args &a, int &bm, int &bn, double &f
     if ((unsigned long long)a.per_slot * (unsigned)nslot > 0x7fffffffull) return false;
     a.nblocks = a.per_slot * (unsigned)nslot;
     flops = 6.0 * (double)a.nblocks * bm * bn * (double)kdim;
+    return true;
+}
+
+// The W launch that goes with a step-1 launch on the 128 x 64 tile, or false where it is declined (an AO dimension off the K tile,
+// an operand off 16 bytes, a shape step 1 would decline).
+bool halfw_hot_plan(const HalfWLaunch &q, HWArgs &a, double &flops) {
+    if (q.nspin < 1 || q.nspin > 2 || q.nslot < 1 || q.nslot > 16 || (q.nao % H1_BK) != 0 || q.nemb != H2_N || !q.kj || !q.sym) return false;
+    if (!half1_hot_usable(q.nL, q.nao, q.nemb)) return false;
+    if ((reinterpret_cast<uintptr_t>(q.Lpq) | reinterpret_cast<uintptr_t>(q.C) | reinterpret_cast<uintptr_t>(q.W)) & 15) return false;
+    a.Lpq = reinterpret_cast<const double2 *>(q.Lpq);
+    a.C = reinterpret_cast<const double2 *>(q.C);
+    a.W = reinterpret_cast<double2 *>(q.W);
+    a.nL = q.nL; a.nao = q.nao; a.nemb = q.nemb; a.col0 = H2_N - H1_BN;
+    a.nspin = q.nspin; a.nslot = q.nslot;
+    const long long tiles_m = ((long long)q.nL * q.nao + H1_BM - 1) / H1_BM;
+    if (tiles_m * q.nspin * q.nslot > 0x7fffffffLL) return false;
+    a.per_slot = (unsigned)(tiles_m * q.nspin);
+    a.nblocks = a.per_slot * (unsigned)q.nslot;
+    a.symmask = 0;
+    for (int i = 0; i < 16; ++i) {
+        a.bk[i] = i < q.nslot ? q.kj[i] : 0;
+        if (i < q.nslot && q.sym[i]) a.symmask |= 1u << i;
+    }
+    a.a_slot_stride = q.a_slot_stride; a.w_slot_stride = q.w_slot_stride; a.w_spin_stride = q.w_spin_stride;
+    a.c_spin_stride = q.c_spin_stride; a.c_k_stride = (long long)q.nao * q.nemb;
+    flops = 6.0 * (double)a.per_slot * __builtin_popcount(a.symmask) * H1_BM * H1_BN * (double)q.nao;
+    return true;
+}
+
+// The split part of a step-2 launch (q.W set): false where the split kernels decline it.
+bool half2w_hot_plan(const Half2Launch &q, const H2Args &a, H2WArgs &w) {
+    if (!q.C || !q.ki || a.kdim != a.nao || ((reinterpret_cast<uintptr_t>(q.W) | reinterpret_cast<uintptr_t>(q.C)) & 15)) return false;
+    w.W = reinterpret_cast<const double2 *>(q.W);
+    w.C = reinterpret_cast<const double2 *>(q.C);
+    if (q.w_slot_stride != (long long)q.nL * q.nao * 64) return false;      // the body steps from block to block by this
+    for (int i = 0; i < H2_MAXSLOT / 2; ++i) w.ki2[i] = w.kj2[i] = 0;
+    for (int i = 0; i < q.nslot; ++i) {
+        if (q.ki[i] < 0 || q.ki[i] > 0xffff || q.kj[i] < 0 || q.kj[i] > 0xffff) return false;
+        if (a.Cj[i] != w.C + (long long)q.kj[i] * q.nao * H2_N) return false;      // the same operand as the pointer form
+        w.ki2[i >> 1] |= (unsigned)q.ki[i] << (16 * (i & 1));
+        w.kj2[i >> 1] |= (unsigned)q.kj[i] << (16 * (i & 1));
+    }
+    w.w_spin_stride = q.w_spin_stride;
     return true;
 }
 
@@ -272,14 +392,24 @@ int half2_hot_plan(dmk_ctx *ctx, const Half2Launch &q, H2Args &a, double &flops)
 }  // namespace
 
 // Returns 1 if the hot path handled the launch, 0 if the caller must use the generic kernel, < 0 on error.
-int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q) {
+int launch_half1_hot(dmk_ctx *ctx, const Half1Launch &q, const HalfWLaunch *w) {
     H1Args a;
     int bm, bn;
     double flops;
     if (!half1_hot_plan(q, a, bm, bn, flops)) return 0;
+    const bool kp = a.kdim != a.nao;
+    if (w) {                              // with the W tiles of the same blocks behind the step-1 workgroups
+        HWArgs aw;
+        double fw;
+        if (kp || bm != H1_BM || bn != H1_BN || !halfw_hot_plan(*w, aw, fw) || (unsigned long long)a.nblocks + aw.nblocks > 0x7fffffffull) return 0;
+        FamScope fs(ctx, DMK_FAM_ZGEMM_HALF1);
+        fs.mfma_flops(flops + fw);
+        hipLaunchKernelGGL(half1w_kernel, dim3(a.nblocks + aw.nblocks), dim3(HNT), 0, ctx->stream, a, aw);
+        DMK_CHECK_LAUNCH(ctx);
+        return 1;
+    }
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF1);
     fs.mfma_flops(flops);
-    const bool kp = a.kdim != a.nao;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a); };
     if (bm == 128 && bn == 48) kp ? go(half1_kernel<true, 128, 2, true, 0, true>) : go(half1_kernel<true, 128, 2, true>);
     else if (bm == 128) kp ? go(half1_kernel<true, 128, 2, false, 0, true>) : go(half1_kernel<true, 128, 2, false>);
@@ -293,6 +423,16 @@ int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q) {
     double flops;
     const int rc = half2_hot_plan(ctx, q, a, flops);
     if (rc != 1) return rc;
+    if (q.W) {
+        H2WArgs w;
+        if (!half2w_hot_plan(q, a, w)) return 0;
+        FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
+        fs.mfma_flops(flops);
+        if (q.re_only) hipLaunchKernelGGL(half2w_kernel<true>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
+        else hipLaunchKernelGGL(half2w_kernel<false>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
+        DMK_CHECK_LAUNCH(ctx);
+        return 1;
+    }
     FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
     fs.mfma_flops(flops);
     if (q.re_only) hipLaunchKernelGGL((half2_kernel<0, true>), dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a);
@@ -312,7 +452,7 @@ int half12_hot_usable(int nL, int nao, int nemb) {
 
 // Step 2 of one queued group and step 1 of the next one in ONE launch (half12_kernel).  1: launched; 0: declined -- one of the two
 // separate launchers would decline, or step 1 would not run the 128 x 64 tile -- and nothing was launched; < 0: error.
-int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1) {
+int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1, const HalfWLaunch *w1) {
     H2Args a2;
     H1Args a1;
     int bm, bn;
@@ -321,6 +461,21 @@ int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1
     if (rc != 1) return rc;
     if (!half1_hot_plan(q1, a1, bm, bn, f1) || bm != H1_BM || bn != H1_BN) return 0;
     const bool kp = a1.kdim != a1.nao;
+    if ((q2.W != nullptr) != (w1 != nullptr)) return 0;          // one order for the whole transform
+    if (w1) {
+        H2WArgs w2;
+        HWArgs aw;
+        double fw;
+        if (kp || !half2w_hot_plan(q2, a2, w2) || !halfw_hot_plan(*w1, aw, fw)) return 0;
+        const unsigned long long nbw = (unsigned long long)a2.nblocks + a1.nblocks + aw.nblocks;
+        if (nbw > 0x7fffffffull) return 0;
+        FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
+        fs.share_with(DMK_FAM_ZGEMM_HALF1, f2, f1 + fw);
+        if (q2.re_only) hipLaunchKernelGGL(half12w_kernel<true>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
+        else hipLaunchKernelGGL(half12w_kernel<false>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
+        DMK_CHECK_LAUNCH(ctx);
+        return 1;
+    }
     const unsigned long long nb = (unsigned long long)a2.nblocks + a1.nblocks;
     if (nb > 0x7fffffffull) return 0;
     // One event interval for both families: it is split between them in proportion to the flop each side

@@ -81,6 +81,12 @@ template <bool RE> __device__ __forceinline__ void pack_acc_t(double *planes, lo
      : (SLOT) == 8 ? (G).Cj[8] : (SLOT) == 9 ? (G).Cj[9] : (SLOT) == 10 ? (G).Cj[10] : (SLOT) == 11 ? (G).Cj[11] \
      : (SLOT) == 12 ? (G).Cj[12] : (SLOT) == 13 ? (G).Cj[13] : (SLOT) == 14 ? (G).Cj[14] : (G).Cj[15])
 
+// k_i of block SLOT from the packed halves of H2WArgs::ki2 (compile-time indices only, as above)
+#define H2_PICK_K2(A, SLOT)                                                                        \
+    ((((SLOT) >> 1) == 0 ? A[0] : ((SLOT) >> 1) == 1 ? A[1] : ((SLOT) >> 1) == 2 ? A[2] : ((SLOT) >> 1) == 3 ? A[3] \
+      : ((SLOT) >> 1) == 4 ? A[4] : ((SLOT) >> 1) == 5 ? A[5] : ((SLOT) >> 1) == 6 ? A[6] : A[7])             \
+         >> (16 * ((SLOT) & 1)) & 0xffffu)
+
 // Host side, what the kernel arguments of both step-2 kernels (H2Args, H2TArgs) share: the queue of a Half2Launch -- operands,
 // partner-term mask, strides, sizes and the K loop bound on a K tile of `bk` rows.  False where the launcher declines: a queue
 // length, spin count or K bound the kernels do not cover, or an operand off the 16 bytes of an LDS-DMA piece.

@@ -1,6 +1,7 @@
 // Body of the nemb = 256 step-2 kernel (zhot.hip), included as text where a kernel runs it: half2_kernel and half2_body, the device
 // function behind half12_kernel.  In scope at the include: the template parameters LAB, RE; `g` (H2Args); `lds`, H2_LDS complex in
-// LDS; ZH_BLOCK_ID, the workgroup's block id within the step-2 grid (before the XCD remap over g.nblocks).
+// LDS; ZH_BLOCK_ID, the workgroup's block id within the step-2 grid (before the XCD remap over g.nblocks); SPL and `gw` (H2WArgs):
+// the split partner term of type 1 (DESIGN.md K6l) -- with SPL false every `if constexpr (SPL)` folds away and `gw` is never read.
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar LDS-DMA addressing
     const int frag_k = lane >> 4, frag_x = lane & 15;
     const unsigned lid = xcd_remap(ZH_BLOCK_ID, g.nblocks);
@@ -18,6 +19,8 @@
     const long long g_naux = g.naux, g_npair = g.npair, g_slot_stride = g.slot_stride;
     const unsigned g_symmask = g.symmask;
     const bool fold = g.fold_diag != 0;
+    // C_j of queued block SLOT: the pointer of the launch, or (SPL) through the packed k_j
+#define ZH_CJ(SLOT) (SPL ? gw.C + cj_off + (long long)H2_PICK_K2(gw.kj2, SLOT) * (g.nao * nemb) : H2_PICK_CJ(g, SLOT) + cj_off)
 
     if (type >= 2) {
         // ---------------- diagonal triangle [d0, d0+128)^2 ----------------------------------------
@@ -31,7 +34,7 @@
         }
         // running issue state (wave-uniform, SGPRs): no division and no kernel-argument load per K-tile
         int is_t = 0, is_slot = 0, is_stage = 0;
-        const double2 *is_ub = Ubase, *is_cb = H2_PICK_CJ(g, 0) + cj_off;
+        const double2 *is_ub = Ubase, *is_cb = ZH_CJ(0);
         // (spreading the four pieces of a tile over the MFMA stream of a K step, instead of a burst after the barrier,
         // measured 2.5 % slower: the inline-asm DMA statements pin the compiler's MFMA / ds_read schedule)
         auto issue_advance = [&]() {
@@ -40,7 +43,7 @@
                 is_t = 0;
                 ++is_slot;
                 is_ub = Ubase + (long long)is_slot * g_slot_stride;
-                is_cb = H2_PICK_CJ(g, is_slot) + cj_off;
+                is_cb = ZH_CJ(is_slot);
             } else {
                 is_ub += H2_BK * nemb;
                 is_cb += H2_BK * nemb;
@@ -151,6 +154,14 @@
     // ---------------- off-diagonal half square: rows [r0, r0+64) x cols [0,128) -------------------------
     const int r0 = 128 + 64 * type;
     const int wm = wave >> 1, wn = wave & 1;            // wave tile 32 x 64
+    // SPL, type 1: the partner segment is S[a][b] += sum_p W[p][a] conj(C_i[p][b]) -- the Ca pieces are rows of the W panel (64
+    // columns), the Ub pieces rows of C_i (columns [0,128), conjugated at the fragment read); type 0 keeps Ca / Ub.
+    // The pieces of a block WITHOUT the partner term are streamed all the same (the ring does not branch per block): its W panel was
+    // never written (halfw_body skips it) and holds whatever the buffer held -- deliberate, the loads stay inside the allocation and
+    // c_sym gates every MFMA that would read them.  Likewise columns [0,128) of Ut are stale on a warm kL: only type 0 reads them.
+    bool wpart = false;
+    if constexpr (SPL) wpart = type == 1;
+    const double csign = wpart ? -1.0 : 1.0;
     // stage = 24 pieces of 64 complex: 0-3 Ua rows, 4-11 Cb (row*2+half), 12-15 Ca rows, 16-23 Ub (row*2+half)
     unsigned voff[6];
 #pragma unroll
@@ -162,25 +173,46 @@
         else if (piece < 16) { row = piece - 12; col = r0; }
         else { row = (piece - 16) >> 1; col = ((piece - 16) & 1) * 64; }
         voff[h] = (unsigned)((row * (int)nemb + col + lane) * 16);
+        if constexpr (SPL) { if (wpart && piece >= 12 && piece < 16) voff[h] = (unsigned)((row * 64 + lane) * 16); }
     }
     int is_t = 0, is_slot = 0, is_stage = 0;
-    const double2 *is_ub = Ubase, *is_cb = H2_PICK_CJ(g, 0) + cj_off;
+    const double2 *is_ub = Ubase, *is_cb = ZH_CJ(0);
+    const double2 *is_wb = nullptr, *is_ci = nullptr;
+    if constexpr (SPL) {
+        is_wb = gw.W + (long long)sp * gw.w_spin_stride + (long long)L * g.nao * 64;
+        is_ci = gw.C + cj_off + (long long)H2_PICK_K2(gw.ki2, 0) * (g.nao * nemb);
+    }
     auto issue = [&]() {
         double2 *st = lds + is_stage * H2S_STAGE;
         // pieces wave + 4 h: h = 0 Ua, 1-2 Cb, 3 Ca, 4-5 Ub -- which operand a piece belongs to does not depend on the wave, so the
         // bases are the two scalar tile pointers and the per-lane part is a loop-invariant byte offset (common.h glds16s_x6)
+        if constexpr (SPL) {
+            const double2 *const s3 = wpart ? is_wb : is_cb, *const s45 = wpart ? is_ci : is_ub;       // wave-uniform
+            glds16s_x6(voff[0], voff[1], voff[2], voff[3], voff[4], voff[5], is_ub, is_cb, is_cb, s3, s45, s45, lds_addr_of(st + wave * 64),
+                       lds_addr_of(st + (wave + 4) * 64), lds_addr_of(st + (wave + 8) * 64), lds_addr_of(st + (wave + 12) * 64),
+                       lds_addr_of(st + (wave + 16) * 64), lds_addr_of(st + (wave + 20) * 64));
+        } else {
         glds16s_x6(voff[0], voff[1], voff[2], voff[3], voff[4], voff[5], is_ub, is_cb, is_cb, is_cb, is_ub, is_ub, lds_addr_of(st + wave * 64),
                    lds_addr_of(st + (wave + 4) * 64), lds_addr_of(st + (wave + 8) * 64), lds_addr_of(st + (wave + 12) * 64),
                    lds_addr_of(st + (wave + 16) * 64), lds_addr_of(st + (wave + 20) * 64));
+        }
         is_stage = is_stage + 1 == H2S_D ? 0 : is_stage + 1;
         if (++is_t == Tb) {
             is_t = 0;
             ++is_slot;
             is_ub = Ubase + (long long)is_slot * g_slot_stride;
-            is_cb = H2_PICK_CJ(g, is_slot) + cj_off;
+            is_cb = ZH_CJ(is_slot);
+            if constexpr (SPL) {
+                is_wb += H2_BK * 64 + (long long)(g.nL - 1) * g.nao * 64;       // the same L of the next block (dense layout)
+                is_ci = gw.C + cj_off + (long long)H2_PICK_K2(gw.ki2, is_slot) * (g.nao * nemb);
+            }
         } else {
             is_ub += H2_BK * nemb;
             is_cb += H2_BK * nemb;
+            if constexpr (SPL) {
+                is_wb += H2_BK * 64;
+                is_ci += H2_BK * nemb;
+            }
         }
     };
     cacc acc[2][4];
@@ -219,7 +251,15 @@
 #pragma unroll
             for (int i = 0; i < 2; ++i) a[i] = cfrag_of_t<RE>(lds_frag(&Ca[i * 16]));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = cfrag_of_t<RE>(lds_frag(&Ub[j * 16]));
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (SPL) {
+                    double2 v = lds_frag(&Ub[j * 16]);
+                    v.y *= csign;                       // conj(C_i) on the W path; type 0 multiplies by one
+                    b[j] = cfrag_of_t<RE>(v);
+                } else {
+                    b[j] = cfrag_of_t<RE>(lds_frag(&Ub[j * 16]));
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -241,3 +281,4 @@
             for (int j = 0; j < 4; ++j)
                 pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row, wn * 64 + j * 16 + frag_x, acc[i][j], r);
         }
+#undef ZH_CJ

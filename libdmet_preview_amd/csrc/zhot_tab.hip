@@ -442,6 +442,7 @@ extern "C" int dmk_half2_tab_table(int nemb, int occ, int first_row_block, int *
 // the generic kernel, < 0 on error.
 int launch_half2_tab(dmk_ctx *ctx, const Half2Launch &q) {
     if (q.skip_invariant) return dmk_fail(ctx, DMK_ERR_INVALID, "half2_tab: skip_invariant belongs to the nemb = 256 kernel");
+    if (q.W) return dmk_fail(ctx, DMK_ERR_INVALID, "half2_tab: the split partner term (W) belongs to the nemb = 256 kernel");
     const int nemb = q.nemb, nL = q.nL, nslot = q.nslot, nspin = q.nspin;
     if (!half2_tab_usable(q.nao, nemb)) return 0;
     // occupancy point (see Cfg2 / Cfg3).  Measured (MI355X, executed TF of this kernel): the evenly dealt WIDE items of small
