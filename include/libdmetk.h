@@ -474,6 +474,62 @@ int dmk_eri_imag_norm(dmk_eri *h, double *maxabs_host);
  * in the sum, as in the reference where max_abs(eri.imag) is taken after mpi.reduce (eri_transform_mpi.py:203-215). */
 int dmk_eri_imag_buffer(dmk_eri *h, double **imag_out, int64_t *elems_out);
 
+/* ------------------------------------------------------------------------- */
+/* a16 : density-fitted k-point J/K build                                      */
+/* replaces routine/pbc_helper.py:314-359 (get_jk_from_eri_7d) on a DF tensor, */
+/* i.e. what kmf.get_jk(dm_kpts=...) computes under Lattice.set_Ham /          */
+/* update_Ham (system/lattice.py:416-592)                                      */
+/* ------------------------------------------------------------------------- */
+
+/* With B^(i,j) the (naux, nao, nao) c128 block of the ordered pair (ki, kj) and dm (spin, nk, nao, nao) c128:
+ *   rho[s][L]     = sum_k sum_pq B^(k,k)[L,p,q] dm[s,k][q,p]
+ *   vj[s,k][r,t]  = (1/nk) sum_L rho[s][L] B^(k,k)[L,r,t]
+ *   vk[s,ki][p,t] = (1/nk) sum_kj sum_L sum_qr B^(ki,kj)[L,p,q] dm[s,kj][q,r] conj(B^(ki,kj)[L,t,r])
+ * The caller streams the blocks through the handle, one at a time (no nk blocks are ever held):
+ *   exchange        every ordered pair (ki, kj): all nk blocks of a row ki, in any order (the order of the pushes of a row is
+ *                   the summation order over kj); rows that get no block stay zero (a ki shard), a row with some but not all
+ *                   of its blocks makes dmk_dfjk_finish fail;
+ *   Coulomb pass 1  every diagonal block (k, k): its contribution to rho;
+ *   Coulomb pass 2  every diagonal block again, after ALL of pass 1: vj of that k.
+ * Out-of-order calls return DMK_ERR_STATE, indices outside [0, nk) or an off-diagonal Coulomb block DMK_ERR_INVALID, in both
+ * cases before anything is launched.  The first exchange product runs as one f64-MFMA GEMM per block, the second as a split-K
+ * GEMM over the auxiliary index whose partial tiles are summed in a fixed order: results are bit-reproducible (no atomics).
+ * An AO block of 4 GiB or more is refused at begin (DMK_ERR_INVALID).  spin is 1 or 2; dm, vj_out, vk_out are 16-byte aligned;
+ * dm is read at begin (a transposed copy is kept).  vj_out / vk_out (shape of dm; NULL when not asked for) are zeroed at begin and
+ * complete after dmk_dfjk_finish.  DESIGN.md K16. */
+typedef struct dmk_dfjk dmk_dfjk;
+/* flags of dmk_dfjk_begin; DMK_DFJK_FIRST_ONLY: exchange pushes stop after the first product (vk is not built) -- for timing the two
+ * products apart, tools/dfjk_bench.py */
+enum { DMK_DFJK_WITH_J = 1, DMK_DFJK_WITH_K = 2, DMK_DFJK_FIRST_ONLY = 4 };
+enum { DMK_DFJK_EXCHANGE = 0, DMK_DFJK_COULOMB1 = 1, DMK_DFJK_COULOMB2 = 2 };   /* `what` of a push        */
+int dmk_dfjk_begin(dmk_ctx *ctx, int nk, int nao, int naux, int spin, int flags, const void *dm, void *vj_out, void *vk_out,
+                   dmk_dfjk **out);
+/* Time reversal: the caller promises dm[-k] = conj(dm[k]) and B^(-i,-j) = conj(B^(i,j)).  minus_k / weights as from
+ * dmk_kmesh_tables (weights 1: own partner, 2 / 0: the computed / the filled point of a pair).  Only k / ki of weight > 0 are then
+ * pushed (others: DMK_ERR_INVALID); finish fills the rest by conjugation and drops the imaginary part of the weight-1 points, so
+ * that out[-k] == conj(out[k]) holds bit for bit.  Before the first push. */
+int dmk_dfjk_set_t_reversal(dmk_dfjk *h, const int32_t *minus_k_host, const int32_t *weights_host);
+/* exxdiv = 'ewald' of PySCF's get_jk: finish adds madelung * S[k] dm[s,k] S[k] to vk[s,k]; ovlp: nk x nao x nao c128 (device),
+ * alive until finish.  Computing the Madelung constant stays with the caller. */
+int dmk_dfjk_set_ewald(dmk_dfjk *h, double madelung, const void *ovlp);
+/* One block (device, naux x nao x nao c128, 16-byte aligned) -- a buffer of the caller's, a slot of the ring below, or a block of a
+ * resident DF tensor read in place.  Work is stream ordered: the buffer may be rewritten on the context stream right away. */
+int dmk_dfjk_push_block(dmk_dfjk *h, int ki, int kj, int what, const void *Lpq);
+/* `*nslots_out` device buffers of one block each (slot s at ring + s * naux*nao*nao c128) owned by the handle, for producers that
+ * write blocks on the device (GDFPhilox.load_blocks_on): fill slots on the context stream, push each with dmk_dfjk_push_block. */
+int dmk_dfjk_block_ring(dmk_dfjk *h, void **ring_out, int *nslots_out);
+/* A block in HOST memory: copied to one of two device staging blocks (`slot` 0 | 1) on a copy stream of the handle's and consumed
+ * on the context stream when it has landed, so that the copy of block n + 1 overlaps the products of block n.  The host buffer
+ * may be refilled once dmk_dfjk_host_slot_wait(h, slot) has returned (two pinned buffers from dmk_host_alloc, alternating). */
+int dmk_dfjk_push_block_host(dmk_dfjk *h, int ki, int kj, int what, const void *Lpq_host, int slot);
+int dmk_dfjk_host_slot_wait(dmk_dfjk *h, int slot);
+/* The 1/nk scaling of vk, the Ewald term and the time-reversal fill.  DMK_ERR_STATE (nothing launched) while a Coulomb pass of a
+ * with-J handle or part of an exchange row is missing.  The results are complete in stream order; dmk_dfjk_free releases the handle. */
+int dmk_dfjk_finish(dmk_dfjk *h);
+/* flop ISSUED to the f64 matrix pipe so far by [0] the first and [1] the second exchange product (3M, padded tiles). */
+int dmk_dfjk_flops(const dmk_dfjk *h, double flops_host[2]);
+int dmk_dfjk_free(dmk_dfjk *h);
+
 /* Procedural DF block (synthetic configs): Philox4x32-10,
  * key (seed_lo, seed_hi), counter (e>>1 lo, e>>1 hi, ki, kj), e = (L*nao+p)*nao+q. */
 int dmk_df_block_philox_on(dmk_ctx *ctx, void *stream, uint64_t seed, int ki, int kj, int naux, int nao, void *out);

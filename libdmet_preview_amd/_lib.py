@@ -111,6 +111,16 @@ PROTOTYPES = {
     "dmk_eri_split_step1": (c_int, [c_vp, P(c_int)]),
     "dmk_eri_imag_norm": (c_int, [c_vp, P(c_dbl)]),
     "dmk_eri_imag_buffer": (c_int, [c_vp, P(c_vp), P(c_i64)]),
+    "dmk_dfjk_begin": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, P(c_vp)]),
+    "dmk_dfjk_set_t_reversal": (c_int, [c_vp, c_vp, c_vp]),
+    "dmk_dfjk_set_ewald": (c_int, [c_vp, c_dbl, c_vp]),
+    "dmk_dfjk_push_block": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
+    "dmk_dfjk_block_ring": (c_int, [c_vp, P(c_vp), P(c_int)]),
+    "dmk_dfjk_push_block_host": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int]),
+    "dmk_dfjk_host_slot_wait": (c_int, [c_vp, c_int]),
+    "dmk_dfjk_finish": (c_int, [c_vp]),
+    "dmk_dfjk_flops": (c_int, [c_vp, P(c_dbl)]),
+    "dmk_dfjk_free": (c_int, [c_vp]),
     "dmk_df_block_philox": (c_int, [c_vp, C.c_uint64, c_int, c_int, c_int, c_int, c_vp]),
     "dmk_eri_restore": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
     "dmk_dgemm_tn_acc": (c_int, [c_vp, c_int, c_int, c_dbl, c_vp, c_vp, c_i64, c_vp, c_i64]),
