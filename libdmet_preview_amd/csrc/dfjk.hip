@@ -11,6 +11,7 @@
 // Complex products are 3M on v_mfma_f64_16x16x4_f64, as in the half transform (zhot_common.h).
 // All offsets are 64-bit; a block of 4 GiB or more is refused at begin.  No atomics anywhere: two runs give the same bits.
 #include "common.h"
+#include "devres.h"
 #include <new>
 
 namespace {
@@ -234,30 +235,21 @@ struct dmk_dfjk {
     const double2 *dm = nullptr; double2 *vj = nullptr, *vk = nullptr;
     long long n2 = 0;
     size_t block_bytes = 0;
-    double2 *dmT = nullptr, *W = nullptr, *part = nullptr, *rho_k = nullptr, *rho = nullptr, *ew = nullptr;
-    int *tab_dev = nullptr;                       // [weights | minus_k | row mask | all ones] x nk
+    DevMem dmT, W, part, rho_k, rho, ew;          // c128 workspaces
+    DevMem tab_dev;                               // int [weights | minus_k | row mask | all ones] x nk
     std::vector<int> weights, minus_k, kcount, j1, j2;
     bool rho_ready = false;
     int nchunk = 1;
     double madelung = 0.0; const double2 *ovlp = nullptr; bool ewald = false;
-    void *ring = nullptr; int ring_slots = 0;
-    void *stage[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
-    bool consumed_set[2] = {false, false};
+    DevMem ring; int ring_slots = 0;
+    HostFeed feed;                                // dmk_dfjk_push_block_host
     double flops[2] = {0.0, 0.0};
 };
 
+// the streams are drained, then the handle goes with everything it owns
 static void dfjk_release(dmk_dfjk *h) {
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
-    for (int s = 0; s < 2; ++s) {
-        if (h->copied[s]) (void)hipEventDestroy(h->copied[s]);
-        if (h->consumed[s]) (void)hipEventDestroy(h->consumed[s]);
-        if (h->stage[s]) (void)hipFree(h->stage[s]);
-    }
-    void *bufs[] = {h->dmT, h->W, h->part, h->rho_k, h->rho, h->ew, h->tab_dev, h->ring};
-    for (void *b : bufs) if (b) (void)hipFree(b);
+    h->feed.sync();
     delete h;
 }
 
@@ -282,24 +274,24 @@ static int dfjk_exchange(dmk_dfjk *h, int ki, int kj, const double2 *B) {
     const int n = h->nao, sn = h->spin * n;
     ZntArgs a1{};
     a1.A = B; a1.lda = n; a1.M = (long long)h->naux * n;
-    a1.B = h->dmT + (long long)kj * h->spin * h->n2; a1.ldb = n; a1.N = sn;
+    a1.B = h->dmT.get<double2>() + (long long)kj * h->spin * h->n2; a1.ldb = n; a1.N = sn;
     a1.K = n; a1.nbatch = 1; a1.sA = a1.sB = 0; a1.nchunk = 1;
-    a1.C = h->W; a1.ldc = sn; a1.sC = 0; a1.tiles_n = (sn + TN - 1) / TN;
+    a1.C = h->W.get<double2>(); a1.ldc = sn; a1.sC = 0; a1.tiles_n = (sn + TN - 1) / TN;
     int rc = dfjk_launch_znt(h, false, a1, 0);
     if (rc) return rc;
     if (h->flags & DMK_DFJK_FIRST_ONLY) return DMK_OK;       // measurement: the first product alone
     for (int s = 0; s < h->spin; ++s) {
         ZntArgs a2{};
-        a2.A = h->W + (long long)s * n; a2.lda = sn; a2.M = n;
+        a2.A = h->W.get<double2>() + (long long)s * n; a2.lda = sn; a2.M = n;
         a2.B = B; a2.ldb = n; a2.N = n;
         a2.K = n; a2.nbatch = h->naux; a2.sA = (long long)n * sn; a2.sB = h->n2; a2.nchunk = h->nchunk;
-        a2.C = h->part; a2.ldc = n; a2.sC = h->n2; a2.tiles_n = (n + TN - 1) / TN;
+        a2.C = h->part.get<double2>(); a2.ldc = n; a2.sC = h->n2; a2.tiles_n = (n + TN - 1) / TN;
         rc = dfjk_launch_znt(h, true, a2, 1);
         if (rc) return rc;
         FamScope fs(ctx, DMK_FAM_JK);
         const long long nd = 2 * h->n2;
         hipLaunchKernelGGL(dfjk_reduce_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, ctx->stream, nd, h->nchunk,
-                           (const double *)h->part, (double *)(h->vk + ((long long)s * h->nk + ki) * h->n2));
+                           h->part.get<const double>(), (double *)(h->vk + ((long long)s * h->nk + ki) * h->n2));
         DMK_CHECK_LAUNCH(ctx);
     }
     return DMK_OK;
@@ -311,7 +303,7 @@ static int dfjk_upload_tables(dmk_dfjk *h) {
         t[k] = h->weights[k]; t[h->nk + k] = h->minus_k[k];
         t[2 * h->nk + k] = (h->kcount[k] == h->nk) ? 1 : 0; t[3 * h->nk + k] = 1;
     }
-    DMK_HIP(h->ctx, hipMemcpyAsync(h->tab_dev, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, h->ctx->stream));
+    DMK_HIP(h->ctx, hipMemcpyAsync(h->tab_dev.get<void>(), t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, h->ctx->stream));
     DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));       // `t` is pageable and goes out of scope
     return DMK_OK;
 }
@@ -344,12 +336,12 @@ int dmk_dfjk_begin(dmk_ctx *ctx, int nk, int nao, int naux, int spin, int flags,
     if (nc < 1) nc = 1;
     h->nchunk = (int)nc;
     const size_t mats = (size_t)spin * nk * h->n2 * 16;
-    hipError_t e = dmk_dev_alloc(ctx, (void **)&h->dmT, mats);
-    if (e == hipSuccess) e = dmk_dev_alloc(ctx, (void **)&h->tab_dev, 4 * (size_t)nk * sizeof(int));
-    if (e == hipSuccess && wk) e = dmk_dev_alloc(ctx, (void **)&h->W, h->block_bytes * spin);
-    if (e == hipSuccess && wk) e = dmk_dev_alloc(ctx, (void **)&h->part, (size_t)h->nchunk * h->n2 * 16);
-    if (e == hipSuccess && wj) e = dmk_dev_alloc(ctx, (void **)&h->rho_k, (size_t)nk * spin * naux * 16);
-    if (e == hipSuccess && wj) e = dmk_dev_alloc(ctx, (void **)&h->rho, (size_t)spin * naux * 16);
+    hipError_t e = h->dmT.alloc(ctx, mats);
+    if (e == hipSuccess) e = h->tab_dev.alloc(ctx, 4 * (size_t)nk * sizeof(int));
+    if (e == hipSuccess && wk) e = h->W.alloc(ctx, h->block_bytes * spin);
+    if (e == hipSuccess && wk) e = h->part.alloc(ctx, (size_t)h->nchunk * h->n2 * 16);
+    if (e == hipSuccess && wj) e = h->rho_k.alloc(ctx, (size_t)nk * spin * naux * 16);
+    if (e == hipSuccess && wj) e = h->rho.alloc(ctx, (size_t)spin * naux * 16);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         dfjk_release(h);
@@ -357,12 +349,12 @@ int dmk_dfjk_begin(dmk_ctx *ctx, int nk, int nao, int naux, int spin, int flags,
     }
     {
         FamScope fs(ctx, DMK_FAM_JK);
-        hipLaunchKernelGGL(dfjk_dmT_kernel, dim3(1024), dim3(256), 0, ctx->stream, nk, spin, nao, h->dm, h->dmT);
+        hipLaunchKernelGGL(dfjk_dmT_kernel, dim3(1024), dim3(256), 0, ctx->stream, nk, spin, nao, h->dm, h->dmT.get<double2>());
     }
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && wk) le = hipMemsetAsync(h->vk, 0, mats, ctx->stream);
     if (le == hipSuccess && wj) le = hipMemsetAsync(h->vj, 0, mats, ctx->stream);
-    if (le == hipSuccess && wj) le = hipMemsetAsync(h->rho_k, 0, (size_t)nk * spin * naux * 16, ctx->stream);
+    if (le == hipSuccess && wj) le = hipMemsetAsync(h->rho_k.get<void>(), 0, (size_t)nk * spin * naux * 16, ctx->stream);
     if (le != hipSuccess) {
         dfjk_release(h);
         return dmk_fail(ctx, DMK_ERR_HIP, "dfjk: begin failed: %s", hipGetErrorString(le));
@@ -393,7 +385,7 @@ int dmk_dfjk_set_ewald(dmk_dfjk *h, double madelung, const void *ovlp) {
     if (!h->with_k) return dmk_fail(h->ctx, DMK_ERR_STATE, "dfjk: the Ewald term belongs to K, which this handle does not build");
     if (!ovlp || ((uintptr_t)ovlp & 15)) return dmk_fail(h->ctx, DMK_ERR_INVALID, "dfjk: ovlp null or misaligned");
     if (!h->ew) {
-        hipError_t e = dmk_dev_alloc(h->ctx, (void **)&h->ew, 2 * (size_t)h->spin * h->nk * h->n2 * 16);
+        hipError_t e = h->ew.alloc(h->ctx, 2 * (size_t)h->spin * h->nk * h->n2 * 16);
         if (e != hipSuccess) { (void)hipGetLastError(); return dmk_fail(h->ctx, DMK_ERR_NOMEM, "dfjk: Ewald workspace: %s", hipGetErrorString(e)); }
     }
     h->madelung = madelung; h->ovlp = (const double2 *)ovlp; h->ewald = true;
@@ -428,7 +420,7 @@ int dmk_dfjk_push_block(dmk_dfjk *h, int ki, int kj, int what, const void *Lpq) 
         h->pushed = true;
         FamScope fs(ctx, DMK_FAM_JK);
         hipLaunchKernelGGL(dfjk_rho_kernel, dim3(h->naux, h->spin), dim3(256), 0, ctx->stream, h->nao, h->naux, B,
-                           (const double2 *)(h->dmT + (long long)ki * h->spin * h->n2), h->rho_k + (long long)ki * h->spin * h->naux);
+                           h->dmT.get<const double2>() + (long long)ki * h->spin * h->n2, h->rho_k.get<double2>() + (long long)ki * h->spin * h->naux);
         DMK_CHECK_LAUNCH(ctx);
         h->j1[ki] = 1;
         return DMK_OK;
@@ -442,7 +434,7 @@ int dmk_dfjk_push_block(dmk_dfjk *h, int ki, int kj, int what, const void *Lpq) 
         FamScope fs(ctx, DMK_FAM_JK);
         const int n = h->spin * h->naux;
         hipLaunchKernelGGL(dfjk_rho_sum_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h->nk, n,
-                           h->tr ? (const int *)h->tab_dev : (const int *)nullptr, (const double2 *)h->rho_k, h->rho);
+                           h->tr ? h->tab_dev.get<const int>() : (const int *)nullptr, h->rho_k.get<const double2>(), h->rho.get<double2>());
         DMK_CHECK_LAUNCH(ctx);
         h->rho_ready = true;
     }
@@ -450,8 +442,8 @@ int dmk_dfjk_push_block(dmk_dfjk *h, int ki, int kj, int what, const void *Lpq) 
         FamScope fs(ctx, DMK_FAM_JK);
         const unsigned nb = (unsigned)((h->n2 + 63) / 64);
         double2 *vj = h->vj + (long long)ki * h->n2;
-        if (h->spin == 1) hipLaunchKernelGGL(dfjk_vj_kernel<1>, dim3(nb), dim3(64), 0, ctx->stream, h->nao, h->naux, B, (const double2 *)h->rho, 1.0 / h->nk, vj, (long long)h->nk * h->n2);
-        else hipLaunchKernelGGL(dfjk_vj_kernel<2>, dim3(nb), dim3(64), 0, ctx->stream, h->nao, h->naux, B, (const double2 *)h->rho, 1.0 / h->nk, vj, (long long)h->nk * h->n2);
+        if (h->spin == 1) hipLaunchKernelGGL(dfjk_vj_kernel<1>, dim3(nb), dim3(64), 0, ctx->stream, h->nao, h->naux, B, h->rho.get<const double2>(), 1.0 / h->nk, vj, (long long)h->nk * h->n2);
+        else hipLaunchKernelGGL(dfjk_vj_kernel<2>, dim3(nb), dim3(64), 0, ctx->stream, h->nao, h->naux, B, h->rho.get<const double2>(), 1.0 / h->nk, vj, (long long)h->nk * h->n2);
         DMK_CHECK_LAUNCH(ctx);
     }
     h->j2[ki] = 1;
@@ -463,12 +455,12 @@ int dmk_dfjk_block_ring(dmk_dfjk *h, void **ring_out, int *nslots_out) {
     if (h->finished) return dmk_fail(h->ctx, DMK_ERR_STATE, "dfjk: already finished");
     if (!h->ring) {
         for (int n = 4; n >= 1 && !h->ring; n >>= 1) {
-            if (dmk_dev_alloc(h->ctx, &h->ring, h->block_bytes * n) == hipSuccess) h->ring_slots = n;
-            else { (void)hipGetLastError(); h->ring = nullptr; }
+            if (h->ring.alloc(h->ctx, h->block_bytes * n) == hipSuccess) h->ring_slots = n;
+            else (void)hipGetLastError();
         }
         if (!h->ring) return dmk_fail(h->ctx, DMK_ERR_NOMEM, "dfjk: no memory for a block ring");
     }
-    *ring_out = h->ring; *nslots_out = h->ring_slots;
+    *ring_out = h->ring.get<void>(); *nslots_out = h->ring_slots;
     return DMK_OK;
 }
 
@@ -478,31 +470,16 @@ int dmk_dfjk_push_block_host(dmk_dfjk *h, int ki, int kj, int what, const void *
     if (h->finished) return dmk_fail(ctx, DMK_ERR_STATE, "dfjk: push after finish");
     if (slot < 0 || slot > 1 || !Lpq_host) return dmk_fail(ctx, DMK_ERR_INVALID, "dfjk: bad host slot / buffer");
     if (ki < 0 || ki >= h->nk || kj < 0 || kj >= h->nk) return dmk_fail(ctx, DMK_ERR_INVALID, "dfjk: k index (%d, %d) outside [0, %d)", ki, kj, h->nk);
-    if (!h->copy_stream) {
-        DMK_HIP(ctx, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for (int s = 0; s < 2; ++s) {
-            DMK_HIP(ctx, hipEventCreateWithFlags(&h->copied[s], hipEventDisableTiming));
-            DMK_HIP(ctx, hipEventCreateWithFlags(&h->consumed[s], hipEventDisableTiming));
-        }
-    }
-    if (!h->stage[slot]) {
-        hipError_t e = dmk_dev_alloc(ctx, &h->stage[slot], h->block_bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); h->stage[slot] = nullptr; return dmk_fail(ctx, DMK_ERR_NOMEM, "dfjk: staging block: %s", hipGetErrorString(e)); }
-    }
-    if (h->consumed_set[slot]) DMK_HIP(ctx, hipStreamWaitEvent(h->copy_stream, h->consumed[slot], 0));
-    DMK_HIP(ctx, hipMemcpyAsync(h->stage[slot], Lpq_host, h->block_bytes, hipMemcpyHostToDevice, h->copy_stream));
-    DMK_HIP(ctx, hipEventRecord(h->copied[slot], h->copy_stream));
-    DMK_HIP(ctx, hipStreamWaitEvent(ctx->stream, h->copied[slot], 0));
-    const int rc = dmk_dfjk_push_block(h, ki, kj, what, h->stage[slot]);
-    DMK_HIP(ctx, hipEventRecord(h->consumed[slot], ctx->stream));
-    h->consumed_set[slot] = true;
-    return rc;
+    if (int rc = h->feed.open(ctx)) return rc;
+    void *staged = nullptr;
+    if (int rc = h->feed.stage(slot, Lpq_host, h->block_bytes, &staged)) return rc;
+    if (int rc = dmk_dfjk_push_block(h, ki, kj, what, staged)) return rc;
+    return h->feed.done(slot);
 }
 
 int dmk_dfjk_host_slot_wait(dmk_dfjk *h, int slot) {
     if (!h || slot < 0 || slot > 1) return DMK_ERR_INVALID;
-    if (h->copied[slot] && h->consumed_set[slot]) DMK_HIP(h->ctx, hipEventSynchronize(h->copied[slot]));
-    return DMK_OK;
+    return h->feed.wait_copied(slot);
 }
 
 int dmk_dfjk_finish(dmk_dfjk *h) {
@@ -520,7 +497,7 @@ int dmk_dfjk_finish(dmk_dfjk *h) {
                 return dmk_fail(ctx, DMK_ERR_STATE, "dfjk: row ki = %d has %d of %d exchange blocks", k, h->kcount[k], h->nk);
     int rc = dfjk_upload_tables(h);
     if (rc) return rc;
-    const int *w_dev = h->tab_dev, *mk_dev = h->tab_dev + h->nk, *mask_dev = h->tab_dev + 2 * h->nk, *ones_dev = h->tab_dev + 3 * h->nk;
+    const int *w_dev = h->tab_dev.get<int>(), *mk_dev = w_dev + h->nk, *mask_dev = w_dev + 2 * h->nk, *ones_dev = w_dev + 3 * h->nk;
     const dim3 grid((unsigned)((h->n2 + 255) / 256 > 64 ? 64 : (h->n2 + 255) / 256), h->spin * h->nk);
     if (h->with_k) {
         {
@@ -530,7 +507,7 @@ int dmk_dfjk_finish(dmk_dfjk *h) {
         }
         if (h->ewald) {
             // vk[s,k] += madelung S[k] dm[s,k] S[k]
-            double2 *T1 = h->ew, *T2 = h->ew + (long long)h->spin * h->nk * h->n2;
+            double2 *T1 = h->ew.get<double2>(), *T2 = T1 + (long long)h->spin * h->nk * h->n2;
             for (int s = 0; s < h->spin; ++s) {
                 const long long o = (long long)s * h->nk * h->n2;
                 rc = dmk_zgemm_batched(ctx, 0, 0, h->nao, h->nao, h->nao, h->nk, 1.0, h->ovlp, h->n2, h->dm + o, h->n2, T1 + o, h->n2);
