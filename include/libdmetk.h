@@ -276,7 +276,9 @@ typedef struct dmk_eri dmk_eri;
  * (may be NULL), the planes are only taken through dmk_eri_contract_rows, and everything that would contract into an
  * internal ERI (dmk_eri_end_kL without a stack, dmk_eri_contract, a full stack at dmk_eri_begin_kL) returns
  * DMK_ERR_STATE; dmk_eri_finish drops planes still resident (eri_transform.py:486-521, the out-of-core branch);
- * bit3 = SPLIT STEP 1 (dmk_eri_split_step1): for a caller whose kL can come from the invariant-planes cache.
+ * bit3 = SPLIT STEP 1 (dmk_eri_split_step1): for a caller whose kL can come from the invariant-planes cache;
+ * bit4 = STRIP STEP 1 (dmk_eri_strip_step1): implies bit3 and is granted exactly where bit3 is; a warm kL then runs step 1 over
+ * columns [192,256) only and the cached region is the pairs b <= a < 192.
  * Dimensions are free: an nao off the K tile of the hot kernels (8) makes the pipeline keep a zero-padded COPY of C_ao_emb, taken
  * here (change C afterwards and it is not seen; on the tile C is read in place as before); naux off the contraction's K tile and
  * an odd pair count are padded inside the pipeline's own plane buffers; AO blocks of 4 GiB and more are transformed in ranges of
@@ -464,6 +466,12 @@ int dmk_eri_fused_launches(const dmk_eri *h, int64_t *count);
  * 5/4 on a dense kL.  Granted only where the cache of the nemb = 256 region may attach (grouped path, time reversal, no imaginary
  * part tracking), with nao a multiple of 8 and memory for W; otherwise *on = 0 and the transform runs the old order throughout. */
 int dmk_eri_split_step1(const dmk_eri *h, int *on);
+/* Is the pipeline in the strip step-1 mode (dmk_eri_begin flags bit 4; it implies the split mode and is granted with it)?  In it
+ * plane rows [192,256) x columns [128,256) come from a workgroup of the geometry that owns rows [192,256) x columns [0,128) -- the
+ * partner term from W and conj(C_i) again -- and the triangle [128,192)^2 from one of its own, which joins the cached region: the
+ * pairs b <= a < 192, 18528 doubles per auxiliary row and plane.  A warm kL runs step 1 over columns [192,256) only: 1/2 of the
+ * step-1 flop with W.  Against the split mode alone the strip's entries differ in the last bits and all others not at all. */
+int dmk_eri_strip_step1(const dmk_eri *h, int *on);
 /* Without time reversal (dmk_eri_begin flags bit 0 clear) and with flags bit 1 set, the pipeline also accumulates the
  * IMAGINARY part of every contraction, Re_a^T Im_b - Im_a^T Re_b; this returns its max-abs so far -- the
  * `eri_imag_norm = max_abs(eri.imag)` diagnostic of eri_transform.py:385-394 (compared with ERI_IMAG_TOL by the

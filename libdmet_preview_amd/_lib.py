@@ -109,6 +109,7 @@ PROTOTYPES = {
     "dmk_eri_flops": (c_int, [c_vp, P(c_dbl)]),
     "dmk_eri_fused_launches": (c_int, [c_vp, P(c_i64)]),
     "dmk_eri_split_step1": (c_int, [c_vp, P(c_int)]),
+    "dmk_eri_strip_step1": (c_int, [c_vp, P(c_int)]),
     "dmk_eri_imag_norm": (c_int, [c_vp, P(c_dbl)]),
     "dmk_eri_imag_buffer": (c_int, [c_vp, P(c_vp), P(c_i64)]),
     "dmk_dfjk_begin": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, P(c_vp)]),

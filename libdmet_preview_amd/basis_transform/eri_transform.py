@@ -992,11 +992,19 @@ def split_step1_wanted(nemb, can_go_warm, inv_cols=None):
                 and os.environ.get("DMK_ERI_SPLIT1", "1") != "0")
 
 
+def strip_step1_wanted(split1):
+    """Should a caller that asks for the split step 1 (`split1`: what split_step1_wanted gave it) ask for the strip order on top
+    ?  Wherever it asks for the split: the same rule, so the uncached A/B run (DMK_ERI_INV=0) of a caller that can go
+    warm stays in the mode too.  DMK_ERI_STRIP=0 is the A/B switch and gives the order of K6l; DMK_ERI_SPLIT1=0 switches both off."""
+    return bool(split1 and os.environ.get("DMK_ERI_STRIP", "1") != "0")
+
+
 class EriEngine(object):
     """Owns a dmk_eri pipeline: plan -> (begin_kL, push_block*, end_kL)* on one GPU."""
 
     def __init__(self, ctx, kmesh, nao, naux, nemb, spin, C_ao_emb_dev, eri_dev, t_reversal_symm=True, gso=False, plan=None,
-                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None, inv_block=True, split_step1=False):
+                 track_imag=False, rows_only=False, inv_cache=None, inv_cols=None, inv_block=True, split_step1=False,
+                 strip_step1=False):
         """`plan` = (weights, records) of `general_plan` for k lists that are not the np.fft-ordered Gamma-centred mesh
         (then `kmesh` only carries the number of k-points, [nk, 1, 1]); default: the integer-mesh plan of libdmetk.
         `inv_cache`: an EriInvariantCache; the library attaches it only where the invariant region exists (the grouped
@@ -1011,6 +1019,9 @@ class EriEngine(object):
         `split_step1`: ask for the split step-1 mode (dmk_eri_begin flag 8): the partner term of plane rows
         [192,256) x columns [0,128) from W, step 1 of a warm kL over columns [128,256) only; for callers whose kL can come from
         the cache (a dense kL pays 5/4 of step 1).  `self.split_step1` tells whether the library granted it.
+        `strip_step1`: ask for the strip order on top (dmk_eri_begin flag 16; it implies the split and is granted
+        with it): plane rows [192,256) x columns [128,256) by a second W-partner workgroup, the cached region grown to the pairs
+        b <= a < 192, step 1 of a warm kL over columns [192,256) only.  `self.strip_step1` tells whether the library granted it.
         `rows_only`: a pipeline WITHOUT an ERI of its own (`eri_dev` may be None): its planes are only ever taken slab-wise
         with `contract_rows_into`; every path that would contract into an internal ERI refuses instead (dmk_eri_begin flag 4).
         `track_imag`: without time reversal also accumulate the imaginary part of the contraction for the reference's
@@ -1026,12 +1037,14 @@ class EriEngine(object):
         self.track_imag = bool(track_imag) and not self.tr
         ctx.check(lib.dmk_eri_begin(ctx.h, mesh3(self.kmesh), self.nao, self.naux, self.nemb, self.spin,
                                     (1 if self.tr else 0) | (2 if self.track_imag else 0) | (4 if rows_only else 0) |
-                                    (8 if (split_step1 and not self.gso) else 0),
+                                    (8 if (split_step1 and not self.gso) else 0) | (16 if (strip_step1 and not self.gso) else 0),
                                     C_ao_emb_dev.ptr, None if eri_dev is None else eri_dev.ptr, C.byref(h)))
         self.h = h
         on = C.c_int(0)
         ctx.check(lib.dmk_eri_split_step1(self.h, C.byref(on)))
         self.split_step1 = bool(on.value)
+        ctx.check(lib.dmk_eri_strip_step1(self.h, C.byref(on)))
+        self.strip_step1 = bool(on.value)
         self.weights, self.records = eri_plan(self.kmesh, self.tr) if plan is None else plan
         self.nslots = 1
         self.block_buf = ctx.empty((self.naux, self.nao, self.nao), np.complex128)
@@ -1571,7 +1584,8 @@ def _emb_eri_fast_gdf(cell, mydf, C_ao_lo, basis, kscaled_center, symmetry, C_ao
             inv = mydf.inv_cache
     split1 = split_step1_wanted(nemb, can_cache and getattr(mydf, "df_token", None) is not None, inv_cols)
     eng = EriEngine(ctx, kmesh, nao, naux, nemb, spin, C_dev, eri_dev, t_reversal_symm, plan=plan,
-                    track_imag=not t_reversal_symm, inv_cache=inv, inv_cols=inv_cols, split_step1=split1)
+                    track_imag=not t_reversal_symm, inv_cache=inv, inv_cols=inv_cols, split_step1=split1,
+                    strip_step1=strip_step1_wanted(split1))
     try:
         kL_list = None
         dist = None

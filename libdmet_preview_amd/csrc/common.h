@@ -370,6 +370,9 @@ struct Half2Launch {
     const void *W = nullptr;             // [spin][slot][nL][nao][64] (HalfWLaunch)
     const void *C = nullptr; const int *ki = nullptr, *kj = nullptr;    // C_i / C_j of block s: C + k[s] * nao * nemb (+ cj_spin_stride)
     long long w_slot_stride = 0, w_spin_stride = 0;
+    // with W, the strip order: the triangle [128,256)^2 as a strip of type 1's geometry plus a corner, so that a
+    // skip_invariant launch (type 1 and the strip) reads columns [192,256) of Ut only
+    bool strip = false;
 };
 int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q);
 // Step 2 of `q2` and step 1 of `q1` (the NEXT group: it must not write what q2 reads) in one launch.  1: launched, 0: declined and

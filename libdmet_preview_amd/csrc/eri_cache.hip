@@ -14,7 +14,10 @@
 // The table-driven kernel (zhot_tab.hip) owns blocks by data: with A = 16 floor(ninv / 16) for `ninv` invariant leading columns, the
 // 16 x 16 blocks of block rows below A / 16 hold exactly the pairs b <= a < A -- the prefix [0, A (A + 1) / 2) of every plane row, a
 // function of columns [0, A) alone.  A warm kL copies the prefix back and launches the table without those block rows.
-constexpr int INV_COLS = 192, INV_PREFIX = 8256, INV_ROW = INV_PREFIX + 64 * 128;
+//
+// In the strip order (K6m) the corner [128,192)^2 has a workgroup type of its own too, and the region is every pair b <= a < 192: the
+// contiguous prefix [0, INV_STRIP_ROW) of every plane row, copied like the table path's.
+constexpr int INV_COLS = 192, INV_PREFIX = 8256, INV_ROW = INV_PREFIX + 64 * 128, INV_STRIP_ROW = 192 * 193 / 2;
 
 struct dmk_eri_cache {
     dmk_ctx *ctx;
@@ -22,7 +25,7 @@ struct dmk_eri_cache {
     // what the entries were built from: the shape, the region (tab_A: 0 = that of the nemb = 256 kernel, else A of the table path)
     // and columns [0, ncols) of C_ao_emb ([spin nk nao][ncols] c128; ncols = INV_COLS or A)
     bool have_cols = false;
-    int shape[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // mesh, nao, naux, nemb, spin, partner order of type 1 (split step 1)
+    int shape[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // mesh, nao, naux, nemb, spin, order of step 2 (0 old, 1 split step 1, 2 strip)
     int tab_A = 0, ncols = 0;
     DevMem cols;
     size_t cols_rows = 0;
@@ -102,7 +105,7 @@ __global__ void blk_corner_kernel(double *__restrict__ eri, double *__restrict__
 }
 
 // doubles per auxiliary row and plane of a cache entry of this pipeline's region
-int inv_row_len(const dmk_eri *h) { return h->inv_A ? h->inv_A * (h->inv_A + 1) / 2 : INV_ROW; }
+int inv_row_len(const dmk_eri *h) { return h->inv_A ? h->inv_A * (h->inv_A + 1) / 2 : h->strip1 ? INV_STRIP_ROW : INV_ROW; }
 
 // One verdict of a device-side check: the cache's flag is zeroed, `launch` enqueues a kernel that sets it, and the flag is read
 // back (the one synchronisation of the check).
@@ -137,7 +140,7 @@ int cols_same(dmk_eri *h, dmk_eri_cache *c, const double2 *stored, int col0, int
 static int inv_region_copy(dmk_eri *h, double *entry, bool to_planes) {
     dmk_ctx *ctx = h->ctx;
     const int nplanes = h->re_only ? 1 : 2;
-    const int row = inv_row_len(h), prefix = h->inv_A ? row : INV_PREFIX;
+    const int row = inv_row_len(h), prefix = (h->inv_A || h->strip1) ? row : INV_PREFIX;
     const dim3 grid((row + 255) / 256, (unsigned)h->naux, (unsigned)(h->spin * nplanes));
     FamScope fs(ctx, DMK_FAM_MISC);
     hipLaunchKernelGGL(to_planes ? inv_region_copy_kernel<true> : inv_region_copy_kernel<false>, grid, dim3(256), 0, ctx->stream,
@@ -228,7 +231,7 @@ int dmk_eri_cache_stats(const dmk_eri_cache *cache, int64_t stats[5]) {
 // or a single bit drops every entry.
 static int inv_attach(dmk_eri *h, dmk_eri_cache *cache, int tab_A, int ncols, int *attached) {
     dmk_ctx *ctx = h->ctx;
-    const int shape[8] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin, h->split1 ? 1 : 0};
+    const int shape[8] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin, h->strip1 ? 2 : h->split1 ? 1 : 0};
     const size_t rows = (size_t)h->spin * h->mesh.nk * h->nao;
     bool same = cache->have_cols && cache->cols_rows == rows && cache->tab_A == tab_A && cache->ncols == ncols;
     for (int i = 0; i < 8 && same; ++i) same = cache->shape[i] == shape[i];
@@ -387,6 +390,7 @@ int blk_decide(dmk_eri *h, int kchunk_w2, int kchunk_w1, int *skip, bool *save, 
     const int64_t head[] = {h->mesh.n[0], h->mesh.n[1], h->mesh.n[2], h->nao, h->naux, h->nemb, h->spin, h->pr, h->pl, h->blk_ne, S,
                             kchunk_w2, kchunk_w1, h->n_w2, h->n_w1};
     if (h->split1) k = blk_mix(k, 0x73706c6974ULL);          // the other partner order of type 1: never the same entry
+    if (h->strip1) k = blk_mix(k, 0x7374726970ULL);          // nor the strip order
     for (int64_t v : head) k = blk_mix(k, (uint64_t)v);
     for (int w = 2; w >= 1; --w) {
         const dmk_eri::WeightClass wc = h->weight_class(w);

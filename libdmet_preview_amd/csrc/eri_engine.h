@@ -128,6 +128,10 @@ struct dmk_eri {
     // stay bit-identical -- and a warm kL runs step 1 over columns [128,256) only.  W sits behind the halves of Ut in the same
     // workspace, one half per half of Ut, [spin][group][naux nao][64] each.
     bool split1 = false;
+    // STRIP STEP 1 (flags bit 4; implies split1, granted with it): step 2 covers the triangle [128,256)^2 with a strip
+    // (rows [192,256) x cols [128,256), the W partner) and a corner ([128,192)^2) in place of type 3, the cached region grows by the
+    // corner to the pairs b <= a < 192, and a warm kL runs step 1 over columns [192,256) only (tile 3 of four) plus W.
+    bool strip1 = false;
     double2 *Wbuf = nullptr;
     size_t w_half_elems = 0;
     dmk_eri(dmk_ctx *c, const int m[3]) : ctx(c), mesh(m) {}

@@ -152,15 +152,16 @@ int dmk_eri_begin(dmk_ctx *ctx, const int mesh[3], int nao, int naux, int nemb, 
     // split step 1 (flags bit 3): where the invariant planes may attach -- the grouped nemb = 256 path with time reversal and no
     // imaginary-part tracking -- with nao on the K tile, a block in one range of L and step 1 on the tile the W kernel shares;
     // anything else, or no memory for W (C5: + 2.6 GB per half), runs the old order for the whole transform
-    h->split1 = (flags & 8) && h->hot256 && h->group > 1 && h->tr && !h->imag && nemb == 256 && !kpad && h->hot_rows >= naux &&
+    h->split1 = (flags & (8 | 16)) && h->hot256 && h->group > 1 && h->tr && !h->imag && nemb == 256 && !kpad && h->hot_rows >= naux &&
                 half12_hot_usable(naux, nao, nemb) != 0 && m.nk <= 0x10000;
+    h->strip1 = h->split1 && (flags & 16);          // the strip order (bit 4) implies the split and is granted with it
     const size_t w_half_bytes = (size_t)spin * h->group * h->w_slot_elems() * sizeof(double2);
     size_t ut_bytes = (half_bytes + (h->split1 ? w_half_bytes : 0)) * (h->fuse ? 2 : 1);
     ws_take(ctx, 0, plane_bytes, h->planes);
     ws_take(ctx, 1, ut_bytes, h->Ut);
     if (h->planes && !h->Ut && h->split1) {        // no room for W: the old order
         (void)hipGetLastError();
-        h->split1 = false;
+        h->split1 = h->strip1 = false;
         ut_bytes = half_bytes * (h->fuse ? 2 : 1);
         ws_take(ctx, 1, ut_bytes, h->Ut);
     }
@@ -230,6 +231,12 @@ int dmk_eri_flops(const dmk_eri *h, double f[2]) {
 int dmk_eri_split_step1(const dmk_eri *h, int *on) {
     if (!h || !on) return DMK_ERR_INVALID;
     *on = h->split1 ? 1 : 0;
+    return DMK_OK;
+}
+
+int dmk_eri_strip_step1(const dmk_eri *h, int *on) {
+    if (!h || !on) return DMK_ERR_INVALID;
+    *on = h->strip1 ? 1 : 0;
     return DMK_OK;
 }
 
@@ -330,7 +337,8 @@ static Half1Launch half1_hot_desc(const dmk_eri *h, const double2 *L, int l0, in
     q.nL = nl; q.nao = h->nao; q.nemb = h->nemb; q.nspin = h->spin; q.kdim = h->kdim;
     q.ci_spin_stride = h->c_spin_stride(); q.ut_spin_stride = (long long)h->group * (long long)h->slot_elems();
     // split step 1, warm kL: types 1 and 3 of step 2 read columns [128,256) of Ut only (tiles 2 and 3 of four)
-    if (h->split1 && h->inv_warm) q.first_col_tile = 2;
+    // (strip order: type 1 and the strip read columns [192,256) only -- tile 3)
+    if (h->split1 && h->inv_warm) q.first_col_tile = h->strip1 ? 3 : 2;
     return q;
 }
 
@@ -362,7 +370,7 @@ static void eri_step2_group(const dmk_eri *h, dmk_eri::Step2Group &g) {
     q.planes_spin_stride = h->planes_spin_stride(); q.re_only = h->re_only;
     q.skip_invariant = h->hot256 && g.inv_warm;
     if (h->split1) {
-        q.W = h->w_cur(); q.C = h->Ch;
+        q.W = h->w_cur(); q.C = h->Ch; q.strip = h->strip1;
         q.w_slot_stride = (long long)h->w_slot_elems(); q.w_spin_stride = (long long)h->group * q.w_slot_stride;
     }
     g.q = q;

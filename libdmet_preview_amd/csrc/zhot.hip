@@ -145,6 +145,9 @@ __global__ __launch_bounds__(HNT, 2) void half1w_kernel(const H1Args g, const HW
 // step 2 (nemb == 256): per L four workgroups
 //   type 0 / 1 : rows [128,192) / [192,256) x cols [0,128) of the off-diagonal square (8 blocks / wave)
 //   type 2 / 3 : diagonal triangle [0,128)^2 / [128,256)^2, block rows (w, 7-w) per wave (9 blocks / wave)
+// strip order (K6m, half2s_kernel): type 3 gives way to
+//   strip      : rows [192,256) x cols [128,256), type 1's geometry and W partner, b <= a written (8 blocks / wave)
+//   corner     : diagonal triangle [128,192)^2, block rows (w, 3-w) on waves 0 and 1 (5 blocks each)
 // =============================================================================================
 constexpr int H2_N = 256, H2_BK = 4;
 constexpr int H2_MAXSLOT = 16;
@@ -194,7 +197,7 @@ struct H2WArgs {
 template <int LAB = 0, bool RE = false>
 __global__ __launch_bounds__(HNT, 2) void half2_kernel(const H2Args g) {
     __shared__ __attribute__((aligned(16))) double2 lds[H2_LDS];
-    constexpr bool SPL = false;
+    constexpr bool SPL = false, STRIP = false;
     const H2WArgs gw{};
 #define ZH_BLOCK_ID blockIdx.x
 #include "zhot_half2_body.inc"
@@ -205,7 +208,19 @@ template <bool RE>
 __global__ __launch_bounds__(HNT, 2) void half2w_kernel(const H2Args g, const H2WArgs gw) {
     __shared__ __attribute__((aligned(16))) double2 lds[H2_LDS];
     constexpr int LAB = 0;
-    constexpr bool SPL = true;
+    constexpr bool SPL = true, STRIP = false;
+#define ZH_BLOCK_ID blockIdx.x
+#include "zhot_half2_body.inc"
+#undef ZH_BLOCK_ID
+}
+
+// K6m, the strip instantiations (STRIP in zhot_half2_body.inc): per (L, spin) the workgroups 0, 1, 2, corner, strip (dense) or 1 and
+// the strip (warm) -- no workgroup reads columns [128,192) of Ut on a warm kL.  Same arguments as the split form.
+template <bool RE>
+__global__ __launch_bounds__(HNT, 2) void half2s_kernel(const H2Args g, const H2WArgs gw) {
+    __shared__ __attribute__((aligned(16))) double2 lds[H2_LDS];
+    constexpr int LAB = 0;
+    constexpr bool SPL = true, STRIP = true;
 #define ZH_BLOCK_ID blockIdx.x
 #include "zhot_half2_body.inc"
 #undef ZH_BLOCK_ID
@@ -214,7 +229,7 @@ __global__ __launch_bounds__(HNT, 2) void half2w_kernel(const H2Args g, const H2
 // (as half1_body: the device function of the same text, for half12_kernel)
 template <int LAB, bool RE>
 __device__ __forceinline__ void half2_body(const H2Args &g, const unsigned bid, double2 *const lds) {
-    constexpr bool SPL = false;
+    constexpr bool SPL = false, STRIP = false;
     const H2WArgs gw{};
 #define ZH_BLOCK_ID bid
 #include "zhot_half2_body.inc"
@@ -223,7 +238,16 @@ __device__ __forceinline__ void half2_body(const H2Args &g, const unsigned bid, 
 template <bool RE>
 __device__ __forceinline__ void half2w_body(const H2Args &g, const H2WArgs &gw, const unsigned bid, double2 *const lds) {
     constexpr int LAB = 0;
-    constexpr bool SPL = true;
+    constexpr bool SPL = true, STRIP = false;
+#define ZH_BLOCK_ID bid
+#include "zhot_half2_body.inc"
+#undef ZH_BLOCK_ID
+}
+
+template <bool RE>
+__device__ __forceinline__ void half2s_body(const H2Args &g, const H2WArgs &gw, const unsigned bid, double2 *const lds) {
+    constexpr int LAB = 0;
+    constexpr bool SPL = true, STRIP = true;
 #define ZH_BLOCK_ID bid
 #include "zhot_half2_body.inc"
 #undef ZH_BLOCK_ID
@@ -252,6 +276,15 @@ template <bool RE>
 __global__ __launch_bounds__(HNT, 2) void half12w_kernel(const H2Args g2, const H2WArgs gw2, const H1Args g1, const HWArgs gw1) {
     __shared__ __attribute__((aligned(16))) double2 lds[H12_LDS];
     if (blockIdx.x < g2.nblocks) half2w_body<RE>(g2, gw2, blockIdx.x, lds);
+    else if (blockIdx.x - g2.nblocks < g1.nblocks) half1_body<true, H1_BM, false, 0, false>(g1, blockIdx.x - g2.nblocks, lds);
+    else halfw_body(gw1, blockIdx.x - g2.nblocks - g1.nblocks, lds);
+}
+
+// The strip form (K6m): the same launch with the strip instantiation of step 2
+template <bool RE>
+__global__ __launch_bounds__(HNT, 2) void half12s_kernel(const H2Args g2, const H2WArgs gw2, const H1Args g1, const HWArgs gw1) {
+    __shared__ __attribute__((aligned(16))) double2 lds[H12_LDS];
+    if (blockIdx.x < g2.nblocks) half2s_body<RE>(g2, gw2, blockIdx.x, lds);
     else if (blockIdx.x - g2.nblocks < g1.nblocks) half1_body<true, H1_BM, false, 0, false>(g1, blockIdx.x - g2.nblocks, lds);
     else halfw_body(gw1, blockIdx.x - g2.nblocks - g1.nblocks, lds);
 }
@@ -378,12 +411,18 @@ int half2_hot_plan(dmk_ctx *ctx, const Half2Launch &q, H2Args &a, double &flops)
     if (!half2_hot_usable(q.nao, q.nemb)) return 0;
     if (!fill_half2_queue(a, q, H2_BK)) return 0;
     a.skip_invariant = q.skip_invariant ? 1 : 0;
-    a.nblocks = (unsigned)((q.skip_invariant ? 2 : 4) * q.nL * q.nspin);
+    if (q.strip && !q.W) return dmk_fail(ctx, DMK_ERR_INVALID, "half2_hot: the strip order needs the W operand of the split partner term");
+    if ((long long)(q.skip_invariant ? 2 : q.strip ? 5 : 4) * q.nL * q.nspin > 0x7fffffffLL) return 0;
+    a.nblocks = (unsigned)((q.skip_invariant ? 2 : q.strip ? 5 : 4) * q.nL * q.nspin);
     // 136 of the 256 16 x 16 blocks per L and spin; a block with the time-reversal partner term runs a second segment
     // (without the 16 diagonal blocks when the whole group is symmetrised: they are folded in the epilogue)
     // skip_invariant: types 1 and 3 only -- 32 + 36 = 68 blocks, the partner term without the 8 diagonal blocks of type 3 when folded
     const double nsym = (double)__builtin_popcount(a.symmask);
-    const double blocks = q.skip_invariant ? 68.0 * q.nslot + (a.fold_diag ? 60.0 : 68.0) * nsym
+    // strip order (K6m): warm, type 1 and the strip -- 32 + 32 blocks, each with its partner product; dense, types 0, 1, 2, the
+    // corner (10 blocks, 4 of them diagonal) and the strip -- 32 + 32 + 36 + 10 + 32 = 142, the partner term without the 8 + 4 folded
+    // diagonal blocks
+    const double blocks = q.strip ? (q.skip_invariant ? 64.0 * q.nslot + 64.0 * nsym : 142.0 * q.nslot + (a.fold_diag ? 130.0 : 142.0) * nsym)
+                          : q.skip_invariant ? 68.0 * q.nslot + (a.fold_diag ? 60.0 : 68.0) * nsym
                                            : 136.0 * q.nslot + (a.fold_diag ? 120.0 : 136.0) * nsym;
     flops = (q.re_only ? 4.0 : 6.0) * blocks * 256.0 * (double)a.kdim * (double)q.nL * (double)q.nspin;
     return 1;
@@ -428,7 +467,11 @@ int launch_half2_hot(dmk_ctx *ctx, const Half2Launch &q) {
         if (!half2w_hot_plan(q, a, w)) return 0;
         FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
         fs.mfma_flops(flops);
-        if (q.re_only) hipLaunchKernelGGL(half2w_kernel<true>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
+        if (q.strip) {
+            if (q.re_only) hipLaunchKernelGGL(half2s_kernel<true>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
+            else hipLaunchKernelGGL(half2s_kernel<false>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
+        }
+        else if (q.re_only) hipLaunchKernelGGL(half2w_kernel<true>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
         else hipLaunchKernelGGL(half2w_kernel<false>, dim3(a.nblocks), dim3(HNT), 0, ctx->stream, a, w);
         DMK_CHECK_LAUNCH(ctx);
         return 1;
@@ -471,7 +514,11 @@ int launch_half12_hot(dmk_ctx *ctx, const Half2Launch &q2, const Half1Launch &q1
         if (nbw > 0x7fffffffull) return 0;
         FamScope fs(ctx, DMK_FAM_ZGEMM_HALF2);
         fs.share_with(DMK_FAM_ZGEMM_HALF1, f2, f1 + fw);
-        if (q2.re_only) hipLaunchKernelGGL(half12w_kernel<true>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
+        if (q2.strip) {
+            if (q2.re_only) hipLaunchKernelGGL(half12s_kernel<true>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
+            else hipLaunchKernelGGL(half12s_kernel<false>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
+        }
+        else if (q2.re_only) hipLaunchKernelGGL(half12w_kernel<true>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
         else hipLaunchKernelGGL(half12w_kernel<false>, dim3((unsigned)nbw), dim3(HNT), 0, ctx->stream, a2, w2, a1, aw);
         DMK_CHECK_LAUNCH(ctx);
         return 1;

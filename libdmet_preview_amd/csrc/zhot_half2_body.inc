@@ -1,13 +1,23 @@
 // Body of the nemb = 256 step-2 kernel (zhot.hip), included as text where a kernel runs it: half2_kernel and half2_body, the device
 // function behind half12_kernel.  In scope at the include: the template parameters LAB, RE; `g` (H2Args); `lds`, H2_LDS complex in
 // LDS; ZH_BLOCK_ID, the workgroup's block id within the step-2 grid (before the XCD remap over g.nblocks); SPL and `gw` (H2WArgs):
-// the split partner term of type 1 (DESIGN.md K6l) -- with SPL false every `if constexpr (SPL)` folds away and `gw` is never read.
+// the split partner term of type 1 (DESIGN.md K6l) -- with SPL false every `if constexpr (SPL)` folds away and `gw` is never read;
+// STRIP (K6m, implies SPL): the triangle [128,256)^2 is covered by a strip (type 4: rows [192,256) x cols [128,256), type 1's geometry
+// moved 128 columns to the right, W partner) and a corner (type 5: the triangle [128,192)^2, four block rows) instead of type 3.
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar LDS-DMA addressing
     const int frag_k = lane >> 4, frag_x = lane & 15;
     const unsigned lid = xcd_remap(ZH_BLOCK_ID, g.nblocks);
     // (blockIdx and kernel arguments only: wave-uniform either way)
-    const int Lall = g.skip_invariant ? (int)(lid >> 1) : (int)(lid >> 2);
-    const int type = g.skip_invariant ? 1 + 2 * (int)(lid & 1) : (int)(lid & 3);
+    int Lall_, type_;
+    if constexpr (STRIP) {
+        // warm: types 1 and 4 per (L, spin); dense: 0, 1, 2, the corner and the strip
+        if (g.skip_invariant) { Lall_ = (int)(lid >> 1); type_ = (lid & 1) ? 4 : 1; }
+        else { Lall_ = (int)(lid / 5u); const int t5 = (int)lid - 5 * Lall_; type_ = t5 < 3 ? t5 : t5 == 3 ? 5 : 4; }
+    } else {
+        Lall_ = g.skip_invariant ? (int)(lid >> 1) : (int)(lid >> 2);
+        type_ = g.skip_invariant ? 1 + 2 * (int)(lid & 1) : (int)(lid & 3);
+    }
+    const int Lall = Lall_, type = type_;
     const int sp = Lall >= g.nL ? 1 : 0;     // nspin <= 2
     const int L = Lall - sp * g.nL;
     const long long nemb = H2_N;
@@ -22,9 +32,10 @@
     // C_j of queued block SLOT: the pointer of the launch, or (SPL) through the packed k_j
 #define ZH_CJ(SLOT) (SPL ? gw.C + cj_off + (long long)H2_PICK_K2(gw.kj2, SLOT) * (g.nao * nemb) : H2_PICK_CJ(g, SLOT) + cj_off)
 
-    if (type >= 2) {
+    if (STRIP ? (type == 2 || type == 5) : type >= 2) {
         // ---------------- diagonal triangle [d0, d0+128)^2 ----------------------------------------
-        const int d0 = (type - 2) * 128;
+        // (STRIP, type 5: the same panels at d0 = 128, of which only block rows 0-3 -- the corner [128,192)^2 -- are computed)
+        const int d0 = STRIP ? (type == 5 ? 128 : 0) : (type - 2) * 128;
         // stage = 16 pieces of 64 complex: piece p < 8 -> U row p/2, half p%2 ; p >= 8 -> C likewise; 4 pieces per wave
         unsigned voff[4];                      // byte offset of this lane's 16 B inside a K-tile of the operand
 #pragma unroll
@@ -56,9 +67,9 @@
                        lds_addr_of(st + (wave + 4) * 64), lds_addr_of(st + (wave + 8) * 64), lds_addr_of(st + (wave + 12) * 64));
             issue_advance();
         };
-        auto run = [&](auto tag) {
+        auto run = [&](auto tag, auto tag2) {
             constexpr int R1 = decltype(tag)::value;
-            constexpr int R2 = 7 - R1;
+            constexpr int R2 = decltype(tag2)::value;
             cacc acc1[R1 + 1], acc2[R2 + 1];
 #pragma unroll
             for (int c = 0; c <= R1; ++c) cacc_zero(acc1[c]);
@@ -142,17 +153,41 @@
                     pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row2, d0 + c * 16 + frag_x, acc2[c], r);
             }
         };
+        if constexpr (STRIP) {
+            if (type == 5) {
+                // the corner: block rows paired (w, 3 - w), 5 of its 10 blocks each on waves 0 and 1 -- every accumulator sees the
+                // products type 3 of the other orders gives it, in the same sequence; waves 2 and 3 feed the ring and keep the barriers
+                if (wave == 0) run(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+                else if (wave == 1) run(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
+                else {
+                    issue();
+                    if (T > 1) issue();
+                    if (T > 2) issue();
+                    for (int t = 0; t < T; ++t) {
+                        const int later = T - 1 - t;
+                        if (later >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                        else if (later == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        __builtin_amdgcn_s_barrier();
+                        if (t + 3 < T) issue();
+                    }
+                    if (fold) __syncthreads();
+                }
+                return;
+            }
+        }
         switch (wave) {
-            case 0: run(std::integral_constant<int, 0>{}); break;
-            case 1: run(std::integral_constant<int, 1>{}); break;
-            case 2: run(std::integral_constant<int, 2>{}); break;
-            default: run(std::integral_constant<int, 3>{}); break;
+            case 0: run(std::integral_constant<int, 0>{}, std::integral_constant<int, 7>{}); break;
+            case 1: run(std::integral_constant<int, 1>{}, std::integral_constant<int, 6>{}); break;
+            case 2: run(std::integral_constant<int, 2>{}, std::integral_constant<int, 5>{}); break;
+            default: run(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{}); break;
         }
         return;
     }
 
     // ---------------- off-diagonal half square: rows [r0, r0+64) x cols [0,128) -------------------------
-    const int r0 = 128 + 64 * type;
+    const int r0 = STRIP ? (type == 0 ? 128 : 192) : 128 + 64 * type;
+    const int cb0 = (STRIP && type == 4) ? 128 : 0;       // first column of the Cb and Ub (C_i) pieces and of the output
     const int wm = wave >> 1, wn = wave & 1;            // wave tile 32 x 64
     // SPL, type 1: the partner segment is S[a][b] += sum_p W[p][a] conj(C_i[p][b]) -- the Ca pieces are rows of the W panel (64
     // columns), the Ub pieces rows of C_i (columns [0,128), conjugated at the fragment read); type 0 keeps Ca / Ub.
@@ -160,7 +195,7 @@
     // never written (halfw_body skips it) and holds whatever the buffer held -- deliberate, the loads stay inside the allocation and
     // c_sym gates every MFMA that would read them.  Likewise columns [0,128) of Ut are stale on a warm kL: only type 0 reads them.
     bool wpart = false;
-    if constexpr (SPL) wpart = type == 1;
+    if constexpr (SPL) wpart = STRIP ? type != 0 : type == 1;
     const double csign = wpart ? -1.0 : 1.0;
     // stage = 24 pieces of 64 complex: 0-3 Ua rows, 4-11 Cb (row*2+half), 12-15 Ca rows, 16-23 Ub (row*2+half)
     unsigned voff[6];
@@ -169,9 +204,9 @@
         const int piece = wave + 4 * h;
         int row, col;
         if (piece < 4) { row = piece; col = r0; }
-        else if (piece < 12) { row = (piece - 4) >> 1; col = ((piece - 4) & 1) * 64; }
+        else if (piece < 12) { row = (piece - 4) >> 1; col = cb0 + ((piece - 4) & 1) * 64; }
         else if (piece < 16) { row = piece - 12; col = r0; }
-        else { row = (piece - 16) >> 1; col = ((piece - 16) & 1) * 64; }
+        else { row = (piece - 16) >> 1; col = cb0 + ((piece - 16) & 1) * 64; }
         voff[h] = (unsigned)((row * (int)nemb + col + lane) * 16);
         if constexpr (SPL) { if (wpart && piece >= 12 && piece < 16) voff[h] = (unsigned)((row * 64 + lane) * 16); }
     }
@@ -279,6 +314,6 @@
             const int row = r0 + wm * 32 + i * 16 + frag_k + 4 * r;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row, wn * 64 + j * 16 + frag_x, acc[i][j], r);
+                pack_acc_t<RE>(g_planes, g_naux, g_npair, L, row, cb0 + wn * 64 + j * 16 + frag_x, acc[i][j], r);      // (strip: b <= a only)
         }
 #undef ZH_CJ

@@ -425,11 +425,13 @@ def eri_stage(ctx, sysm, d_C, nemb, eri_dev, kL_list=None, timers=None, max_bloc
             inv = sysm.eri_inv_cache = et.EriInvariantCache(ctx)
     # split step 1: asked for exactly where the cache above could exist -- a provider with a token and 192 impurity
     # columns -- with or without DMK_ERI_INV, so the uncached A/B run sums in the order of the cached ones; a caller that can never
-    # go warm never pays the dense surcharge.  DMK_ERI_SPLIT1=0: the old order
+    # go warm never pays the dense surcharge.  DMK_ERI_SPLIT1=0: the old order.  The strip order (K6m) rides on the same rule;
+    # DMK_ERI_STRIP=0 keeps K6l's
     srcs = [p for p in (sysm.df, getattr(sysm, "df_resident", None)) if p is not None]
     split1 = et.split_step1_wanted(nemb, any(getattr(p, "df_token", None) is not None for p in srcs), len(sysm.imp_idx))
     eng = et.EriEngine(ctx, sysm.mesh, sysm.nao, sysm.naux, nemb, sysm.spin, d_C, eri_dev, True, inv_cache=inv,
-                       inv_cols=len(sysm.imp_idx), inv_block=os.environ.get("DMK_ERI_INV_BLOCK", "1") != "0", split_step1=split1)
+                       inv_cols=len(sysm.imp_idx), inv_block=os.environ.get("DMK_ERI_INV_BLOCK", "1") != "0", split_step1=split1,
+                       strip_step1=et.strip_step1_wanted(split1))
     rows = None
     try:
         todo = eng.irreducible_kL() if kL_list is None else list(kL_list)
