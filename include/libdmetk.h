@@ -632,6 +632,28 @@ int dmk_jk_s4_rows(dmk_ctx *ctx, int n, const double *eri, int64_t ld, int nrang
  * solver/scf.py:311-321. */
 int dmk_eri_to_s4(dmk_ctx *ctx, int n, int from_symmetry, const double *in, double *out);
 
+/* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
+ * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the
+ * indicator of the nimp impurity indices imp_idx_host (host int32, inside [0, n), no repeats; nimp = 0 is legal):
+ * get_H2_scaled, slater.py:1734-1778, bit for bit.
+ *   (in_symmetry, out_symmetry) = (4, 4), (1, 4), (8, 4), (4, 1): the rule of the 4-fold branch -- weight 1 copies the element
+ *       untouched, weights 1/4, 1/2, 3/4 are one multiply, weight 0 ASSIGNS +0.0 (a NaN or Inf there does not survive);
+ *       (1 | 8, 4) gathers as dmk_eri_to_s4 first, (4, 1) writes ao2mo.restore(1, .) of the scaled 4-fold block directly;
+ *   (1, 1): the rule of the 1-fold branch -- every element is multiplied, by 0.0 and 1.0 too (NaN stays NaN).
+ * Layouts: 4-fold npair x npair and 1-fold n^2 x n^2 row-major with pitches ld_in / ld_out in elements (at least a row;
+ * ld_in is not read for the 8-fold input, which is the packed lower triangle of the 4-fold matrix).  in == out with equal
+ * symmetry and pitch scales in place; any other overlap of the two is DMK_ERR_INVALID, as are bad indices, before any launch.
+ * 16-byte accesses where bases and pitches allow, 8-byte ones otherwise; all offsets 64-bit.  Returns after the stream drained. */
+int dmk_dmet_h2_scaled(dmk_ctx *ctx, int n, const int32_t *imp_idx_host, int nimp, int in_symmetry, const double *in,
+                       int64_t ld_in, int out_symmetry, double *out, int64_t ld_out);
+/* Democratic global density stripe of one fragment whose impurity indices lie in the first cell (get_rho_glob_R, compact form,
+ * slater_helper.py:229-249): with G[T] = B[T] rho_emb B[0]^T,
+ *     out[s][T][i][j] = 1/2 ( m_j G[T][i][j] + m_i G[subtract(0, T)][j][i] )
+ * basis (spin, ncells, nlo, neo), rho_emb (spin, neo, neo; symmetric), out (spin, ncells, nlo, nlo): device f64, cells in the
+ * order of dmk_cell_add_table.  One dmk_dgemm_batched product per spin and a combine kernel; the workspace is freed on return. */
+int dmk_rho_glob(dmk_ctx *ctx, const int mesh[3], int nlo, int neo, int spin, const double *basis, const double *rho_emb,
+                 const int32_t *imp_idx_host, int nimp, double *out);
+
 /* ---- correlation-potential fit (routine/slater.py:851-1329) ------------------
  * Row dots and column sums of a row-major matrix A (M x N, lda) in ONE streaming pass:
  *     yrow[r] = sum_c A[r][c] xrow[c]   (xrow != NULL)      -> grad[p] = <dV_dparam[p], dw_dV>,  slater.py:1141

@@ -56,6 +56,14 @@ _FUNCTIONS = [
     # response formulas, the Cholesky vectors behind convert_eri_to_gdf
     ("routine.slater_helper", ["routine.slater_helper", "routine.slater"], ["get_rdm1_idem"]),
     ("routine.slater", ["routine.slater"], ["get_active_projector_full"]),
+    # behind the solver: results, the democratic global density, the veff rebuild and the DMET energy Hamiltonian
+    # (dmet/Hubbard.py:43-71 calls them as slater.*; routine/spinless.py:23 keeps its own copies of the two scalers: the GSO twin
+    # is not built)
+    ("routine.slater", ["routine.slater"],
+     ["get_H1_scaled", "get_H2_scaled", "transformResults", "get_veff_from_rdm1_emb", "get_H_dmet", "get_E_dmet", "get_E_dmet_HF",
+      "get_H1_dmet"]),
+    ("routine.slater_helper", ["routine.slater_helper", "routine.slater"],
+     ["get_emb_basis_other_cell", "get_rho_glob_R", "get_rho_glob_k", "get_rho_glob_full"]),
     ("routine.ftsystem", ["routine.ftsystem"], ["kernel", "make_rdm1", "get_rho_grad", "get_dw_dv"]),
     ("utils.cholesky", ["utils.cholesky"], ["modified_cholesky", "modified_cholesky_uhf", "get_cderi_rhf", "get_cderi_uhf"]),
     ("routine.localizer", ["routine.localizer"], ["localize_bath", "localize_bath_scdm"]),

@@ -11,16 +11,25 @@ and the one-body folds into the embedding space (slater_helper.py:22-156):
   transform_local / transform_imp / transform_imp_env
   transform_4idx / transform_eri_local   (model lattices: four quarter transforms per cell, dmk_dgemm_tn_acc_rect)
 
+and, behind the solver, the democratic global density (slater_helper.py:158-309):
+
+  get_emb_basis_other_cell / get_rho_glob_R / get_rho_glob_k / get_rho_glob_full   one product per spin + dmk_rho_glob's combine
+
 The in-core 4-fold and 8-fold forms are padded on the device (dmk_pad_block_f64); `unit2emb_dev` keeps
 the ERI in HBM for callers that stay on the device.
 """
 import numpy as np
 
-from libdmet_preview_amd._lib import lib, get_ctx
+try:
+    from collections.abc import Iterable
+except ImportError:  # pragma: no cover
+    from collections import Iterable
+
+from libdmet_preview_amd._lib import lib, get_ctx, mesh3
 from libdmet_preview_amd.settings import IMAG_DISCARD_TOL
 from libdmet_preview_amd.utils import devmat
 from libdmet_preview_amd.utils import logger as log
-from libdmet_preview_amd.utils.misc import max_abs
+from libdmet_preview_amd.utils.misc import max_abs, add_spin_dim
 
 
 def init_H2(norb, eri_symmetry, dtype=np.double, spin_dim=None):
@@ -246,3 +255,99 @@ def transform_eri_local(basis, lattice, H2):
             _quarter_chain_dev(ctx, d_H2[1], nscsites, [d_b[1][i]] * 4, d_res[1], nbasis)
             _quarter_chain_dev(ctx, d_H2[2], nscsites, [d_b[0][i], d_b[0][i], d_b[1][i], d_b[1][i]], d_res[2], nbasis)
     return np.asarray([d.get() for d in d_res])
+
+
+# ---------------------------------------------------------------------------------------------
+# democratic global density (slater_helper.py:158-309)
+# ---------------------------------------------------------------------------------------------
+
+def get_emb_basis_other_cell(lattice, basis, R, reorder_idx=None):
+    """Embedding basis of the R-th cell's impurity problem: the cell blocks of `basis` permuted by I -> I - R."""
+    basis = np.asarray(basis)
+    old_shape = basis.shape
+    if len(old_shape) == 3:
+        basis = basis[None]
+    if reorder_idx is None:
+        reorder_idx = [lattice.subtract(I, R) for I in range(basis.shape[1])]
+    basis_R = basis[:, reorder_idx]
+    return basis_R[0] if len(old_shape) == 3 else basis_R
+
+
+def _lattice_mesh(lattice):
+    kmesh = getattr(lattice, "kmesh", None)
+    return mesh3(list(np.asarray(lattice.csize if kmesh is None else kmesh).ravel()))
+
+
+def rho_glob_stripe(lattice, basis, rho_emb):
+    """The compact democratic density (spin, ncells, nlo, nlo) of ONE fragment on the device (dmk_rho_glob).
+
+    The reference sums, over every cell R, the product C_R rho C_R[:nlo]^H of the basis shifted to R with its imp-env blocks
+    halved and its env-env block zeroed (slater_helper.py:229-249).  For impurity indices inside the first cell the masks leave
+    of that sum only   rho[T] = 1/2 (G[T] o m_j + G[subtract(0, T)]^T o m_i),   G[T] = B[T] rho_emb B[0]^T,
+    with m the impurity indicator: one product per spin.  `rho_emb` is taken symmetric, as a density matrix is (the transposed
+    term is read off the same product).  Impurity indices beyond the first cell raise NotImplementedError: the reference's
+    compact branch indexes its (ncells nlo, nlo) product out of range there."""
+    basis = np.asarray(basis, dtype=np.float64)
+    if basis.ndim == 3:
+        basis = basis[None]
+    spin, ncells, nlo, neo = basis.shape
+    rho_emb = np.asarray(add_spin_dim(rho_emb, spin, non_spin_dim=2))
+    if np.iscomplexobj(rho_emb):
+        rho_emb = rho_emb.real
+    imp = np.asarray(lattice.imp_idx, dtype=np.int64).ravel()
+    if imp.size and (imp.min() < 0 or imp.max() >= nlo):
+        raise NotImplementedError("get_rho_glob_R: impurity indices %s reach outside the first cell (nlo = %d); the democratic "
+                                  "sum collapses to one product only for a first-cell fragment" % (imp.tolist(), nlo))
+    mesh = _lattice_mesh(lattice)
+    table = np.empty((ncells, ncells), dtype=np.int32)
+    if lib.dmk_cell_add_table(mesh, -1, table.ctypes.data) != 0 or \
+            [lattice.subtract(0, T) for T in range(ncells)] != table[0].tolist():
+        raise NotImplementedError("get_rho_glob_R: the lattice's cell order is not the row-major mesh order of the device tables")
+    ctx = get_ctx()
+    d_b, d_r = ctx.to_device(basis), ctx.to_device(rho_emb, np.float64)
+    d_out = ctx.empty((spin, ncells, nlo, nlo), np.float64)
+    imp32 = np.ascontiguousarray(imp, dtype=np.int32)
+    ctx.check(lib.dmk_rho_glob(ctx.h, mesh, int(nlo), int(neo), int(spin), d_b.ptr, d_r.ptr,
+                               imp32.ctypes.data if imp32.size else None, int(imp32.size), d_out.ptr))
+    return d_out.get()
+
+
+def get_rho_glob_R(basis, lattice, rho_emb, symmetric=True, compact=True, sign=None):
+    """Global density in the site basis by democratic partitioning (slater_helper.py:183-270): (spin, ncells, nlo, nlo) if
+    compact, else (spin, ncells nlo, ncells nlo) = lattice.expand of the same stripe.  Lists of (basis, lattice, rho_emb) with
+    `sign` are the signed sum over fragments (and force the full form, as in the reference)."""
+    if not isinstance(lattice, Iterable):
+        basis, lattice, rho_emb = [basis], [lattice], [rho_emb]
+    if sign is None:
+        sign = np.ones(len(lattice), dtype=int)
+    else:
+        sign = np.asarray(sign)
+        compact = False
+    assert len(sign) == len(lattice)
+    rho_glob = 0.0
+    for basis_I, lattice_I, rho_emb_I, sign_I in zip(basis, lattice, rho_emb, sign):
+        rho_R = rho_glob_stripe(lattice_I, basis_I, rho_emb_I)
+        if not compact:
+            rho_R = lattice_I.expand(rho_R)
+        rho_glob = rho_glob + rho_R * sign_I
+    return rho_glob
+
+
+def get_rho_glob_k(basis, lattice, rho_emb, symmetric=True, compact=True, sign=None):
+    """lattice.R2k of the democratic stripe (slater_helper.py:272-290)."""
+    if sign is not None:
+        compact = False
+    rho_R = get_rho_glob_R(basis, lattice, rho_emb, symmetric=symmetric, compact=compact, sign=sign)
+    lat0 = lattice[0] if isinstance(lattice, Iterable) else lattice
+    return lat0.R2k(rho_R if compact else lat0.extract_stripe(rho_R))
+
+
+def get_rho_glob_full(basis, lattice, rho_emb, symmetric=True, compact=True, sign=None):
+    """The democratic density in full shape (slater_helper.py:292-309)."""
+    if sign is not None:
+        compact = False
+    rho_R = get_rho_glob_R(basis, lattice, rho_emb, symmetric=symmetric, compact=compact, sign=sign)
+    if compact:
+        lat0 = lattice[0] if isinstance(lattice, Iterable) else lattice
+        return lat0.expand(rho_R)
+    return rho_R
