@@ -632,6 +632,48 @@ int dmk_jk_s4_rows(dmk_ctx *ctx, int n, const double *eri, int64_t ld, int nrang
  * solver/scf.py:311-321. */
 int dmk_eri_to_s4(dmk_ctx *ctx, int n, int from_symmetry, const double *in, double *out);
 
+/* ---- the impurity solver at mean-field level (solver/scf.py:231-253, :354-460, :954-1043) --------
+ * J[dm_j] and K[dm_k] of one 4-fold block from ONE pass over it (dmk_jk_s4 streams the block once for J and once for K):
+ *     vj[i][j] = sum_kl (ij|kl) dm_j[k][l]          vk[j][k] = sum_il (ij|kl) dm_k[i][l]
+ * n <= 512.  Either density may be NULL (its output is then not touched; the call is then the matching dmk_jk_s4 pass).
+ * Fixed-order reductions, no atomics: bit-reproducible from run to run. */
+int dmk_fock_s4(dmk_ctx *ctx, int n, const double *eri, int64_t ld, const double *dm_j, const double *dm_k, double *vj, double *vk);
+/* The same restricted to host row ranges [lo, hi) with the rule and the partial-result meaning of dmk_jk_s4_rows. */
+int dmk_fock_s4_rows(dmk_ctx *ctx, int n, const double *eri, int64_t ld, int nranges, const int64_t *ranges_host, const double *dm_j,
+                     const double *dm_k, double *vj, double *vk);
+/* DIIS coefficients (HOST, no context): the c minimising |sum_i c_i e_i|^2 under sum_i c_i = 1 from the Gram matrix
+ * B[i][j] = <e_i, e_j> (m x m row-major, 1 <= m <= 12), through the pseudo-inverse of the bordered matrix of B scaled to unit
+ * largest diagonal (directions with |eigenvalue| <= 1e-13 are dropped).  An all-zero B gives c = (0, ..., 0, 1).
+ * DMK_ERR_NOCONV when no usable solution exists. */
+int dmk_diis_coeffs(int m, const double *B_host, double *c_host);
+/* Restricted (nspin = 1, orbitals occupied by 2, dm spin-traced) or unrestricted (nspin = 2) Hartree-Fock on resident 4-fold ERI
+ * blocks, which the handle BORROWS (aa; bb and ab for nspin = 2; pitch ld).  Copied at create: h1 (nspin, n, n); h1_energy
+ * (optional: the one-body term the ENERGY is taken with, e.g. h1 without a chemical-potential shift); ovlp and xorth = ovlp^-1/2
+ * (novlp = 0: identity; 1: one matrix; nspin: one per spin, UIHF.eig).  1 <= diis_dim <= 12.  All matrices, results and the DIIS
+ * ring live in one device allocation owned by the handle.
+ *   dmk_scf_run : nocc_host[nspin] occupied orbitals per spin (aufbau); dm0 (nspin, n, n) or NULL for the core-Hamiltonian guess;
+ *       exchange scaled by alpha; e_const added to the energy.  Every iteration: F = h1 + veff(D), E = sum h1_energy D +
+ *       1/2 sum veff D + e_const, error X^T (F D S - S D F) X, commutator DIIS (Gram row on the device, dmk_diis_coeffs on the
+ *       host, the extrapolated Fock matrix as a device linear combination), dmk_eigh_batched_real (batch = spin), density.  ONE
+ *       record (at most 14 doubles) is read back per iteration.  Converged when |dE| < tol and the orbital-gradient norm
+ *       (|error| / sqrt 2) < tol_grad; after max_iter diagonalisations the last iterate stays.  The orbitals are those of the final
+ *       Fock matrix.  result_host[5]: E, converged (0 | 1), diagonalisations, gradient norm, last dE.
+ *   dmk_scf_get : copy a result to device memory of the caller: density, Fock matrix, veff (nspin, n, n), orbitals (nspin, n, n;
+ *       ROW m = orbital m), orbital energies (nspin, n).
+ *   dmk_scf_veff : veff of any density (nspin, n, n) with the handle's blocks.
+ * flags: DMK_SCF_TWO_PASS builds J and K with two dmk_jk_s4 passes per block instead of dmk_fock_s4. */
+typedef struct dmk_scf dmk_scf;
+enum { DMK_SCF_TWO_PASS = 1 };
+enum { DMK_SCF_DM = 0, DMK_SCF_FOCK = 1, DMK_SCF_VEFF = 2, DMK_SCF_MO_COEFF = 3, DMK_SCF_MO_ENERGY = 4 };
+int dmk_scf_create(dmk_ctx *ctx, int n, int nspin, const double *h1, const double *h1_energy, const double *ovlp, const double *xorth,
+                   int novlp, const double *eri_aa, const double *eri_bb, const double *eri_ab, int64_t ld, int diis_dim, int flags,
+                   dmk_scf **out);
+int dmk_scf_run(dmk_scf *h, const int *nocc_host, const double *dm0, double alpha, double e_const, int max_iter, double tol,
+                double tol_grad, int use_diis, double *result_host /*[5]*/);
+int dmk_scf_get(dmk_scf *h, int what, double *out);
+int dmk_scf_veff(dmk_scf *h, const double *dm, double alpha, double *veff_out);
+int dmk_scf_free(dmk_scf *h);
+
 /* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
  * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the
  * indicator of the nimp impurity indices imp_idx_host (host int32, inside [0, n), no repeats; nimp = 0 is legal):

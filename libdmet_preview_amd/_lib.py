@@ -136,7 +136,15 @@ PROTOTYPES = {
     "dmk_jk_s4": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmk_jk_s4_rows": (c_int, [c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmk_eri_to_s4": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
-    "dmk_dmet_h2_scaled": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
+    "dmk_fock_s4": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "dmk_fock_s4_rows": (c_int, [c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmk_diis_coeffs": (c_int, [c_int, c_vp, c_vp]),
+    "dmk_scf_create": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_int, P(c_vp)]),
+    "dmk_scf_run": (c_int, [c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int, c_dbl, c_dbl, c_int, c_vp]),
+    "dmk_scf_get": (c_int, [c_vp, c_int, c_vp]),
+    "dmk_scf_veff": (c_int, [c_vp, c_vp, c_dbl, c_vp]),
+    "dmk_scf_free": (c_int, [c_vp]),
+    "dmk_dmet_h2_scaled":(c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
     "dmk_rho_glob": (c_int, [c_vp, _int3, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "dmk_sym_norm_bound": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
     "dmk_modified_cholesky": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_dbl, c_int, c_vp, P(c_int), P(c_int)]),

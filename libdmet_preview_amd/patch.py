@@ -48,6 +48,8 @@ _FUNCTIONS = [
     # J / K on the resident ERI (routine/slater.py:30 imports them by name)
     ("solver.scf", ["solver.scf", "routine.slater"], ["_get_jk", "_get_veff"]),
     ("solver.scf", ["solver.scf", "routine.spinless"], ["_get_veff_ghf"]),          # routine/spinless.py:28 imports it by name
+    # Hartree-Fock without PySCF (solver/scf_solver.py builds its scfsolver as scf.SCF(...), an attribute lookup at call time)
+    ("solver.scf", ["solver.scf"], ["SCF"]),
     # one-body folds (routine/slater.py:35 star-imports slater_helper)
     ("routine.slater_helper", ["routine.slater_helper", "routine.slater"],
      ["transform_trans_inv", "transform_trans_inv_k", "transform_local", "transform_imp", "transform_imp_env",
