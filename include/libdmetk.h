@@ -674,6 +674,42 @@ int dmk_scf_get(dmk_scf *h, int what, double *out);
 int dmk_scf_veff(dmk_scf *h, const double *dm, double alpha, double *veff_out);
 int dmk_scf_free(dmk_scf *h);
 
+/* ---- MO integrals and MP2 (solver/scf.py:71-189, :1245-1264, solver/mp.py:33-95) ----------
+ * Four-index transform of ONE 4-fold packed block (npair x npair, row pitch ld >= npair, the bra pair is the row; the layout of
+ * dmk_fock_s4 / dmk_eri_to_s4), NOT assumed symmetric under bra <-> ket (the alpha-beta block is not):
+ *     out[(i,j)][(k,l)] = sum_pqrs c1[p][i] c2[q][j] eri[pair(p,q)][pair(r,s)] c3[r][k] c4[s][l]
+ * c_m: n x n_m row-major with leading dimension ldc_m >= n_m, COLUMNS are orbitals (a column range of an n x n mo_coeff is passed
+ * by pointer offset); 1 <= n_m <= n <= 512.  out is contiguous row-major, (n1 n2) x (n3 n4).  DMK_AO2MO_PACK_BRA keeps i >= j only,
+ * in pair() order (rows), DMK_AO2MO_PACK_KET k >= l (columns); a flag is valid only when its two matrices are the same pointer with
+ * the same leading dimension and width (otherwise DMK_ERR_INVALID).  Both flags with one matrix give a 4-fold block again.
+ * Two half transforms on v_mfma_f64_16x16x4_f64 whose operand loader expands the packed triangle on the fly; the intermediate lives
+ * in a workspace of at most ws_bytes (0: DMK_AO2MO_WS_DEFAULT) that the call allocates and releases before it returns, and the
+ * work is cut into slabs of k that fit it (each slab yields complete output columns).  The result does not depend on the slabbing,
+ * bit for bit; fixed-order sums, no atomics.  A workspace that cannot hold one k: DMK_ERR_INVALID with the bytes needed in the
+ * message.  Every argument check returns DMK_ERR_INVALID before any launch.  Returns after the stream drained.
+ *   dmk_ao2mo_plan (HOST, no context): plan_host[3] = slabs, bytes of workspace the call would allocate, elements of out. */
+enum { DMK_AO2MO_PACK_BRA = 1, DMK_AO2MO_PACK_KET = 2 };
+#define DMK_AO2MO_WS_DEFAULT ((int64_t)12 << 30)
+int dmk_ao2mo_s4(dmk_ctx *ctx, int n, const double *eri, int64_t ld, const double *c1, int64_t ldc1, int n1, const double *c2,
+                 int64_t ldc2, int n2, const double *c3, int64_t ldc3, int n3, const double *c4, int64_t ldc4, int n4, int flags,
+                 int64_t ws_bytes, double *out);
+int dmk_ao2mo_plan(int n, int n1, int n2, int n3, int n4, int flags, int64_t ws_bytes, int64_t *plan_host /*[3]*/);
+/* MP2 from device (ia|jb) blocks as dmk_ao2mo_s4 writes them (rows (i,a), columns (j,b), unpacked) and device orbital energies:
+ * the correlation energy (*e_corr_dev), the blocks of the unrelaxed one-particle density in the MO basis and, when t2 is not NULL,
+ * the amplitudes in (i, j, a, b) order.  With D = (e_i + e_j) - (e_a + e_b):
+ *   restricted    t = (ia|jb) / D, t~ = 2 t_ij^ab - t_ij^ba, e = sum t~ (ia|jb), X_ij = sum_kab t_ik^ab t~_jk^ab,
+ *                 Y_ab = sum_ijc t_ij^ac t~_ij^bc, doo = 2 - (X + X^T), dvv = Y + Y^T  (spin-traced, trace N)
+ *   unrestricted  t_aa = [(ia|jb) - (ib|ja)] / D (t_bb likewise), t_ab = (ia|JB) / D, e = 1/4 sum t_aa <ij||ab> + 1/4 sum t_bb
+ *                 <IJ||AB> + sum t_ab (ia|JB), doo_a = 1 - 1/2 sum_kab t_aa t_aa - sum_KaB t_ab t_ab, dvv_a = 1/2 sum t_aa t_aa +
+ *                 sum t_ab t_ab, the beta blocks with t_ab contracted over its alpha indices
+ * One fused elementwise kernel per block; the densities are dmk_dgemm_batched products with K cut into slabs along an occupied index
+ * and summed in a fixed order.  No atomics.  nocc, nvir >= 1 (per spin).  The workspace is released before the call returns. */
+int dmk_mp2_rhf(dmk_ctx *ctx, int nocc, int nvir, const double *ovov, const double *e_occ, const double *e_vir, double *e_corr_dev,
+                double *doo, double *dvv, double *t2);
+int dmk_mp2_uhf(dmk_ctx *ctx, int nocc_a, int nvir_a, int nocc_b, int nvir_b, const double *ovov, const double *OVOV, const double *ovOV,
+                const double *e_occ_a, const double *e_vir_a, const double *e_occ_b, const double *e_vir_b, double *e_corr_dev,
+                double *doo_a, double *dvv_a, double *doo_b, double *dvv_b, double *t2aa, double *t2ab, double *t2bb);
+
 /* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
  * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the
  * indicator of the nimp impurity indices imp_idx_host (host int32, inside [0, n), no repeats; nimp = 0 is legal):

@@ -144,6 +144,12 @@ PROTOTYPES = {
     "dmk_scf_get": (c_int, [c_vp, c_int, c_vp]),
     "dmk_scf_veff": (c_int, [c_vp, c_vp, c_dbl, c_vp]),
     "dmk_scf_free": (c_int, [c_vp]),
+    "dmk_ao2mo_s4": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_i64, c_int,
+                             c_int, c_i64, c_vp]),
+    "dmk_ao2mo_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_i64, P(c_i64)]),
+    "dmk_mp2_rhf": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmk_mp2_uhf": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                            c_vp, c_vp, c_vp]),
     "dmk_dmet_h2_scaled":(c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
     "dmk_rho_glob": (c_int, [c_vp, _int3, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "dmk_sym_norm_bound": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),

@@ -50,6 +50,9 @@ _FUNCTIONS = [
     ("solver.scf", ["solver.scf", "routine.spinless"], ["_get_veff_ghf"]),          # routine/spinless.py:28 imports it by name
     # Hartree-Fock without PySCF (solver/scf_solver.py builds its scfsolver as scf.SCF(...), an attribute lookup at call time)
     ("solver.scf", ["solver.scf"], ["SCF"]),
+    # the MO integral transform: the correlated solvers of the reference call these as scf.incore_transform /
+    # scf.ao2mo_Ham, attribute lookups at call time
+    ("solver.scf", ["solver.scf"], ["incore_transform", "ao2mo_Ham"]),
     # one-body folds (routine/slater.py:35 star-imports slater_helper)
     ("routine.slater_helper", ["routine.slater_helper", "routine.slater"],
      ["transform_trans_inv", "transform_trans_inv_k", "transform_local", "transform_imp", "transform_imp_env",

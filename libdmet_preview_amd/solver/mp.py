@@ -1,0 +1,201 @@
+"""
+Second-order Moller-Plesset on the device, over the Hartree-Fock object of solver/scf.py (DeviceHF):
+
+  MP2      restricted   (PySCF's mp.MP2 as SCF.MP2 of the reference uses it, solver/scf.py:1245-1264)
+  UIMP2    unrestricted (solver/mp.py:33-95)
+  run_mp2  (E, rdm1) with the return conventions of the reference's SCF.MP2
+
+The (ia|jb) blocks come from dmk_ao2mo_s4 applied to the ERI blocks the DeviceHF already holds -- the ERI is not
+uploaded again -- and amplitudes, energy and the unrelaxed density from dmk_mp2_rhf / dmk_mp2_uhf (K20).  Not built: frozen orbitals,
+generalised or Bogoliubov references, and non-canonical orbitals without their orbital energies (PySCF iterates the amplitudes
+there).  The module imports without a GPU.
+"""
+import numpy as np
+
+from libdmet_preview_amd._lib import lib, c_vp
+from libdmet_preview_amd.solver import scf
+from libdmet_preview_amd.utils import logger as log
+
+
+class _ERIS(object):
+    """What ao2mo() hands back: the (ia|jb) blocks as device arrays, rows (i, a), columns (j, b)."""
+    ovov = OVOV = ovOV = None
+
+
+def _check_frozen(frozen):
+    if not (frozen is None or (np.isscalar(frozen) and frozen == 0)):
+        raise NotImplementedError("MP2 with frozen orbitals (frozen = %r) is not built" % (frozen,))
+
+
+class _MP2Base(object):
+    _restricted = True
+
+    def __init__(self, mf, frozen=None, mo_coeff=None, mo_occ=None):
+        _check_frozen(frozen)
+        if not isinstance(mf, scf.DeviceHF):
+            raise NotImplementedError("%s needs the device Hartree-Fock object (solver.scf.DeviceHF), got %s; generalised and "
+                                      "Bogoliubov references are not built" % (type(self).__name__, type(mf).__name__))
+        if mf._restricted != self._restricted:
+            raise NotImplementedError("%s over %s Hartree-Fock object" % (type(self).__name__,
+                                                                          "a restricted" if mf._restricted else "an unrestricted"))
+        self._scf, self.frozen = mf, frozen
+        self.mo_coeff = mf.mo_coeff if mo_coeff is None else mo_coeff
+        self.mo_occ = mf.mo_occ if mo_occ is None else mo_occ
+        if self.mo_coeff is None or self.mo_occ is None:
+            raise ValueError("%s: the Hartree-Fock object has no orbitals yet (run its kernel first)" % type(self).__name__)
+        self.mo_energy = None
+        self.e_corr = self.t2 = None
+        self._doo = self._dvv = None
+        self._set_orbitals(self.mo_coeff)
+
+    # ---- orbitals ------------------------------------------------------------------------------------------------------------------
+    def _spins(self, a):
+        a = np.asarray(a, dtype=np.float64)
+        return a[None] if self._restricted else a
+
+    def _set_orbitals(self, mo_coeff):
+        n = self._scf._n
+        c, occ = self._spins(mo_coeff), self._spins(self.mo_occ)
+        ns = 1 if self._restricted else 2
+        if c.shape != (ns, n, n) or occ.shape != (ns, n):
+            raise ValueError("mo_coeff %s / mo_occ %s do not fit %d spin channel(s) of %d orbitals" % (c.shape, occ.shape, ns, n))
+        # [occupied | virtual] column order of every spin: the blocks of the transform are column ranges of one matrix
+        self._order = [np.concatenate([np.flatnonzero(occ[s] > 0), np.flatnonzero(occ[s] <= 0)]) for s in range(ns)]
+        self._nocc = [int(np.count_nonzero(occ[s] > 0)) for s in range(ns)]
+        if any(o < 1 or o >= n for o in self._nocc):
+            raise ValueError("MP2 needs occupied and virtual orbitals in every spin channel (nocc = %s of %d)" % (self._nocc, n))
+        self._c = c
+
+    @property
+    def nmo(self):
+        return self._scf._n if self._restricted else (self._scf._n, self._scf._n)
+
+    @property
+    def nocc(self):
+        return self._nocc[0] if self._restricted else tuple(self._nocc)
+
+    @property
+    def e_tot(self):
+        return self._scf.e_tot + (self.e_corr or 0.0)
+
+    def _dev_coeff(self):
+        ctx = self._scf._ctx
+        return [ctx.to_device(self._c[s][:, self._order[s]]) for s in range(len(self._c))]
+
+    def _energies(self, mo_energy, custom_coeff):
+        if mo_energy is None:
+            if custom_coeff or self.mo_coeff is not self._scf.mo_coeff:
+                raise NotImplementedError("orbitals other than the Hartree-Fock object's own need their mo_energy (non-canonical "
+                                          "orbitals, whose amplitudes PySCF iterates, are not built)")
+            if not self._scf.converged:
+                raise NotImplementedError("the Hartree-Fock calculation has not converged: give mo_energy explicitly (PySCF would "
+                                          "iterate the amplitudes)")
+            mo_energy = self._scf.mo_energy
+        e = self._spins(mo_energy)
+        if e.shape != (len(self._c), self._scf._n):
+            raise ValueError("mo_energy of shape %s" % (e.shape,))
+        return e
+
+    # ---- the integrals ------------------------------------------------------------------------------------------------------------
+    def ao2mo(self, mo_coeff=None):
+        if mo_coeff is not None:
+            self._set_orbitals(mo_coeff)
+        mf = self._scf
+        ctx, n, ld = mf._ctx, mf._n, mf._ld
+        d_c = self._dev_coeff()
+        rng = lambda s: ((d_c[s], 0, self._nocc[s]), (d_c[s], self._nocc[s], n - self._nocc[s]))
+        eris = _ERIS()
+        oa, va = rng(0)
+        eris.ovov = scf.ao2mo_block_dev(ctx, n, mf._blocks[0], (oa, va, oa, va), ld=ld)
+        if not self._restricted:
+            ob, vb = rng(1)
+            eris.OVOV = scf.ao2mo_block_dev(ctx, n, mf._blocks[1], (ob, vb, ob, vb), ld=ld)
+            eris.ovOV = scf.ao2mo_block_dev(ctx, n, mf._blocks[2], (oa, va, ob, vb), ld=ld)
+        return eris
+
+    # ---- the density ----------------------------------------------------------------------------------------------------------------
+    def _rdm1_mo(self, s):
+        n, o = self._scf._n, self._nocc[s]
+        d = np.zeros((n, n))
+        d[:o, :o], d[o:, o:] = self._doo[s], self._dvv[s]
+        out = np.empty((n, n))
+        out[np.ix_(self._order[s], self._order[s])] = d          # back to the column order of mo_coeff
+        return out
+
+    def make_rdm1(self, ao_repr=False):
+        """The unrelaxed MP2 one-particle density: in the MO basis (the order of mo_coeff), or C D C^T with ao_repr=True.  Restricted:
+        spin-traced (n, n); unrestricted: (2, n, n)."""
+        if self._doo is None:
+            self.kernel(with_t2=False)
+        dm = [self._rdm1_mo(s) for s in range(len(self._c))]
+        if ao_repr:
+            dm = [self._c[s] @ dm[s] @ self._c[s].T for s in range(len(dm))]
+        return dm[0] if self._restricted else np.asarray(dm)
+
+
+class MP2(_MP2Base):
+    _restricted = True
+
+    def kernel(self, mo_energy=None, mo_coeff=None, with_t2=True):
+        """-> (e_corr, t2): t2 (nocc, nocc, nvir, nvir) on the host, None with with_t2=False."""
+        e = self._energies(mo_energy, mo_coeff is not None)
+        eris = self.ao2mo(mo_coeff)
+        mf = self._scf
+        ctx, n, o = mf._ctx, mf._n, self._nocc[0]
+        v = n - o
+        d_e = ctx.to_device(e[0][self._order[0]])
+        d_ec, d_oo, d_vv = ctx.empty((1,), np.float64), ctx.empty((o, o), np.float64), ctx.empty((v, v), np.float64)
+        d_t2 = ctx.empty((o, o, v, v), np.float64) if with_t2 else None
+        ctx.check(lib.dmk_mp2_rhf(ctx.h, o, v, eris.ovov.ptr, d_e.ptr, c_vp(d_e.address + 8 * o), d_ec.ptr, d_oo.ptr, d_vv.ptr,
+                                  d_t2.ptr if with_t2 else None))
+        self.mo_energy = mo_energy if mo_energy is not None else mf.mo_energy
+        self.e_corr = float(d_ec.get()[0])
+        self._doo, self._dvv = [d_oo.get()], [d_vv.get()]
+        self.t2 = d_t2.get() if with_t2 else None
+        return self.e_corr, self.t2
+
+
+class UIMP2(_MP2Base):
+    _restricted = False
+
+    def kernel(self, mo_energy=None, mo_coeff=None, with_t2=True):
+        """-> (e_corr, t2): t2 = (t2aa, t2ab, t2bb) on the host in (i, j, a, b) order, None with with_t2=False."""
+        e = self._energies(mo_energy, mo_coeff is not None)
+        eris = self.ao2mo(mo_coeff)
+        mf = self._scf
+        ctx, n = mf._ctx, mf._n
+        (oa, ob), (va, vb) = self._nocc, [n - x for x in self._nocc]
+        d_e = [ctx.to_device(e[s][self._order[s]]) for s in range(2)]
+        vir = lambda s: c_vp(d_e[s].address + 8 * self._nocc[s])
+        d_ec = ctx.empty((1,), np.float64)
+        d_d = [ctx.empty(sh, np.float64) for sh in ((oa, oa), (va, va), (ob, ob), (vb, vb))]
+        d_t = [ctx.empty(sh, np.float64) for sh in ((oa, oa, va, va), (oa, ob, va, vb), (ob, ob, vb, vb))] if with_t2 else [None] * 3
+        p = lambda a: a.ptr if a is not None else None
+        ctx.check(lib.dmk_mp2_uhf(ctx.h, oa, va, ob, vb, eris.ovov.ptr, eris.OVOV.ptr, eris.ovOV.ptr, d_e[0].ptr, vir(0), d_e[1].ptr,
+                                  vir(1), d_ec.ptr, d_d[0].ptr, d_d[1].ptr, d_d[2].ptr, d_d[3].ptr, p(d_t[0]), p(d_t[1]), p(d_t[2])))
+        self.mo_energy = mo_energy if mo_energy is not None else mf.mo_energy
+        self.e_corr = float(d_ec.get()[0])
+        self._doo, self._dvv = [d_d[0].get(), d_d[2].get()], [d_d[1].get(), d_d[3].get()]
+        self.t2 = tuple(t.get() for t in d_t) if with_t2 else None
+        return self.e_corr, self.t2
+
+
+def run_mp2(scfsolver, mo_energy=None, mo_coeff=None, mo_occ=None, frozen=None):
+    """SCF.MP2 of the reference (solver/scf.py:1245-1264) over a solver.scf.SCF whose HF() has run: -> (E, rdm1) with E the
+    CORRELATION energy that mp.kernel() returns and rdm1 the density in the AO representation -- rdm1[None] * 0.5 restricted,
+    (2, n, n) unrestricted.  The solver's `.mp` holds the MP2 object afterwards."""
+    if not scfsolver.doneHF:
+        log.warn("running HF first with default settings")
+        scfsolver.HF()
+    log.check(scfsolver.mf.converged, "Hartree-Fock calculation has not converged")
+    if scfsolver.spinRestricted:
+        log.result("Restricted MP2 on the device")
+        scfsolver.mp = MP2(scfsolver.mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+    else:
+        log.result("Unrestricted MP2 on the device")
+        scfsolver.mp = UIMP2(scfsolver.mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+    E, _ = scfsolver.mp.kernel(mo_energy=mo_energy, mo_coeff=mo_coeff, with_t2=False)
+    rdm1 = scfsolver.mp.make_rdm1(ao_repr=True)
+    if scfsolver.spinRestricted:
+        rdm1 = rdm1[None] * 0.5          # NOTE the 0.5 factor and additional dim
+    return E, rdm1

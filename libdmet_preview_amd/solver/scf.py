@@ -4,6 +4,9 @@ The ERI x density piece of libdmet/solver/scf.py on the MI355X:
   _get_jk     solver/scf.py:255-335   (RHF / UHF / UIHF; pyscf hf.dot_eri_dm -> dmk_jk_s4)
   _get_veff   solver/scf.py:337-352
   SCF         solver/scf.py:883-1304  (the Hartree-Fock part: HF, get_mo, get_mo_energy; `.mf` = DeviceHF)
+  regularize_coeff, incore_transform, ao2mo_Ham   solver/scf.py:51-189  (pyscf ao2mo -> dmk_ao2mo_s4)
+
+MP2 on top of a finished SCF is solver.mp.run_mp2(scfsolver) (solver/mp.py); SCF.MP2 itself still raises.
 
 The embedding ERI is streamed from HBM in its 4-fold packed form, once for J (both directions of the
 alpha-beta block in the same pass) and once for K; 1-fold / 8-fold inputs are gathered into the 4-fold
@@ -124,6 +127,182 @@ def _get_veff_ghf(dm, eri):
 
 
 # *********************************************************************
+# MO integral transform on the device: DESIGN.md K19
+# *********************************************************************
+
+_AO2MO_PACK_BRA, _AO2MO_PACK_KET = 1, 2
+
+
+def regularize_coeff(mo_coeffs):
+    """Four sets of MO coefficients -> ([c0, c1, c2, c3], spin): every entry a 2-d array (spin 1; a one-element list is unwrapped)
+    or a pair of them [c_alpha, c_beta] (spin 2); `spin` is that of the last entry, as in the reference (solver/scf.py:51-69)."""
+    out, spin = [], 1
+    for mo in mo_coeffs:
+        if isinstance(mo, np.ndarray) and mo.ndim == 2:
+            out.append(mo)
+            spin = 1
+        else:
+            spin = len(mo)
+            out.append(mo[0] if spin == 1 else mo)
+    return out, spin
+
+
+def _col_range(c):
+    """(DevArray of a row-major (n, ncols) matrix, first column, width) from that triple or from a bare DevArray (all columns)."""
+    if isinstance(c, tuple):
+        d, c0, w = c
+        return d, int(c0), int(w)
+    return c, 0, int(c.shape[-1])
+
+
+def ao2mo_block_dev(ctx, n, d_eri, coeffs, compact=False, ld=None, ws_bytes=0):
+    """One 4-fold device block through dmk_ao2mo_s4: `coeffs` are four column ranges (DevArray (n, ncols), first column, width) or
+    bare DevArrays.  compact=True packs a pair index whose two ranges are the same range of the same array.  Returns the DevArray
+    (rows (i, j), columns (k, l)); nothing crosses to the host."""
+    npair = n * (n + 1) // 2
+    cs = [_col_range(c) for c in coeffs]
+    for d, c0, w in cs:
+        if d.shape[-2] != n or c0 < 0 or w < 1 or c0 + w > d.shape[-1]:
+            raise ValueError("ao2mo: a coefficient range [%d, %d) of a %s matrix for n = %d" % (c0, c0 + w, d.shape, n))
+    same = lambda a, b: a[0].address == b[0].address and a[0].shape[-1] == b[0].shape[-1] and a[1:] == b[1:]
+    flags = 0
+    if compact and same(cs[0], cs[1]):
+        flags |= _AO2MO_PACK_BRA
+    if compact and same(cs[2], cs[3]):
+        flags |= _AO2MO_PACK_KET
+    w = [c[2] for c in cs]
+    rows = w[0] * (w[0] + 1) // 2 if flags & _AO2MO_PACK_BRA else w[0] * w[1]
+    cols = w[2] * (w[2] + 1) // 2 if flags & _AO2MO_PACK_KET else w[2] * w[3]
+    out = ctx.empty((rows, cols), np.float64)
+    args = []
+    for d, c0, wd in cs:
+        args += [c_vp(d.address + 8 * c0), int(d.shape[-1]), wd]
+    ctx.check(lib.dmk_ao2mo_s4(ctx.h, int(n), d_eri.ptr, int(ld or npair), *(args + [flags, int(ws_bytes), out.ptr])))
+    return out
+
+
+def _same_coeff(a, b):
+    return a is b or (a.shape == b.shape and np.array_equal(a, b))
+
+
+def _upload_coeffs(ctx, cs):
+    """Host coefficient matrices -> DevArrays; matrices that are the same array (or equal) share one upload, and with it one pointer."""
+    seen, out = [], []
+    for c in cs:
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        for h, d in seen:
+            if _same_coeff(h, c):
+                out.append(d)
+                break
+        else:
+            d = ctx.to_device(c)
+            seen.append((c, d))
+            out.append(d)
+    return out
+
+
+def _spin_blocks_to_dev(ctx, eri, nao):
+    """ERI (s1 / s4 / s8, with or without a spin axis) -> list of 4-fold device blocks (one per entry of the spin axis)."""
+    eri = np.asarray(eri, dtype=np.double)
+    fmt, spin_dim = integral.get_eri_format(eri, nao)
+    if spin_dim == 0:
+        eri = eri[None]
+    return [_block_to_dev_s4(ctx, blk, fmt, nao) for blk in eri]
+
+
+def incore_transform_dev(ctx, n, blocks, c, compact=False, ld=None, ws_bytes=0):
+    """incore_transform over device arrays: `blocks` the 4-fold DevArrays (one, or aa, bb, ab), `c` four DevArrays / column ranges or
+    four [alpha, beta] pairs of them.  Returns the list of transformed DevArrays (one, or aa, bb, ab)."""
+    log.eassert(len(c) == 4, "Need 4 coefficents for transformation.")
+    spin_resolved = isinstance(c[-1], (list,)) and len(c[-1]) == 2
+    if not spin_resolved:
+        c = [x[0] if isinstance(x, list) else x for x in c]
+        log.eassert(len(blocks) == 1, "a spin-independent transform takes one ERI block, got %d", len(blocks))
+        return [ao2mo_block_dev(ctx, n, blocks[0], c, compact, ld, ws_bytes)]
+    log.eassert(len(blocks) in (1, 3), "spin-resolved coefficients take one ERI block or (aa, bb, ab), got %d", len(blocks))
+    b = list(blocks) * 3 if len(blocks) == 1 else blocks
+    pick = lambda spins: [c[m][s] for m, s in enumerate(spins)]
+    return [ao2mo_block_dev(ctx, n, b[0], pick((0, 0, 0, 0)), compact, ld, ws_bytes),
+            ao2mo_block_dev(ctx, n, b[1], pick((1, 1, 1, 1)), compact, ld, ws_bytes),
+            ao2mo_block_dev(ctx, n, b[2], pick((0, 0, 1, 1)), compact, ld, ws_bytes)]
+
+
+def incore_transform(eri, c, compact=False):
+    """Two-electron integral transformation (solver/scf.py:71-119) on the device: c is a tuple of four coefficient sets, each a
+    2-d array or [alpha, beta]; eri s1 / s4 / s8 with or without a spin axis.  The result always has a spin axis: (1, ., .) or
+    (aa, bb, ab) with the ab block transformed by (C_a, C_a, C_b, C_b).  compact=True packs a pair index whose two coefficient
+    matrices are the same array."""
+    log.eassert(len(c) == 4, "Need 4 coefficents for transformation.")
+    c, spin = regularize_coeff(c)
+    if spin == 1:
+        nao = c[0].shape[-2]
+        _, spin_dim = integral.get_eri_format(np.asarray(eri), nao)
+        if spin_dim > 1 or spin_dim < 0:
+            raise ValueError("a spin-independent transform of an ERI with a spin axis of %d" % spin_dim)
+        ctx = get_ctx()
+        out = incore_transform_dev(ctx, nao, _spin_blocks_to_dev(ctx, eri, nao), _upload_coeffs(ctx, c), compact)
+        return out[0].get()[np.newaxis]
+    elif spin == 2:
+        nao = c[0][0].shape[-2]
+        _, spin_dim = integral.get_eri_format(np.asarray(eri), nao)
+        if spin_dim not in (0, 1, 3):
+            raise ValueError("a spin-resolved transform of an ERI with a spin axis of %d" % spin_dim)
+        ctx = get_ctx()
+        flat = _upload_coeffs(ctx, [c[m][s] for m in range(4) for s in range(2)])
+        d_c = [[flat[2 * m], flat[2 * m + 1]] for m in range(4)]
+        out = incore_transform_dev(ctx, nao, _spin_blocks_to_dev(ctx, eri, nao), d_c, compact)
+        return np.asarray([o.get() for o in out])
+    raise ValueError("Incorrect spin dimension (%s) of mo_coeff." % spin)
+
+
+def ao2mo_Ham_dev(ctx, norb, d_h1, blocks, d_C, compact=True, ld=None, ws_bytes=0):
+    """ao2mo_Ham over device arrays, in the spirit of set_integral_dev: d_h1 (s1, norb, norb), `blocks` the 4-fold DevArrays (one, or
+    aa, bb, ab), d_C (s, norb, norb) with s = 1 (restricted) or 2.  Returns (d_h1_mo (s, norb, norb), [transformed blocks]): one block
+    for s = 1, (aa, bb, ab) for s = 2; nothing crosses to the host."""
+    ns, nn = int(d_C.shape[0]), norb * norb
+    d_t, d_out = ctx.empty((ns, norb, norb), np.float64), ctx.empty((ns, norb, norb), np.float64)
+    sh = nn if d_h1.shape[0] == ns and ns > 1 else 0
+    ctx.check(lib.dmk_dgemm_batched(ctx.h, 0, 0, norb, norb, norb, ns, 1.0, d_h1.ptr, norb, sh, d_C.ptr, norb, nn, 0.0, d_t.ptr, norb, nn))
+    ctx.check(lib.dmk_dgemm_batched(ctx.h, 1, 0, norb, norb, norb, ns, 1.0, d_C.ptr, norb, nn, d_t.ptr, norb, nn, 0.0, d_out.ptr, norb, nn))
+    cs = [d_C.offset(s * nn, (norb, norb)) for s in range(ns)]
+    if ns == 1:
+        return d_out, [ao2mo_block_dev(ctx, norb, blocks[0], [cs[0]] * 4, compact, ld, ws_bytes)]
+    return d_out, incore_transform_dev(ctx, norb, blocks, [[cs[0], cs[1]]] * 4, compact, ld, ws_bytes)
+
+
+def ao2mo_Ham(Ham, C, compact=True, in_place=False):
+    """The Hamiltonian in the MO basis C (solver/scf.py:121-189): H1 -> C^T H1 C, the ERI through dmk_ao2mo_s4 -- 4-fold (compact) or
+    (spin, norb, norb, norb, norb).  Restricted: C (norb, norb) or (1, norb, norb); unrestricted: C (2, norb, norb), an ERI of one
+    spin block serves aa, bb and ab."""
+    norb = Ham.norb
+    if Ham.bogoliubov:
+        raise NotImplementedError("ao2mo_Ham: Bogoliubov Hamiltonians are not built")
+    C_ = np.asarray(C, dtype=np.float64)
+    if C_.ndim == 2:
+        C_ = C_[np.newaxis]
+    H1 = np.asarray(Ham.H1["cd"], dtype=np.float64)
+    ctx = get_ctx()
+    blocks = _spin_blocks_to_dev(ctx, Ham.H2["ccdd"], norb)
+    if Ham.restricted:
+        C_ = C_[:1]
+        blocks = blocks[:1]
+    else:
+        log.eassert(C_.ndim == 3 and C_.shape[0] == 2, "unrestricted ao2mo_Ham needs C of shape (2, norb, norb)")
+        if len(blocks) not in (1, 3):
+            raise ValueError("ao2mo_Ham: an ERI with a spin axis of %d" % len(blocks))
+    d_h1, d_eri = ao2mo_Ham_dev(ctx, norb, ctx.to_device(H1), blocks, ctx.to_device(C_), compact)
+    h1e = d_h1.get()
+    eri = np.asarray([b.get() for b in d_eri])
+    if not compact:
+        eri = eri.reshape((-1, norb, norb, norb, norb))
+    if in_place:
+        Ham.H1["cd"] = h1e
+        Ham.H2["ccdd"] = eri
+        return Ham
+    return integral.Integral(norb, Ham.restricted, Ham.bogoliubov, Ham.H0, {"cd": h1e}, {"ccdd": eri})
+
+
+# *********************************************************************
 # Hartree-Fock on the device (RHF, UHF, UIHF): DESIGN.md K18
 # *********************************************************************
 
@@ -178,6 +357,7 @@ class DeviceHF(object):
         self.mo_coeff = self.mo_energy = self.mo_occ = None
         self.converged, self.e_tot, self.cycles = False, 0.0, 0
         self._blocks = blocks                       # borrowed DevArrays: kept alive here, never freed by the handle
+        self._ld = int(ld)                          # their row pitch (solver/mp.py reads the blocks in place)
         self._run = (None, None, None)
         n, ns = self._n, self._ns
         novlp, d_S, d_X = 0, None, None
@@ -440,10 +620,10 @@ class SCF(object):
         raise NotImplementedError("GGHF: the generalised mean field of the solver layer is not built")
 
     def MP2(self, *args, **kwargs):
-        raise NotImplementedError("MP2: post-HF needs an MO transform, which is not built")
+        raise NotImplementedError("MP2 is not wired into SCF: call solver.mp.run_mp2(scfsolver) (DESIGN.md K19, K20)")
 
     def GMP2(self, *args, **kwargs):
-        raise NotImplementedError("GMP2: post-HF needs an MO transform, which is not built")
+        raise NotImplementedError("GMP2: generalised references are not built (restricted / unrestricted MP2: solver.mp.run_mp2)")
 
     def get_mo(self):
         log.eassert(self.doneHF, "Hartree-Fock calculation is not done")

@@ -6,8 +6,8 @@ Hartree-Fock of solver/scf.py.
   run_dmet_ham   :353-421  (the energy of the HF state on a scaled DMET Hamiltonian)
   make_rdm1 / 2  :423-490
 
-Post-HF (MP2, OO-MP2, OO-CCD), GHF and BCS are not built: they raise NotImplementedError when asked for.  The module imports without
-a GPU; the device context is created by the first call that computes.
+OO-MP2, OO-CCD, GHF and BCS are not built, and SCFSolver(mp2=True) is not wired: they raise NotImplementedError when asked for.  MP2 on
+a finished run is solver.mp.run_mp2(solver.scfsolver).  The module imports without a GPU; the device context is created by the first call that computes.
 """
 import numpy as np
 
@@ -22,7 +22,8 @@ class SCFSolver(object):
                  beta=np.inf, conv_tol_grad=None, verbose=4, **kwargs):
         for name, on in (("mp2", mp2), ("oomp2", oomp2), ("ooccd", ooccd), ("ghf", ghf), ("bcs", bcs)):
             if on:
-                raise NotImplementedError("SCFSolver(%s=True): only the plain Hartree-Fock branch is built" % name)
+                raise NotImplementedError("SCFSolver(%s=True): only the plain Hartree-Fock branch is built%s" % (
+                    name, " (MP2 of a finished run: solver.mp.run_mp2(solver.scfsolver))" if name == "mp2" else ""))
         self.restricted, self.Sz = restricted, Sz
         self.conv_tol, self.conv_tol_grad, self.max_cycle, self.max_memory = tol, conv_tol_grad, max_cycle, max_memory
         self.alpha, self.beta = alpha, beta
