@@ -161,7 +161,6 @@ __global__ __launch_bounds__(NT) void ao2mo_transpose_kernel(long long rows, lon
 }
 
 long long pair_of(long long k) { return k * (k + 1) / 2; }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 template <int GATHER, int TD>
 int gemm_launch(dmk_ctx *ctx, const Ao2moGemm &g) {
@@ -253,15 +252,15 @@ int64_t make_plan(int n, int n1, int n2, int n3, int n4, int flags, int64_t ws_b
     const long long t_min = (long long)n * std::max(std::max(n1, n2), std::max(n3, n4));      // one row
     const long long per_col = (std::max(p.npair, p.nij) + p.npair) * 8;
     const long long widest = p.pack_ket ? n3 : n4;                                            // columns of the slab k = n3 - 1 alone
-    const int64_t least = (int64_t)align256((size_t)t_min * 8) + 512 + widest * per_col;
+    const int64_t least = (int64_t)dmk_align256((size_t)t_min * 8) + 512 + widest * per_col;
     if (budget < least) return least;
     p.t_doubles = std::max<long long>(t_min, std::min<int64_t>(T_BYTES_MAX, budget / 4) / 8);
     const long long t_need = std::min<long long>(p.t_doubles, std::max(p.npair, p.nkl) * t_min);   // never more than every row at once
     p.t_doubles = std::max(t_min, t_need);
-    p.col_cap = (budget - (int64_t)align256((size_t)p.t_doubles * 8) - 512) / per_col;
+    p.col_cap = (budget - (int64_t)dmk_align256((size_t)p.t_doubles * 8) - 512) / per_col;
     if (p.col_cap < widest) {           // the intermediate gives way to the slab
         p.t_doubles = t_min;
-        p.col_cap = (budget - (int64_t)align256((size_t)p.t_doubles * 8) - 512) / per_col;
+        p.col_cap = (budget - (int64_t)dmk_align256((size_t)p.t_doubles * 8) - 512) / per_col;
     }
     p.k_edges.assign(1, 0);
     long long most = 0;
@@ -274,8 +273,8 @@ int64_t make_plan(int n, int n1, int n2, int n3, int n4, int flags, int64_t ws_b
     }
     p.nslab = (int)p.k_edges.size() - 1;
     p.col_cap = most;
-    p.bytes = (int64_t)align256((size_t)p.t_doubles * 8) + (int64_t)align256((size_t)(std::max(p.npair, p.nij) * most) * 8) +
-              (int64_t)align256((size_t)(p.npair * most) * 8);
+    p.bytes = (int64_t)dmk_align256((size_t)p.t_doubles * 8) + (int64_t)dmk_align256((size_t)(std::max(p.npair, p.nij) * most) * 8) +
+              (int64_t)dmk_align256((size_t)(p.npair * most) * 8);
     return 0;
 }
 
@@ -330,8 +329,8 @@ int dmk_ao2mo_s4(dmk_ctx *ctx, int n, const double *eri, int64_t ld, const doubl
     StreamDrain drain{ctx->stream};
     char *base = ws.get<char>();
     double *T = reinterpret_cast<double *>(base);
-    double *bufA = reinterpret_cast<double *>(base + align256((size_t)p.t_doubles * 8));
-    double *bufB = reinterpret_cast<double *>(reinterpret_cast<char *>(bufA) + align256((size_t)(std::max(p.npair, p.nij) * p.col_cap) * 8));
+    double *bufA = reinterpret_cast<double *>(base + dmk_align256((size_t)p.t_doubles * 8));
+    double *bufB = reinterpret_cast<double *>(reinterpret_cast<char *>(bufA) + dmk_align256((size_t)(std::max(p.npair, p.nij) * p.col_cap) * 8));
     long long col0 = 0;
     for (int s = 0; s < p.nslab; ++s) {
         const int k0 = p.k_edges[s], k1 = p.k_edges[s + 1];

@@ -737,11 +737,9 @@ __global__ void restore_4to1_kernel(int n, const double *__restrict__ e4, double
 __global__ void restore_4to8_kernel(long long npair, const double *__restrict__ e4, double *__restrict__ out) {
     const long long total = npair * (npair + 1) / 2;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        long long p = (long long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while (p * (p + 1) / 2 > t) --p;
-        while ((p + 1) * (p + 2) / 2 <= t) ++p;
-        const long long q = t - p * (p + 1) / 2;
-        out[t] = e4[p * npair + q];
+        int p, q;
+        dmk_tril_rc(t, p, q);
+        out[t] = e4[(long long)p * npair + q];
     }
 }
 

@@ -1,6 +1,7 @@
 // Shared internals of libdmetk (not part of the public ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -114,6 +115,18 @@ struct RfWorkspace {
 };
 int rf_workspace(dmk_ctx *ctx, int n, int batch, RfWorkspace *W);
 int dmk_scratch2(dmk_ctx *ctx, size_t bytes, void **out);
+
+inline size_t dmk_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// grid of a grid-stride loop over N elements, 256 threads per workgroup, at most `cap` workgroups
+inline int dmk_grid1d(long long N, int cap) { return (int)std::min<long long>((N + 255) / 256, cap); }
+
+// inverse of the packed lower-triangle index: t = k (k + 1) / 2 + l, k >= l
+__device__ __forceinline__ void dmk_tril_rc(long long t, int &k, int &l) {
+    k = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((long long)(k + 1) * (k + 2) / 2 <= t) ++k;
+    while ((long long)k * (k + 1) / 2 > t) --k;
+    l = (int)(t - (long long)k * (k + 1) / 2);
+}
 
 // XCD-aware, bijective remap of a 1-D block id: blocks that the dispatcher places on the
 // same XCD (id % 8) receive a contiguous range of logical ids, so that neighbouring tiles
@@ -252,6 +265,13 @@ __device__ double dmk_wave_sum(double v);
 #endif
 
 // ---- launchers implemented in the .hip files ---------------------------------------------
+
+// fit.hip: tril[b][pair(k,l)] = full[b][k][l] + full[b][l][k] (k > l), full[b][k][k]; full[b][i][j] = tril[b][pair(max, min)]
+// (+ add_tril); each is one launch timed under the family `fam`
+int launch_sym_fold(dmk_ctx *ctx, int fam, int n, int batch, const double *full, double *tril);
+int launch_sym_unpack(dmk_ctx *ctx, int fam, int n, int batch, const double *tril, const double *add_tril, double *full);
+// fit.hip: y[c] = sum_b part[b][c], b < nblk, c < n, in a fixed order; inside the caller's FamScope
+int launch_partsum(dmk_ctx *ctx, long long n, int nblk, const double *part, double *y);
 
 // C (M x N, ldc) += alpha * X^T Y;  X: K x M (ldx), Y: K x N (ldy)   (dgemm_tn.hip)
 struct DgemmTn {

@@ -533,7 +533,6 @@ __global__ __launch_bounds__(256) void wy_apply_t_kernel(int nbp, int m, const d
         }
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int alloc_or_refuse(dmk_ctx *ctx, void **out, size_t bytes, const char *what, int n) {
     if (dmk_dev_alloc(ctx, out, bytes) != hipSuccess) {
@@ -651,9 +650,9 @@ int vectors(dmk_eighl *h, int m, const int32_t *idx, double *Vt) {
     const int ncl = (int)cl_r0.size();
     // workspace: Z (m n) | Y (n m) | scratch of the inverse iteration (7 n m) | V, Vt panels | G, S, U | tables
     const size_t mn = (size_t)m * n;
-    const size_t b_Z = align256(mn * 8), b_Y = b_Z, b_ws = align256(7 * mn * 8), b_V = align256((size_t)NB * n * 8),
-                 b_G = align256((size_t)NB * NB * 8), b_S = align256((size_t)NB * m * 8), b_dots = align256((size_t)m * 8),
-                 b_int = align256((size_t)m * 4);
+    const size_t b_Z = dmk_align256(mn * 8), b_Y = b_Z, b_ws = dmk_align256(7 * mn * 8), b_V = dmk_align256((size_t)NB * n * 8),
+                 b_G = dmk_align256((size_t)NB * NB * 8), b_S = dmk_align256((size_t)NB * m * 8), b_dots = dmk_align256((size_t)m * 8),
+                 b_int = dmk_align256((size_t)m * 4);
     const size_t total = b_Z + b_Y + b_ws + 2 * b_V + b_G + 2 * b_S + b_dots + 7 * b_int;
     if (total > ctx->scratch_bytes) {
         size_t fr = 0, tot = 0;

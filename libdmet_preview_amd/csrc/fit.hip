@@ -24,13 +24,6 @@ constexpr int CI = 8;             // column iterations per workgroup (gemv2): 20
 
 __device__ __forceinline__ double wave_sum(double v) { return dmk_wave_sum(v); }
 
-__device__ __forceinline__ void tril_rc(long long t, int &k, int &l) {
-    k = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((long long)(k + 1) * (k + 2) / 2 <= t) ++k;
-    while ((long long)k * (k + 1) / 2 > t) --k;
-    l = (int)(t - (long long)k * (k + 1) / 2);
-}
-
 // rowpart[cc][r] = sum_{c in chunk cc} A[r][c] xrow[c];   colpart[rb][c] = sum_{r in block rb} A[r][c] xcol[r]
 __global__ __launch_bounds__(NT) void gemv2_kernel(long long M, long long N, const double *__restrict__ A, long long lda,
                                                    const double *__restrict__ xrow, const double *__restrict__ xcol,
@@ -196,7 +189,7 @@ __global__ void sym_fold_kernel(int n, int batch, const double *__restrict__ ful
          t += (long long)gridDim.x * blockDim.x) {
         const long long b = t / npair;
         int k, l;
-        tril_rc(t % npair, k, l);
+        dmk_tril_rc(t % npair, k, l);
         const double *f = full + b * n * n;
         tril[t] = (k == l) ? f[(long long)k * n + k] : f[(long long)k * n + l] + f[(long long)l * n + k];
     }
@@ -273,7 +266,7 @@ __global__ void dv_dparam_kernel(int nent, int nb, long long ldg, const double *
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < npair;
          t += (long long)gridDim.x * blockDim.x) {
         int p, q;
-        tril_rc(t, p, q);
+        dmk_tril_rc(t, p, q);
         double s = 0.0;
         for (int z = z0; z < z1; ++z)
             s = fma(zv[z], G[((long long)zi[z] * nb + p) * ldg + (long long)zj[z] * nb + q], s);
@@ -319,8 +312,6 @@ __global__ void axpy_kernel(long long n, double alpha, const double *__restrict_
         y[t] = fma(alpha, x[t], y[t]);
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-int grid_for(long long total, int cap = 8192) { return (int)std::min<long long>((total + 255) / 256, cap); }
 
 // ---- fused T = 0 objective of the embedding fit (dmk_fit_objective) --------------------------------------------------------
 // full[b] = unpack(v0[b] + t v1[b] + H1[b]): the ray form of the embedding potential (V_emb is linear in the parameters) and the
@@ -448,6 +439,28 @@ int launch_dgemm_small_nn(dmk_ctx *ctx, int M, int N, int K, int batch, const do
     return DMK_OK;
 }
 
+int launch_sym_fold(dmk_ctx *ctx, int fam, int n, int batch, const double *full, double *tril) {
+    FamScope fs(ctx, fam);
+    hipLaunchKernelGGL(sym_fold_kernel, dim3(dmk_grid1d((long long)n * (n + 1) / 2 * batch, 8192)), dim3(256), 0, ctx->stream, n, batch,
+                       full, tril);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+int launch_sym_unpack(dmk_ctx *ctx, int fam, int n, int batch, const double *tril, const double *add_tril, double *full) {
+    FamScope fs(ctx, fam);
+    hipLaunchKernelGGL(sym_unpack_kernel, dim3(dmk_grid1d((long long)n * n * batch, 8192)), dim3(256), 0, ctx->stream, n, batch, tril,
+                       add_tril, full);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+int launch_partsum(dmk_ctx *ctx, long long n, int nblk, const double *part, double *y) {
+    hipLaunchKernelGGL(partsum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(NT), 0, ctx->stream, n, nblk, part, y);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
 extern "C" {
 
 int dmk_dgemv2(dmk_ctx *ctx, int64_t M, int64_t N, const double *A, int64_t lda, const double *xrow, const double *xcol,
@@ -457,7 +470,7 @@ int dmk_dgemv2(dmk_ctx *ctx, int64_t M, int64_t N, const double *A, int64_t lda,
         return dmk_fail(ctx, DMK_ERR_INVALID, "dgemv2: bad arguments");
     FamScope fs(ctx, DMK_FAM_FIT);
     const int nrb = (int)((M + RB - 1) / RB), ncc = (int)((N + NT * CI - 1) / (NT * CI));
-    const size_t b_row = xrow ? align256((size_t)ncc * M * 8) : 0, b_col = xcol ? align256((size_t)nrb * N * 8) : 0;
+    const size_t b_row = xrow ? dmk_align256((size_t)ncc * M * 8) : 0, b_col = xcol ? dmk_align256((size_t)nrb * N * 8) : 0;
     void *ws = nullptr;
     int rc = dmk_scratch(ctx, b_row + b_col + 256, &ws);
     if (rc) return rc;
@@ -466,11 +479,8 @@ int dmk_dgemv2(dmk_ctx *ctx, int64_t M, int64_t N, const double *A, int64_t lda,
     hipLaunchKernelGGL(gemv2_kernel, dim3(nrb, ncc), dim3(NT), 0, ctx->stream, (long long)M, (long long)N, A, (long long)lda,
                        xrow, xcol, xrow ? rowpart : (double *)nullptr, xcol ? colpart : (double *)nullptr);
     DMK_CHECK_LAUNCH(ctx);
-    if (xrow) hipLaunchKernelGGL(partsum_kernel, dim3((unsigned)((M + 63) / 64)), dim3(NT), 0, ctx->stream, (long long)M, ncc,
-                                 rowpart, yrow);
-    if (xcol) hipLaunchKernelGGL(partsum_kernel, dim3((unsigned)((N + 63) / 64)), dim3(NT), 0, ctx->stream, (long long)N, nrb,
-                                 colpart, ycol);
-    DMK_CHECK_LAUNCH(ctx);
+    if (xrow && (rc = launch_partsum(ctx, M, ncc, rowpart, yrow))) return rc;
+    if (xcol && (rc = launch_partsum(ctx, N, nrb, colpart, ycol))) return rc;
     return DMK_OK;
 }
 
@@ -498,21 +508,13 @@ int dmk_dgemm_batched(dmk_ctx *ctx, int opA, int opB, int M, int N, int K, int b
 int dmk_sym_fold(dmk_ctx *ctx, int n, int batch, const double *full, double *tril) {
     if (!ctx) return DMK_ERR_INVALID;
     if (n <= 0 || batch <= 0 || !full || !tril) return dmk_fail(ctx, DMK_ERR_INVALID, "sym_fold: bad arguments");
-    FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(sym_fold_kernel, dim3(grid_for((long long)n * (n + 1) / 2 * batch)), dim3(256), 0, ctx->stream, n, batch,
-                       full, tril);
-    DMK_CHECK_LAUNCH(ctx);
-    return DMK_OK;
+    return launch_sym_fold(ctx, DMK_FAM_FIT, n, batch, full, tril);
 }
 
 int dmk_sym_unpack(dmk_ctx *ctx, int n, int batch, const double *tril, const double *add_tril, double *full) {
     if (!ctx) return DMK_ERR_INVALID;
     if (n <= 0 || batch <= 0 || !full || !tril) return dmk_fail(ctx, DMK_ERR_INVALID, "sym_unpack: bad arguments");
-    FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(sym_unpack_kernel, dim3(grid_for((long long)n * n * batch)), dim3(256), 0, ctx->stream, n, batch, tril,
-                       add_tril, full);
-    DMK_CHECK_LAUNCH(ctx);
-    return DMK_OK;
+    return launch_sym_unpack(ctx, DMK_FAM_FIT, n, batch, tril, add_tril, full);
 }
 
 int dmk_gather2d_f64(dmk_ctx *ctx, int nrow, int ncol, const int32_t *row_idx, const int32_t *col_idx, const double *in,
@@ -521,7 +523,7 @@ int dmk_gather2d_f64(dmk_ctx *ctx, int nrow, int ncol, const int32_t *row_idx, c
     if (nrow < 0 || ncol < 0 || !in || !out) return dmk_fail(ctx, DMK_ERR_INVALID, "gather2d: bad arguments");
     if (nrow == 0 || ncol == 0) return DMK_OK;
     FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(gather2d_kernel, dim3(grid_for((long long)nrow * ncol)), dim3(256), 0, ctx->stream, nrow, ncol, row_idx,
+    hipLaunchKernelGGL(gather2d_kernel, dim3(dmk_grid1d((long long)nrow * ncol, 8192)), dim3(256), 0, ctx->stream, nrow, ncol, row_idx,
                        col_idx, in, (long long)ld_in, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
@@ -533,7 +535,7 @@ int dmk_ewise_mul(dmk_ctx *ctx, int mode, int64_t nrow, int64_t ncol, const doub
         return dmk_fail(ctx, DMK_ERR_INVALID, "ewise_mul: bad arguments");
     if (nrow == 0 || ncol == 0) return DMK_OK;
     FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(ewise_kernel, dim3(grid_for(nrow * ncol)), dim3(256), 0, ctx->stream, mode, (long long)nrow,
+    hipLaunchKernelGGL(ewise_kernel, dim3(dmk_grid1d(nrow * ncol, 8192)), dim3(256), 0, ctx->stream, mode, (long long)nrow,
                        (long long)ncol, A, B, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
@@ -560,7 +562,7 @@ int dmk_fit_kmat(dmk_ctx *ctx, int n, int batch, const double *ew, const double 
     if (n <= 0 || batch <= 0 || !ew || !K || (beta > 0.0 && !f) || (beta <= 0.0 && (nocc < 0 || nocc > n)))
         return dmk_fail(ctx, DMK_ERR_INVALID, "fit_kmat: bad arguments");
     FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(fit_kmat_kernel, dim3(grid_for((long long)batch * n * n)), dim3(256), 0, ctx->stream, n, batch, ew, f, beta, nocc, K);
+    hipLaunchKernelGGL(fit_kmat_kernel, dim3(dmk_grid1d((long long)batch * n * n, 8192)), dim3(256), 0, ctx->stream, n, batch, ew, f, beta, nocc, K);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -572,7 +574,7 @@ int dmk_scatter2d_add_f64(dmk_ctx *ctx, int m, const int32_t *idx, const double 
         return dmk_fail(ctx, DMK_ERR_INVALID, "scatter2d_add: bad arguments");
     if (m == 0) return DMK_OK;
     FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(scatter2d_kernel, dim3(grid_for((long long)m * m)), dim3(256), 0, ctx->stream, m, idx, src, alpha, dst,
+    hipLaunchKernelGGL(scatter2d_kernel, dim3(dmk_grid1d((long long)m * m, 8192)), dim3(256), 0, ctx->stream, m, idx, src, alpha, dst,
                        (long long)ld_dst, elem_stride);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
@@ -583,7 +585,7 @@ int dmk_axpy_f64(dmk_ctx *ctx, int64_t n, double alpha, const double *x, double 
     if (n < 0 || !x || !y) return dmk_fail(ctx, DMK_ERR_INVALID, "axpy: bad arguments");
     if (n == 0) return DMK_OK;
     FamScope fs(ctx, DMK_FAM_FIT);
-    hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (long long)n, alpha, x, y);
+    hipLaunchKernelGGL(axpy_kernel, dim3(dmk_grid1d(n, 8192)), dim3(256), 0, ctx->stream, (long long)n, alpha, x, y);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -597,7 +599,7 @@ int dmk_vcor_dV_dparam(dmk_ctx *ctx, int nent, int nb, const double *G, int64_t 
     if (nent > 65535) return dmk_fail(ctx, DMK_ERR_INVALID, "vcor_dV_dparam: more than 65535 entries per call");
     FamScope fs(ctx, DMK_FAM_FIT);
     const long long npair = (long long)nb * (nb + 1) / 2;
-    hipLaunchKernelGGL(dv_dparam_kernel, dim3(grid_for(npair, 256), nent), dim3(256), 0, ctx->stream, nent, nb, (long long)ldg, G,
+    hipLaunchKernelGGL(dv_dparam_kernel, dim3(dmk_grid1d(npair, 256), nent), dim3(256), 0, ctx->stream, nent, nb, (long long)ldg, G,
                        nz_ptr, nz_i, nz_j, nz_val, dV, reinterpret_cast<const long long *>(out_off));
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
@@ -635,7 +637,7 @@ int dmk_fit_objective(dmk_ctx *ctx, const dmk_fit_args *a, double *f2, int *stat
     }
     {
         FamScope fs(ctx, DMK_FAM_FIT);
-        hipLaunchKernelGGL(fit_ray_unpack_kernel, dim3(grid_for((long long)nb * nb * spin)), dim3(256), 0, ctx->stream, nb, spin,
+        hipLaunchKernelGGL(fit_ray_unpack_kernel, dim3(dmk_grid1d((long long)nb * nb * spin, 8192)), dim3(256), 0, ctx->stream, nb, spin,
                            a->v0, a->v1, a->t, a->H1, a->H, norm_here ? a->ray_norm : nullptr, norm_here ? W.anorm : nullptr,
                            norm_here ? W.state : nullptr, norm_here ? W.arrive : nullptr);
         DMK_CHECK_LAUNCH(ctx);

@@ -89,8 +89,6 @@ __global__ void mp2_density_kernel(int d, double diag, double c1, int sym1, cons
     }
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-int grid1d(long long N) { return (int)std::max<long long>(1, std::min<long long>((N + 255) / 256, 4096)); }
 
 struct StreamDrain {
     hipStream_t s;
@@ -112,7 +110,7 @@ int density_product(dmk_ctx *ctx, int which, int o1, int o2, int v1, int v2, con
 int density_out(dmk_ctx *ctx, int d, double diag, double c1, int sym1, const double *P1, int nb1, double c2, const double *P2, int nb2,
                 double *out) {
     if (d <= 0) return DMK_OK;
-    hipLaunchKernelGGL(mp2_density_kernel, dim3(grid1d((long long)d * d)), dim3(256), 0, ctx->stream, d, diag, c1, sym1, P1, nb1, c2, P2,
+    hipLaunchKernelGGL(mp2_density_kernel, dim3(std::max(1, dmk_grid1d((long long)d * d, 4096))), dim3(256), 0, ctx->stream, d, diag, c1, sym1, P1, nb1, c2, P2,
                        nb2, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
@@ -132,7 +130,7 @@ int amp_launch(dmk_ctx *ctx, int o1, int o2, int v1, int v2, const double *V, co
 struct Carver {
     char *p;
     explicit Carver(void *base) : p(static_cast<char *>(base)) {}
-    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += align256((size_t)std::max<long long>(count, 1) * 8); return q; }
+    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += dmk_align256((size_t)std::max<long long>(count, 1) * 8); return q; }
 };
 
 }  // namespace

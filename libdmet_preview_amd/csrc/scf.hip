@@ -1,17 +1,13 @@
-// K18 -- embedded Hartree-Fock on the device: the one-pass Fock build and the SCF driver around it.
+// K18 -- embedded Hartree-Fock on the device: the SCF driver.
 //
 // Replaces the PySCF kernel behind the reference's SCF.HF (solver/scf.py:954-1043: RIHF / UIHF, :231-253, :354-460).
-//
-// fock_row_kernel   jk_k_kernel (jk.hip) with the Coulomb row dot riding on the values it has already loaded: one workgroup per
-//                   packed row r = pair(i, j) streams E[r][:] ONCE and writes the exchange row vectors Yi[r] = M dm[i,:],
-//                   Yj[r] = M dm[j,:] (M[k][l] = E[r][pair(k,l)]) and yrow[r] = sum_c E[r][c] x~[c].  x~ (the pair-folded
-//                   density) lies at the offsets of the row itself, pair(k,l) being the row's own index, and is loaded with the
-//                   row: same lanes, same masks, same prefetch distance.  All reductions have a fixed order (no atomics).
-// Algorithmic bytes: 8 npair^2 per block for J AND K (dmk_jk_s4 streams the block once for each).
 //
 // dmk_scf           the handle owns h1, overlap, S^-1/2, densities, Fock matrices, orbitals and the DIIS ring (one allocation); the
 //                   ERI blocks are borrowed.  An iteration reads back ONE record (two energy sums and the new row of the DIIS
 //                   matrix, at most DIIS_MAX + 2 doubles); nothing of size n^2 crosses to the host inside the loop.
+// Fock build        scf_veff calls dmk_fock_s4 (jk.hip: J and K of a block from one pass over it), or two dmk_jk_s4 passes per block
+//                   under DMK_SCF_TWO_PASS; the alpha-beta block needs J only and goes through dmk_jk_s4 either way.
+// This file holds the driver, the DIIS arithmetic (dmk_diis_coeffs, host) and the small elementwise kernels around them.
 #include "devres.h"
 #include <algorithm>
 #include <cmath>
@@ -20,137 +16,8 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int NW = NT / 64;
-constexpr int JRB = 32;          // row-range granularity shared with dmk_jk_s4_rows (jk.hip)
 constexpr int DIIS_MAX = 12;
 constexpr int NDOT_MAX = DIIS_MAX + 2;
-
-template <int NM>
-__global__ __launch_bounds__(NT) void fock_row_kernel(int n, const double *__restrict__ E, long long ld,
-                                                      const double *__restrict__ xt, const double *__restrict__ dm,
-                                                      double *__restrict__ yrow, double *__restrict__ Yi,
-                                                      double *__restrict__ Yj, long long row0) {
-    extern __shared__ double sh[];
-    __shared__ double jred[NW];
-    double *xi = sh, *xj = sh + n;                 // dm[i,:], dm[j,:]
-    double *ai = sh + 2 * n, *aj = sh + 3 * n;     // row parts y[k] (one writer per k)
-    double *red = sh + 4 * n;                      // [NW][2][n] mirrored parts per wave
-    const long long r = row0 + blockIdx.x;
-    int i = (int)((sqrt(8.0 * (double)r + 1.0) - 1.0) * 0.5);
-    while ((long long)(i + 1) * (i + 2) / 2 <= r) ++i;
-    while ((long long)i * (i + 1) / 2 > r) --i;
-    const int j = (int)(r - (long long)i * (i + 1) / 2);
-    for (int t = threadIdx.x; t < n; t += NT) {
-        xi[t] = dm[(long long)i * n + t];
-        xj[t] = dm[(long long)j * n + t];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double xli[NM], xlj[NM], yi[NM], yj[NM];
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        const int l = lane + 64 * m;
-        xli[m] = l < n ? xi[l] : 0.0;
-        xlj[m] = l < n ? xj[l] : 0.0;
-        yi[m] = 0.0;
-        yj[m] = 0.0;
-    }
-    const double *Er = E + r * ld;
-    // rows k and n-1-k of the triangle hold n+1 elements together (jk_k_kernel); the x~ values of a row pair travel with it
-    const int nhalf = (n + 1) / 2;
-    double v0[NM], v1[NM], x0[NM], x1[NM], v0n[NM], v1n[NM], x0n[NM], x1n[NM];
-    auto load_pair = [&](int p, double (&a0)[NM], double (&a1)[NM], double (&b0)[NM], double (&b1)[NM]) {
-        const int k0 = p, k1 = n - 1 - p;
-        const long long o0 = (long long)k0 * (k0 + 1) / 2, o1 = (long long)k1 * (k1 + 1) / 2;
-        const bool two = k1 != k0;
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const int l = lane + 64 * m;
-            const bool in0 = p < nhalf && l <= k0, in1 = p < nhalf && two && l <= k1;
-            a0[m] = in0 ? Er[o0 + l] : 0.0;
-            a1[m] = in1 ? Er[o1 + l] : 0.0;
-            b0[m] = in0 ? xt[o0 + l] : 0.0;
-            b1[m] = in1 ? xt[o1 + l] : 0.0;
-        }
-    };
-    double ja = 0.0, jb = 0.0;                             // Coulomb row dot, two chains
-    load_pair(wave, v0, v1, x0, x1);
-    for (int p = wave; p < nhalf; p += NW) {
-        const int k0 = p, k1 = n - 1 - p;
-        const bool two = k1 != k0;
-        load_pair(p + NW, v0n, v1n, x0n, x1n);             // next pair's rows in flight while this one is reduced
-        const double xi0 = xi[k0], xj0 = xj[k0], xi1 = xi[k1], xj1 = xj[k1];
-        double pa0 = 0.0, pb0 = 0.0, pa1 = 0.0, pb1 = 0.0;
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const int l = lane + 64 * m;
-            ja = fma(v0[m], x0[m], ja);                    // J: E[r][pair(k,l)] x~[pair(k,l)]
-            jb = fma(v1[m], x1[m], jb);
-            yi[m] = fma(v0[m], xi0, yi[m]);                // y[l] += M[k][l] x[k]   (includes the diagonal once)
-            yj[m] = fma(v0[m], xj0, yj[m]);
-            yi[m] = fma(v1[m], xi1, yi[m]);
-            yj[m] = fma(v1[m], xj1, yj[m]);
-            const double w0 = (l < k0) ? v0[m] : 0.0, w1 = (l < k1) ? v1[m] : 0.0;
-            pa0 = fma(w0, xli[m], pa0);                    // y[k] += M[k][l] x[l],  l < k
-            pb0 = fma(w0, xlj[m], pb0);
-            pa1 = fma(w1, xli[m], pa1);
-            pb1 = fma(w1, xlj[m], pb1);
-        }
-        pa0 = dmk_wave_sum(pa0);
-        pb0 = dmk_wave_sum(pb0);
-        pa1 = dmk_wave_sum(pa1);
-        pb1 = dmk_wave_sum(pb1);
-        if (lane == 0) {
-            ai[k0] = pa0;
-            aj[k0] = pb0;
-            if (two) {
-                ai[k1] = pa1;
-                aj[k1] = pb1;
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            v0[m] = v0n[m];
-            v1[m] = v1n[m];
-            x0[m] = x0n[m];
-            x1[m] = x1n[m];
-        }
-    }
-    const double js = dmk_wave_sum(ja + jb);
-    if (lane == 0) jred[wave] = js;
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        const int l = lane + 64 * m;
-        if (l < n) {
-            red[(wave * 2 + 0) * n + l] = yi[m];
-            red[(wave * 2 + 1) * n + l] = yj[m];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) yrow[r] = (jred[0] + jred[1]) + (jred[2] + jred[3]);
-    for (int t = threadIdx.x; t < n; t += NT) {
-        double si = ai[t], sj = aj[t];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            si += red[(w * 2 + 0) * n + t];
-            sj += red[(w * 2 + 1) * n + t];
-        }
-        Yi[r * n + t] = si;
-        Yj[r * n + t] = sj;
-    }
-}
-
-// K[a][k] = sum_{i >= a} Yi[pair(i,a)][k] + sum_{j < a} Yj[pair(a,j)][k], in that order
-__global__ __launch_bounds__(NT) void fock_k_gather_kernel(int n, const double *__restrict__ Yi, const double *__restrict__ Yj,
-                                                           double *__restrict__ K) {
-    const int a = blockIdx.x;
-    for (int k = threadIdx.x; k < n; k += NT) {
-        double s = 0.0;
-        for (int i = a; i < n; ++i) s += Yi[((long long)i * (i + 1) / 2 + a) * n + k];
-        for (int j = 0; j < a; ++j) s += Yj[((long long)a * (a + 1) / 2 + j) * n + k];
-        K[(long long)a * n + k] = s;
-    }
-}
 
 // out = c0 p0 + c1 p1 + c2 p2 (null pointers contribute nothing)
 __global__ void scf_lin3_kernel(long long N, double c0, const double *p0, double c1, const double *p1, double c2, const double *p2,
@@ -198,71 +65,6 @@ __global__ void scf_combine_kernel(long long N, Combo C, const double *__restric
         for (int q = 0; q < C.count; ++q) s = fma(C.c[q], ring[(long long)C.slot[q] * N + t], s);
         out[t] = s;
     }
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-int grid1d(long long N) { return (int)std::min<long long>((N + 255) / 256, 4096); }
-
-int fock_s4_impl(dmk_ctx *ctx, const char *who, int n, const double *eri, int64_t ld, int nranges, const int64_t *ranges,
-                 const double *dm_j, const double *dm_k, double *vj, double *vk) {
-    if (!ctx) return DMK_ERR_INVALID;
-    const long long npair = (long long)n * (n + 1) / 2;
-    if (n <= 0 || !eri || ld < npair) return dmk_fail(ctx, DMK_ERR_INVALID, "%s: bad arguments", who);
-    if (n > 512) return dmk_fail(ctx, DMK_ERR_INVALID, "%s: supports n <= 512 (got %d)", who, n);
-    if ((dm_j && !vj) || (dm_k && !vk))
-        return dmk_fail(ctx, DMK_ERR_INVALID, "%s: a density was given without its output matrix", who);
-    const int64_t whole[2] = {0, npair};
-    const bool sharded = nranges > 0;
-    if (!sharded) { nranges = 1; ranges = whole; }
-    for (int q = 0; q < nranges; ++q)      // the rule of dmk_jk_s4_rows, so that one sharding serves both entry points
-        if (ranges[2 * q] < 0 || ranges[2 * q + 1] > npair || ranges[2 * q] > ranges[2 * q + 1] || (ranges[2 * q] % JRB) != 0 ||
-            ((ranges[2 * q + 1] % JRB) != 0 && ranges[2 * q + 1] != npair))
-            return dmk_fail(ctx, DMK_ERR_INVALID, "%s: row range %d = [%lld, %lld) must lie in [0, %lld), start on a multiple of %d and "
-                            "end on one (or at the last row)", who, q, (long long)ranges[2 * q], (long long)ranges[2 * q + 1], npair, JRB);
-    if (!dm_j || !dm_k) {                  // one density: one pass over the block either way
-        if (!dm_j && !dm_k) return DMK_OK;
-        return sharded ? dmk_jk_s4_rows(ctx, n, eri, ld, nranges, ranges, dm_j, nullptr, dm_k, vj, nullptr, vk)
-                       : dmk_jk_s4(ctx, n, eri, ld, dm_j, nullptr, dm_k, vj, nullptr, vk);
-    }
-    const size_t b_vec = align256((size_t)npair * 8), b_Y = align256((size_t)npair * n * 8);
-    void *ws = nullptr;
-    int rc = dmk_scratch(ctx, 2 * b_vec + 2 * b_Y, &ws);
-    if (rc) return rc;
-    char *p = static_cast<char *>(ws);
-    double *xt = reinterpret_cast<double *>(p); p += b_vec;
-    double *yrow = reinterpret_cast<double *>(p); p += b_vec;
-    double *Yi = reinterpret_cast<double *>(p); p += b_Y;
-    double *Yj = reinterpret_cast<double *>(p);
-    if (sharded) {       // rows outside the ranges contribute zeros to the fixed-order reductions below
-        DMK_HIP(ctx, hipMemsetAsync(yrow, 0, (size_t)npair * 8, ctx->stream));
-        DMK_HIP(ctx, hipMemsetAsync(Yi, 0, 2 * b_Y, ctx->stream));
-    }
-    rc = dmk_sym_fold(ctx, n, 1, dm_j, xt);
-    if (rc) return rc;
-    {
-        FamScope fs(ctx, DMK_FAM_JK);
-        const size_t lds = (size_t)(4 + 2 * NW) * n * sizeof(double);
-        const int nm = (n + 63) / 64;
-#define FOCK_LAUNCH(NM)                                                                                              \
-    do {                                                                                                             \
-        if (lds > 48 * 1024)                                                                                         \
-            DMK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(fock_row_kernel<NM>),                    \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
-        for (int q = 0; q < nranges; ++q)                                                                            \
-            if (ranges[2 * q + 1] > ranges[2 * q])                                                                   \
-                hipLaunchKernelGGL(fock_row_kernel<NM>, dim3((unsigned)(ranges[2 * q + 1] - ranges[2 * q])), dim3(NT), lds, \
-                                   ctx->stream, n, eri, (long long)ld, xt, dm_k, yrow, Yi, Yj, (long long)ranges[2 * q]); \
-    } while (0)
-        if (nm <= 1) FOCK_LAUNCH(1);
-        else if (nm <= 2) FOCK_LAUNCH(2);
-        else if (nm <= 4) FOCK_LAUNCH(4);
-        else FOCK_LAUNCH(8);
-#undef FOCK_LAUNCH
-        DMK_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(fock_k_gather_kernel, dim3(n), dim3(NT), 0, ctx->stream, n, Yi, Yj, vk);
-        DMK_CHECK_LAUNCH(ctx);
-    }
-    return dmk_sym_unpack(ctx, n, 1, yrow, nullptr, vj);
 }
 
 // symmetric eigenproblem of a small matrix by cyclic Jacobi (host): A (m x m, destroyed) -> w, V (columns)
@@ -323,7 +125,7 @@ struct dmk_scf {
 namespace {
 
 int scf_lin3(dmk_scf *h, long long N, double c0, const double *p0, double c1, const double *p1, double c2, const double *p2, double *out) {
-    hipLaunchKernelGGL(scf_lin3_kernel, dim3(grid1d(N)), dim3(256), 0, h->ctx->stream, N, c0, p0, c1, p1, c2, p2, out);
+    hipLaunchKernelGGL(scf_lin3_kernel, dim3(dmk_grid1d(N, 4096)), dim3(256), 0, h->ctx->stream, N, c0, p0, c1, p1, c2, p2, out);
     DMK_CHECK_LAUNCH(h->ctx);
     return DMK_OK;
 }
@@ -399,7 +201,7 @@ int scf_error(dmk_scf *h, double *out) {
         fds = h->T2; other = h->T1;
     }
     double *comm = h->nx ? other : out;
-    hipLaunchKernelGGL(scf_antisym_kernel, dim3(grid1d(h->N())), dim3(256), 0, h->ctx->stream, h->n, h->ns, fds, comm);
+    hipLaunchKernelGGL(scf_antisym_kernel, dim3(dmk_grid1d(h->N(), 4096)), dim3(256), 0, h->ctx->stream, h->n, h->ns, fds, comm);
     DMK_CHECK_LAUNCH(h->ctx);
     if (!h->nx) return DMK_OK;
     if ((rc = scf_mm(h, 0, 0, comm, nn, h->X, sx, fds))) return rc;
@@ -409,16 +211,6 @@ int scf_error(dmk_scf *h, double *out) {
 }  // namespace
 
 extern "C" {
-
-int dmk_fock_s4(dmk_ctx *ctx, int n, const double *eri, int64_t ld, const double *dm_j, const double *dm_k, double *vj, double *vk) {
-    return fock_s4_impl(ctx, "fock_s4", n, eri, ld, 0, nullptr, dm_j, dm_k, vj, vk);
-}
-
-int dmk_fock_s4_rows(dmk_ctx *ctx, int n, const double *eri, int64_t ld, int nranges, const int64_t *ranges_host, const double *dm_j,
-                     const double *dm_k, double *vj, double *vk) {
-    if (ctx && (nranges <= 0 || !ranges_host)) return dmk_fail(ctx, DMK_ERR_INVALID, "fock_s4_rows: needs at least one row range");
-    return fock_s4_impl(ctx, "fock_s4_rows", n, eri, ld, nranges, ranges_host, dm_j, dm_k, vj, vk);
-}
 
 int dmk_diis_coeffs(int m, const double *B_host, double *c_host) {
     if (m <= 0 || m > DIIS_MAX || !B_host || !c_host) return DMK_ERR_INVALID;
@@ -584,7 +376,7 @@ int dmk_scf_run(dmk_scf *h, const int *nocc_host, const double *dm0, double alph
                 if (dmk_diis_coeffs(m, Bm, cb.c) == DMK_OK) {
                     cb.count = m;
                     for (int q = 0; q < m; ++q) cb.slot[q] = q;
-                    hipLaunchKernelGGL(scf_combine_kernel, dim3(grid1d(N)), dim3(256), 0, ctx->stream, N, cb, h->ringF, h->Fx);
+                    hipLaunchKernelGGL(scf_combine_kernel, dim3(dmk_grid1d(N, 4096)), dim3(256), 0, ctx->stream, N, cb, h->ringF, h->Fx);
                     DMK_CHECK_LAUNCH(ctx);
                     Fd = h->Fx;
                 } else pushed = 0;                       // a subspace without a usable solution is started afresh

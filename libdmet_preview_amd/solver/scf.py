@@ -23,6 +23,20 @@ from libdmet_preview_amd.system import integral
 from libdmet_preview_amd.utils import logger as log
 
 
+def _rows_call(ctx, outs, whole, rows, row_ranges):
+    """The `row_ranges` convention of jk_dev / fock_dev: None runs `whole()`, an empty list leaves zero partial results in `outs`,
+    anything else goes to `rows(nranges, pointer)` as an int64 (nranges, 2) array."""
+    if row_ranges is None:
+        ctx.check(whole())
+    elif len(row_ranges) == 0:
+        for o in outs:
+            if o is not None:
+                o.zero_()
+    else:
+        rr = np.ascontiguousarray(row_ranges, dtype=np.int64).reshape(-1, 2)
+        ctx.check(rows(len(rr), rr.ctypes.data))
+
+
 def jk_dev(ctx, n, d_eri, d_dm_row=None, d_dm_col=None, d_dm_k=None, ld=None, row_ranges=None):
     """One 4-fold block: returns device (vj_row, vj_col, vk), None where the density was not given.  `row_ranges`
     ([(lo, hi)] of packed pair rows, lo a multiple of 32): the PARTIAL results of those rows of a row-sharded ERI -- the
@@ -30,17 +44,9 @@ def jk_dev(ctx, n, d_eri, d_dm_row=None, d_dm_col=None, d_dm_k=None, ld=None, ro
     npair = n * (n + 1) // 2
     out = [ctx.empty((n, n), np.float64) if d is not None else None for d in (d_dm_row, d_dm_col, d_dm_k)]
     p = lambda a: a.ptr if a is not None else None
-    if row_ranges is None:
-        ctx.check(lib.dmk_jk_s4(ctx.h, int(n), d_eri.ptr, int(ld or npair), p(d_dm_row), p(d_dm_col), p(d_dm_k),
-                                p(out[0]), p(out[1]), p(out[2])))
-    elif len(row_ranges) == 0:
-        for o in out:
-            if o is not None:
-                o.zero_()
-    else:
-        rr = np.ascontiguousarray(row_ranges, dtype=np.int64).reshape(-1, 2)
-        ctx.check(lib.dmk_jk_s4_rows(ctx.h, int(n), d_eri.ptr, int(ld or npair), len(rr), rr.ctypes.data, p(d_dm_row), p(d_dm_col),
-                                     p(d_dm_k), p(out[0]), p(out[1]), p(out[2])))
+    head = (ctx.h, int(n), d_eri.ptr, int(ld or npair))
+    tail = (p(d_dm_row), p(d_dm_col), p(d_dm_k), p(out[0]), p(out[1]), p(out[2]))
+    _rows_call(ctx, out, lambda: lib.dmk_jk_s4(*head, *tail), lambda nr, rr: lib.dmk_jk_s4_rows(*head, nr, rr, *tail), row_ranges)
     return tuple(out)
 
 
@@ -310,15 +316,9 @@ def fock_dev(ctx, n, d_eri, d_dm_j, d_dm_k, ld=None, row_ranges=None):
     """J[dm_j] and K[dm_k] of one 4-fold block from ONE pass over it (dmk_fock_s4): device (vj, vk).  `row_ranges` as in jk_dev."""
     npair = n * (n + 1) // 2
     vj, vk = ctx.empty((n, n), np.float64), ctx.empty((n, n), np.float64)
-    if row_ranges is None:
-        ctx.check(lib.dmk_fock_s4(ctx.h, int(n), d_eri.ptr, int(ld or npair), d_dm_j.ptr, d_dm_k.ptr, vj.ptr, vk.ptr))
-    elif len(row_ranges) == 0:
-        vj.zero_()
-        vk.zero_()
-    else:
-        rr = np.ascontiguousarray(row_ranges, dtype=np.int64).reshape(-1, 2)
-        ctx.check(lib.dmk_fock_s4_rows(ctx.h, int(n), d_eri.ptr, int(ld or npair), len(rr), rr.ctypes.data, d_dm_j.ptr, d_dm_k.ptr,
-                                       vj.ptr, vk.ptr))
+    head = (ctx.h, int(n), d_eri.ptr, int(ld or npair))
+    tail = (d_dm_j.ptr, d_dm_k.ptr, vj.ptr, vk.ptr)
+    _rows_call(ctx, (vj, vk), lambda: lib.dmk_fock_s4(*head, *tail), lambda nr, rr: lib.dmk_fock_s4_rows(*head, nr, rr, *tail), row_ranges)
     return vj, vk
 
 

@@ -71,9 +71,12 @@ def test_fock_s4_against_the_factored_reference(ctx, n, pad):
     print("fock_s4 n=%d pad=%d: max|dJ| = %.3e  max|dK| = %.3e  (|J| %.2f |K| %.2f)" % (
         n, pad, ej, ek, np.abs(sysm.J("aa", dj)).max(), np.abs(sysm.K("aa", dk)).max()))
     assert ej <= TOL and ek <= TOL
-    # the two passes it replaces give the same matrices to rounding, and the pass is bit-reproducible
-    j2, _, k2 = scf.jk_dev(ctx, n, d_E, ctx.to_device(dj), None, ctx.to_device(dk), ld=npair + pad)
-    assert np.abs(vj.get() - j2.get()).max() <= TOL and np.abs(vk.get() - k2.get()).max() <= TOL
+    # the two passes it replaces: J to rounding (jk_j_kernel sums in another order), K bit for bit (both families of the row kernel
+    # share one body), and the pass is bit-reproducible
+    j2, _, _ = scf.jk_dev(ctx, n, d_E, ctx.to_device(dj), None, None, ld=npair + pad)
+    _, _, k2 = scf.jk_dev(ctx, n, d_E, None, None, ctx.to_device(dk), ld=npair + pad)
+    assert np.abs(vj.get() - j2.get()).max() <= TOL
+    assert np.array_equal(vk.get(), k2.get())
     vj3, vk3 = scf.fock_dev(ctx, n, d_E, ctx.to_device(dj), ctx.to_device(dk), ld=npair + pad)
     assert np.array_equal(vj.get(), vj3.get()) and np.array_equal(vk.get(), vk3.get())
 
@@ -119,6 +122,33 @@ def test_fock_s4_rows_at_n_257(ctx):
     ej, ek = np.abs(vj.get() - want_j).max(), np.abs(vk.get() - want_k).max()
     print("fock_s4_rows n=257 rows [0, 64): max|dJ| = %.3e  max|dK| = %.3e" % (ej, ek))
     assert ej <= TOL and ek <= TOL
+    _, _, k2 = scf.jk_dev(ctx, n, ctx.to_device(rows), None, None, ctx.to_device(dk), row_ranges=[(0, nrows)])
+    assert np.array_equal(vk.get(), k2.get())          # the K-only family of the row kernel: the same arithmetic in the same order
+
+
+def test_fock_s4_row_ranges_add_up(ctx):
+    """The fused pass over row ranges at n = 65 (NM = 2, npair = 2145): the range rule, the clearing of the rows a call does not
+    touch and the fused kernel together.  The partial results of [0, 96) and [96, npair) sum to the whole-block result within
+    1e-12 (entries are O(1); the fixed-order gathers add the same terms with zeros in other places), and each partial K equals
+    the K-only pass over the same range bit for bit."""
+    from libdmet_preview_amd.solver import scf
+    n = 65
+    npair = _npair(n)
+    sysm = R.System(n, 100 + n, [n // 2])
+    rng = np.random.default_rng(6500)
+    d_E = _dev_block(ctx, sysm, "aa")
+    d_dj, d_dk = ctx.to_device(_sym(rng, (n, n))), ctx.to_device(_sym(rng, (n, n)) / np.sqrt(n))
+    vj, vk = (a.get() for a in scf.fock_dev(ctx, n, d_E, d_dj, d_dk))
+    sum_j, sum_k = np.zeros((n, n)), np.zeros((n, n))
+    for rr in ([(0, 96)], [(96, npair)]):
+        pj, pk = (a.get() for a in scf.fock_dev(ctx, n, d_E, d_dj, d_dk, row_ranges=rr))
+        _, _, k2 = scf.jk_dev(ctx, n, d_E, None, None, d_dk, row_ranges=rr)
+        assert np.array_equal(pk, k2.get())
+        sum_j += pj
+        sum_k += pk
+    ej, ek = np.abs(sum_j - vj).max(), np.abs(sum_k - vk).max()
+    print("fock_s4_rows n=65 [0, 96) + [96, %d): max|dJ| = %.3e  max|dK| = %.3e" % (npair, ej, ek))
+    assert ej <= 1e-12 and ek <= 1e-12
 
 
 # ---- 3. argument checks --------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ One resident 4-fold block at n = 256 (8.66 GB), filled on the device as lam L^T 
 in one process on the same buffers:
 
     fused   dmk_fock_s4            J and K from one pass over the block
-    pair    dmk_jk_s4 J-only, then dmk_jk_s4 K-only   (csrc/jk.hip, untouched by K18)
+    pair    dmk_jk_s4 J-only, then dmk_jk_s4 K-only   (jk_j_kernel, then the K-only family of the same row kernel in csrc/jk.hip)
 
 Warm-up calls, then the median of --reps repetitions of each, interleaved (fused, pair, fused, ...) so that clock drift hits both
 alike; the spread reported is (max - min) / median.  Also the wall time of one converged RHF at the same n, with its iteration

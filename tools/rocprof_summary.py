@@ -46,7 +46,7 @@ FAMILY = [("dgemm_tn_acc_dma_kernel", "dgemm"), ("half1_kernel", "zgemm_half1"),
           ("tridiag_tiles_kernel", "eigh_tridiag"), ("backtransform_kernel", "eigh_backtransform"),
           ("backtransform_wy_kernel", "eigh_backtransform"), ("wy_tfactor_kernel", "eigh_tfactor"), ("tri_eigpairs_kernel", "eigh_tripairs"), ("eigh_kernel", "eigh"),
           ("fold_fft_kernel", None), ("jk_j_kernel", "jk_j"),
-          ("jk_k_kernel", "jk_k"), ("gemv2_kernel", "gemv2")]
+          ("jk_row_kernel", "jk_k"), ("gemv2_kernel", "gemv2")]
 
 
 def family_of(name):
