@@ -151,6 +151,112 @@ def test_fock_s4_row_ranges_add_up(ctx):
     assert ej <= 1e-12 and ek <= 1e-12
 
 
+# ---- 2b. the fused pass at its extremes, through the C ABI ---------------------------------------------------------------------------
+#
+# n < 8 (fewer row pairs than waves: some waves own none), n = 128 / 256 (every lane of every m live in NM = 2 / 4) and n = 512 (the
+# documented maximum: 48 KiB of dynamic LDS plus the static jred).  References in np.longdouble; TOL as above, and err / bound printed
+# against the forward bounds  J: (npair + 8) eps sum |E| |x~|   K: (2 n + 8) eps sum |M| |d|   (eps = 2^-52).
+
+LD = np.longdouble
+EPS = 2.0 ** -52
+
+
+def _abi_pass(ctx, fused, n, d_E, ld, d_dj, d_dk, ranges=None):
+    """dmk_fock_s4[_rows] (fused) or the K-only dmk_jk_s4[_rows] over NaN-filled outputs: host (vj, vk), vj None for K-only."""
+    from libdmet_preview_amd._lib import lib
+    vj, vk = ctx.to_device(np.full((n, n), np.nan)), ctx.to_device(np.full((n, n), np.nan))
+    rr = None if ranges is None else np.asarray(ranges, dtype=np.int64).ravel()
+    if fused and ranges is None:
+        rc = lib.dmk_fock_s4(ctx.h, n, d_E.ptr, ld, d_dj.ptr, d_dk.ptr, vj.ptr, vk.ptr)
+    elif fused:
+        rc = lib.dmk_fock_s4_rows(ctx.h, n, d_E.ptr, ld, len(ranges), rr.ctypes.data, d_dj.ptr, d_dk.ptr, vj.ptr, vk.ptr)
+    elif ranges is None:
+        rc = lib.dmk_jk_s4(ctx.h, n, d_E.ptr, ld, None, None, d_dk.ptr, None, None, vk.ptr)
+    else:
+        rc = lib.dmk_jk_s4_rows(ctx.h, n, d_E.ptr, ld, len(ranges), rr.ctypes.data, None, None, d_dk.ptr, None, None, vk.ptr)
+    ctx.check(rc)
+    return (vj.get() if fused else None), vk.get()
+
+
+def _ratio(got, want, bound):
+    return float((np.abs(got.astype(LD) - want) / bound).max())
+
+
+def test_fock_s4_whole_blocks_below_eight(ctx):
+    """Random blocks WITHOUT pair-exchange symmetry (E[p][q] != E[q][p]), non-symmetric dm_j and dm_k, pitch npair + 3 with NaN in
+    the padding, against the einsum over the unpacked block."""
+    pad = 3
+    for n in (1, 2, 3, 4, 7, 8):
+        npair = _npair(n)
+        rng = np.random.default_rng(800 + n)
+        blk = np.full((npair, npair + pad), np.nan)
+        blk[:, :npair] = rng.standard_normal((npair, npair))
+        dj, dk = rng.standard_normal((n, n)), rng.standard_normal((n, n))
+        ti, tj = np.tril_indices(n)
+        half = np.zeros((npair, n, n), dtype=LD)
+        half[:, ti, tj] = blk[:, :npair]
+        half[:, tj, ti] = blk[:, :npair]
+        e1 = np.zeros((n, n, n, n), dtype=LD)
+        e1[ti, tj], e1[tj, ti] = half, half
+        want_j, want_k = np.einsum("ijkl,kl->ij", e1, dj.astype(LD)), np.einsum("ijkl,il->jk", e1, dk.astype(LD))
+        # J is computed on the folded density x~ = dj[k,l] + dj[l,k]: the bound sums |E| |x~|
+        xt = np.abs(dj + dj.T - np.diag(np.diag(dj))).astype(LD)
+        bound_j = (npair + 8) * LD(EPS) * 0.5 * np.einsum("ijkl,kl->ij", np.abs(e1), xt + np.diag(np.diag(xt)))
+        bound_k = (2 * n + 8) * LD(EPS) * np.einsum("ijkl,il->jk", np.abs(e1), np.abs(dk).astype(LD))
+        d_E, d_dj, d_dk = ctx.to_device(blk), ctx.to_device(dj), ctx.to_device(dk)
+        vj, vk = _abi_pass(ctx, True, n, d_E, npair + pad, d_dj, d_dk)
+        ej, ek = np.abs(vj - want_j).max(), np.abs(vk - want_k).max()
+        print("fock_s4 n=%d pad=%d: max|dJ| = %.3e  max|dK| = %.3e  err / bound J %.4f K %.4f" % (
+            n, pad, ej, ek, _ratio(vj, want_j, bound_j), _ratio(vk, want_k, bound_k)))
+        assert np.isfinite(vj).all() and np.isfinite(vk).all() and ej <= TOL and ek <= TOL
+        _, k2 = _abi_pass(ctx, False, n, d_E, npair + pad, d_dj, d_dk)
+        assert np.array_equal(vk, k2)                      # the K-only family: bit for bit
+        vj3, vk3 = _abi_pass(ctx, True, n, d_E, npair + pad, d_dj, d_dk)
+        assert np.array_equal(vj, vj3) and np.array_equal(vk, vk3)
+
+
+@pytest.mark.parametrize("n", [128, 256, 512])
+def test_fock_s4_rows_with_every_lane_live(ctx, n):
+    """Rows [0, 64) as in test_fock_s4_rows_at_n_257: only those rows are allocated, the reference is the same per-row loop, in
+    np.longdouble.  At n = 512 the two ranges [0, 32), [32, 64) of ONE call give the bits of the single range."""
+    nrows = 64
+    npair = _npair(n)
+    rng = np.random.default_rng(n)
+    rows = rng.standard_normal((nrows, npair)) / n
+    dj, dk = _sym(rng, (n, n)), rng.standard_normal((n, n))
+    d_rows, d_dj, d_dk = ctx.to_device(rows), ctx.to_device(dj), ctx.to_device(dk)
+    vj, vk = _abi_pass(ctx, True, n, d_rows, npair, d_dj, d_dk, [(0, nrows)])
+    ti, tj = np.tril_indices(n)
+    xt = np.where(ti == tj, dj[ti, tj], dj[ti, tj] + dj[tj, ti]).astype(LD)
+    dkl = dk.astype(LD)
+    want_j, want_k, abs_j, abs_k = (np.zeros((n, n), dtype=LD) for _ in range(4))
+    M = np.zeros((n, n), dtype=LD)
+    for r in range(nrows):
+        i, j = ti[r], tj[r]
+        row = rows[r].astype(LD)
+        M[ti, tj] = row
+        M[tj, ti] = row
+        want_j[i, j] = want_j[j, i] = row @ xt
+        abs_j[i, j] = abs_j[j, i] = np.abs(row) @ np.abs(xt)
+        want_k[j, :] += M @ dkl[i, :]
+        abs_k[j, :] += np.abs(M) @ np.abs(dkl[i, :])
+        if i != j:
+            want_k[i, :] += M @ dkl[j, :]
+            abs_k[i, :] += np.abs(M) @ np.abs(dkl[j, :])
+    ej, ek = np.abs(vj - want_j).max(), np.abs(vk - want_k).max()
+    live_j, live_k = abs_j > 0, abs_k > 0                  # rows of J / K that the 64 packed rows reach; the rest are exact zeros
+    rj = _ratio(vj[live_j], want_j[live_j], (npair + 8) * LD(EPS) * abs_j[live_j])
+    rk = _ratio(vk[live_k], want_k[live_k], (2 * n + 8) * LD(EPS) * abs_k[live_k])
+    print("fock_s4_rows n=%d rows [0, 64): max|dJ| = %.3e  max|dK| = %.3e  err / bound J %.4f K %.4f" % (n, ej, ek, rj, rk))
+    assert ej <= TOL and ek <= TOL
+    assert not vj[~live_j].any() and not vk[~live_k].any()
+    _, k2 = _abi_pass(ctx, False, n, d_rows, npair, d_dj, d_dk, [(0, nrows)])
+    assert np.array_equal(vk, k2)                          # the K-only family of the row kernel: the same arithmetic in the same order
+    if n == 512:
+        vj2, vk2 = _abi_pass(ctx, True, n, d_rows, npair, d_dj, d_dk, [(0, 32), (32, 64)])
+        assert np.array_equal(vj, vj2) and np.array_equal(vk, vk2)
+
+
 # ---- 3. argument checks --------------------------------------------------------------------------------------------------------------
 
 def test_fock_s4_refuses_bad_arguments(ctx):

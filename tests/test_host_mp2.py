@@ -62,6 +62,65 @@ def test_density_trace_is_the_electron_count(kind, n, Sz):
     assert out["e_corr"] < 0.0 and abs(out["e_corr"]) < 1.0
 
 
+@pytest.mark.parametrize("kind,n,Sz", [("rhf", 6, 0), ("uhf", 6, 2)])
+def test_longdouble_reference_equals_the_float64_one_on_a_listed_system(kind, n, Sz):
+    """The formulas of rmp2_from_g / ump2_from_g at np.longdouble (the reference of tests/test_gpu_mp2_kernel.py) against the
+    float64 evaluation that rmp2 / ump2 return, on listed cases of scf_ref.SEEDS: within 1e-12, and within the forward bounds."""
+    ld = np.longdouble
+    ref = R.run_case(kind, n, Sz)
+    sysm, c, e, nocc = ref["system"], np.asarray(ref["mo_coeff"]), np.asarray(ref["mo_energy"]), ref["nocc"]
+    if kind == "rhf":
+        o = nocc[0]
+        g = M.ovov(sysm, "aa", c[:, :o], c[:, o:], c[:, :o], c[:, o:]).transpose(0, 2, 1, 3)
+        lo, hi = M.rmp2_from_g(g, e[:o], e[o:]), M.rmp2_from_g(g.astype(ld), e[:o].astype(ld), e[o:].astype(ld))
+        bound = M.rmp2_bounds(g, hi)
+        assert lo["t2"].dtype == np.float64 and hi["t2"].dtype == ld and hi["doo"].dtype == ld and hi["dvv"].dtype == ld
+        assert np.array_equal(lo["t2"], M.rmp2(sysm, c, e, o)["t2"])
+    else:
+        (ca, cb), (ea, eb), (oa, ob) = c, e, nocc
+        gaa = M.ovov(sysm, "aa", ca[:, :oa], ca[:, oa:], ca[:, :oa], ca[:, oa:]).transpose(0, 2, 1, 3)
+        gbb = M.ovov(sysm, "bb", cb[:, :ob], cb[:, ob:], cb[:, :ob], cb[:, ob:]).transpose(0, 2, 1, 3)
+        gab = M.ovov(sysm, "ab", ca[:, :oa], ca[:, oa:], cb[:, :ob], cb[:, ob:]).transpose(0, 2, 1, 3)
+        es = (ea[:oa], ea[oa:], eb[:ob], eb[ob:])
+        lo = M.ump2_from_g(gaa, gab, gbb, *es)
+        hi = M.ump2_from_g(gaa.astype(ld), gab.astype(ld), gbb.astype(ld), *(x.astype(ld) for x in es))
+        bound = M.ump2_bounds(gaa, gab, gbb, hi)
+        assert all(x.dtype == ld for x in hi["t2"]) and hi["doo_b"].dtype == ld
+        assert all(np.array_equal(x, y) for x, y in zip(lo["t2"], M.ump2(sysm, c, e, nocc)["t2"]))
+    for key in bound:
+        a, b = (lo[key], hi[key]) if isinstance(bound[key], tuple) else ((lo[key],), (hi[key],))
+        assert max(float(np.abs(x.astype(ld) - y).max()) for x, y in zip(a, b)) <= 1e-12, key
+    ratios = M.ratios(lo, hi, bound)
+    print("%s n=%d Sz=%d float64 against longdouble, err / bound: %s" % (kind, n, Sz, {k: "%.3f" % r for k, r in ratios.items()}))
+    assert max(ratios.values()) <= 1.0
+
+
+def test_float64_formulas_hold_the_bounds_on_synthetic_integrals():
+    """The inputs of tests/test_gpu_mp2_kernel.py (synthetic_g, synthetic_levels) at two of its shapes: numpy's float64 evaluation
+    of the formulas stays within the bounds the device result is held to, denominators are <= -2 and the repeated levels are there."""
+    ld = np.longdouble
+    rng = np.random.default_rng(20)
+    for o, v in [(1, 1), (2, 3), (7, 16)]:
+        V, e = M.synthetic_g(rng, o * v), M.synthetic_levels(rng, o, v)
+        assert np.array_equal(V, V.T) and e[:o].max() <= -0.5 and e[o:].min() >= 0.5
+        assert (o < 2 or e[o - 1] == e[0]) and (v < 2 or e[o + v // 2] == e[o])
+        g = V.reshape(o, v, o, v).transpose(0, 2, 1, 3)
+        lo, hi = M.rmp2_from_g(g, e[:o], e[o:]), M.rmp2_from_g(g.astype(ld), e[:o].astype(ld), e[o:].astype(ld))
+        assert max(M.ratios(lo, hi, M.rmp2_bounds(g, hi)).values()) <= 1.0
+        assert abs(float(np.trace(hi["doo"]) + np.trace(hi["dvv"])) - 2 * o) <= 1e-15 * o * o * v * v
+    oa, va, ob, vb = 5, 9, 2, 12
+    gaa = M.synthetic_g(rng, oa * va).reshape(oa, va, oa, va).transpose(0, 2, 1, 3)
+    gbb = M.synthetic_g(rng, ob * vb).reshape(ob, vb, ob, vb).transpose(0, 2, 1, 3)
+    gab = M.synthetic_g(rng, oa * va, ob * vb).reshape(oa, va, ob, vb).transpose(0, 2, 1, 3)
+    ea, eb = M.synthetic_levels(rng, oa, va), M.synthetic_levels(rng, ob, vb)
+    es = (ea[:oa], ea[oa:], eb[:ob], eb[ob:])
+    lo = M.ump2_from_g(gaa, gab, gbb, *es)
+    hi = M.ump2_from_g(gaa.astype(ld), gab.astype(ld), gbb.astype(ld), *(x.astype(ld) for x in es))
+    assert max(M.ratios(lo, hi, M.ump2_bounds(gaa, gab, gbb, hi)).values()) <= 1.0
+    assert abs(float(np.trace(hi["doo_a"]) + np.trace(hi["dvv_a"])) - oa) <= 1e-15 and \
+        abs(float(np.trace(hi["doo_b"]) + np.trace(hi["dvv_b"])) - ob) <= 1e-15
+
+
 def test_restricted_energy_against_the_spin_orbital_formula():
     """e = 1/4 sum |<ij||ab>|^2 / D over spin orbitals, from the 1-fold block -- a third statement of the energy."""
     n = 6
