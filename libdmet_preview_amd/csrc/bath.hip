@@ -22,9 +22,6 @@
 #include <algorithm>
 #include <vector>
 
-int launch_eigh_public(dmk_ctx *ctx, int n, int batch, const void *A, int a_real, const double *add, int add_group,
-                       double *w, void *Vt, int v_real);
-
 namespace {
 
 constexpr int NT = 256;
@@ -1022,7 +1019,7 @@ int dmk_bath_assemble(dmk_ctx *ctx, const double *U, int nenv, int nb, int nbath
         hipLaunchKernelGGL(jacobi_svd_fast_kernel, dim3(1), dim3(JF_NT), 0, ctx->stream, nbath, S, nbath, ev, Vt, st, 0, 0LL, 0LL, st + 2);
         hipLaunchKernelGGL(inv_sqrt_cols_kernel, dim3(16), dim3(256), 0, ctx->stream, nbath, ev, Vt, 1e-14, X, st + 2);
     } else if (orth) {
-        rc = launch_eigh_public(ctx, nbath, 1, S, 1, nullptr, 0, ev, Vt, 1);
+        rc = dmk_eigh_batched_real(ctx, nbath, 1, S, ev, Vt);
         if (rc) { cleanup(); return rc; }
     }
     {

@@ -251,6 +251,19 @@ __device__ __forceinline__ double dmk_wave_sum(double v) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }
+// Wave64 max (shuffle-xor butterfly): every lane gets it.  Cold paths only (acceptance tests).
+__device__ __forceinline__ double dmk_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// 1 / q: v_rcp_f64 and two Newton steps (full precision for normal q)
+__device__ __forceinline__ double dmk_rcp_nr2(double q) {
+    double r = __builtin_amdgcn_rcp(q);
+    r = r * (2.0 - q * r);
+    r = r * (2.0 - q * r);
+    return r;
+}
 #else
 __device__ unsigned lds_addr_of(const void *p);          // host pass: declarations only
 __device__ void glds16(const void *gsrc, unsigned lds_base);
@@ -262,6 +275,8 @@ __device__ void glds16s_x4(unsigned, unsigned, unsigned, unsigned, const void *,
 __device__ void glds16s_x6(unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, const void *, const void *, const void *,
                            const void *, const void *, const void *, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned);
 __device__ double dmk_wave_sum(double v);
+__device__ double dmk_wave_max(double v);
+__device__ double dmk_rcp_nr2(double q);
 #endif
 
 // ---- launchers implemented in the .hip files ---------------------------------------------
@@ -272,6 +287,18 @@ int launch_sym_fold(dmk_ctx *ctx, int fam, int n, int batch, const double *full,
 int launch_sym_unpack(dmk_ctx *ctx, int fam, int n, int batch, const double *tril, const double *add_tril, double *full);
 // fit.hip: y[c] = sum_b part[b][c], b < nblk, c < n, in a fixed order; inside the caller's FamScope
 int launch_partsum(dmk_ctx *ctx, long long n, int nblk, const double *part, double *y);
+
+// ---- the eigensolver family: what launch_eigh (eigh.hip) calls in the other files
+// eigh_tridiag.hip: CU-resident tridiagonalisation (1 = done, 0 = shape not covered, < 0 on error) and the back-transformation
+int launch_tridiag_resident(dmk_ctx *ctx, int n, int batch, const void *A, const double *add, int add_group, void *Vh, void *tau,
+                            double *d, double *e);
+int launch_backtransform(dmk_ctx *ctx, int n, int batch, const double *Zt, const void *Vh, const void *tau, const int *rank, void *Vt,
+                         void *Tws);
+// eigh_tripairs.hip: 1 = launched (flags must then be honoured by the caller), 0 = shape not covered / DMK_EIGH_TRIPAIRS=0, < 0 on error
+int launch_tri_eigpairs(dmk_ctx *ctx, int n, int batch, const double *d, const double *e, double *Zt, double *w, int *rank_out,
+                        int *flags, int inject);
+// eigh_large.hip: all eigenpairs of one matrix, the n > 2000 route of dmk_eigh_batched_real
+int launch_eigh_large_all(dmk_ctx *ctx, int n, const double *A, double *w, double *Vt);
 
 // C (M x N, ldc) += alpha * X^T Y;  X: K x M (ldx), Y: K x N (ldy)   (dgemm_tn.hip)
 struct DgemmTn {

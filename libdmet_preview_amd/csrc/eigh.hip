@@ -19,7 +19,7 @@
 // Bound: latency / L2: algorithmic HBM traffic is
 // 2*16*n^2 + 8*n bytes per matrix.
 #include "common.h"
-#include "tridiag_bisect.h"
+#include "tridiag_eig.h"
 
 namespace {
 
@@ -33,11 +33,6 @@ __device__ __forceinline__ double2 cmulc(double2 a, double2 b) {   // conj(a) * 
     return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x);
 }
 __device__ __forceinline__ double wave_sum(double v) { return dmk_wave_sum(v); }
-__device__ __forceinline__ double wave_max(double v) {          // cold path only (residual check)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 struct EighArgs {
     int n, batch;
@@ -331,7 +326,6 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
         double *lam = cs + n;                                 // [n] eigenvalue of lane j (ascending inside a block)
         double *bnorm = cs + 2 * n;                           // [n] 1-norm of the block of i
         double *ws = g.ws2 + (size_t)b * 7 * nn;              // seven [row][lane] arrays
-        const double eps = 2.220446049250313e-16;
         double *e2 = reinterpret_cast<double *>(vbuf);        // [n] squared couplings (the reflector buffer is idle now)
         for (int t = tid; t < n; t += NT) {
             dl[t] = d[t];
@@ -339,116 +333,14 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
         }
         for (size_t idx = tid; idx < nn; idx += NT) Zt[idx] = 0.0;
         __syncthreads();
-        if (tid == 0) {
-            int s0 = 0;
-            for (int i = 0; i < n; ++i) {
-                const bool cut = (i == n - 1) || fabs(el[i]) <= eps * (fabs(dl[i]) + fabs(dl[i + 1]));
-                if (!cut) continue;
-                el[i] = 0.0;
-                double nrm = 0.0;
-                for (int q = s0; q <= i; ++q)
-                    nrm = fmax(nrm, fabs(dl[q]) + (q > s0 ? fabs(el[q - 1]) : 0.0) + (q < i ? fabs(el[q]) : 0.0));
-                for (int q = s0; q <= i; ++q) { bs[q] = s0; be[q] = i + 1; bnorm[q] = nrm; }
-                s0 = i + 1;
-            }
-        }
+        if (tid == 0) dmk_tri_split(n, dl, el, bs, be, bnorm);
         __syncthreads();
         for (int t = tid; t < n; t += NT) e2[t] = el[t] * el[t];
         __syncthreads();
-        // ---- inverse iteration, one lane per eigenvector; the pieces are shared by the first pass and by the repair path ----
-        // (c1) elimination with partial pivoting of T - lm I on the rows of j's block (three upper diagonals, multipliers,
-        //      swap flags; tiny pivots replaced by eps |T|)
-        auto inv_factor = [&](const int j, const double lm) {
-            const int s0 = bs[j], t0 = be[j];
-            double *U0 = ws + j, *U1 = U0 + nn, *U2 = U1 + nn, *Lm = U2 + nn, *Pv = Lm + nn;
-            const double pert = fmax(eps * bnorm[j], 1e-300);
-            double cd = dl[s0] - lm, cu = el[s0];
-            for (int i = s0; i + 1 < t0; ++i) {
-                const double sub = el[i], nd = dl[i + 1] - lm, nu = (i + 2 < t0) ? el[i + 1] : 0.0;
-                const size_t o = (size_t)i * n;
-                if (fabs(cd) >= fabs(sub)) {
-                    if (fabs(cd) < pert) cd = cd >= 0.0 ? pert : -pert;
-                    const double mlt = sub / cd;
-                    U0[o] = cd; U1[o] = cu; U2[o] = 0.0; Lm[o] = mlt; Pv[o] = 0.0;
-                    cd = nd - mlt * cu;
-                    cu = nu;
-                } else {
-                    const double mlt = cd / sub;
-                    U0[o] = sub; U1[o] = nd; U2[o] = nu; Lm[o] = mlt; Pv[o] = 1.0;
-                    cd = cu - mlt * nd;
-                    cu = -mlt * nu;
-                }
-            }
-            if (fabs(cd) < pert) cd = cd >= 0.0 ? pert : -pert;
-            U0[(size_t)(t0 - 1) * n] = cd;
-        };
-        // (c2) start vector: hashed uniform numbers in (-1, 1), different for every matrix, eigenvalue, row and attempt
-        auto inv_seed = [&](const int j, const unsigned long long salt) {
-            const int s0 = bs[j], t0 = be[j];
-            double *x = ws + j + 5 * nn;
-            unsigned long long h = ((unsigned long long)b * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)(j + 1) * 0xC2B2AE3D27D4EB4Full) ^
-                                   (salt * 0xD6E8FEB86659FD93ull);
-            for (int i = s0; i < t0; ++i) {
-                h += 0x9E3779B97F4A7C15ull;
-                unsigned long long z = h;
-                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-                z ^= z >> 31;
-                x[(size_t)i * n] = (double)(long long)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-            }
-        };
-        auto inv_xmax = [&](const int j) {
-            const int s0 = bs[j], t0 = be[j];
-            const double *x = ws + j + 5 * nn;
-            double xm = 0.0;
-            for (int i = s0; i < t0; ++i) xm = fmax(xm, fabs(x[(size_t)i * n]));
-            return xm;
-        };
-        // (c3) one solve (T - lm I) x_new = x / xm.  It reads one array and writes another (forward x -> y, backward y -> x), so
-        //      the loads of a pass do not alias its stores and the compiler may run several rows ahead of the recurrence; the
-        //      scale of the next right-hand side (max |x|) is gathered during the backward pass and returned.
-        auto inv_solve = [&](const int j, const double xm_in) {
-            const int s0 = bs[j], t0 = be[j];
-            const double *U0 = ws + j, *U1 = U0 + nn, *U2 = U1 + nn, *Lm = U2 + nn, *Pv = Lm + nn;
-            double *x = ws + j + 5 * nn;
-            double *__restrict__ yv = x + nn;                  // second vector, lane-major like the others
-            const double sc = xm_in > 0.0 ? 1.0 / xm_in : 1.0;
-            double cur = x[(size_t)s0 * n] * sc;
-#pragma unroll 4
-            for (int i = s0; i + 1 < t0; ++i) {                // forward: row swaps and multipliers
-                const size_t o = (size_t)i * n;
-                double nxt = x[o + n] * sc;
-                const double pv = Pv[o], ml = Lm[o];
-                if (pv != 0.0) { const double tsw = cur; cur = nxt; nxt = tsw; }
-                yv[o] = cur;
-                cur = nxt - ml * cur;
-            }
-            yv[(size_t)(t0 - 1) * n] = cur;
-            double x1 = 0.0, x2 = 0.0, xm = 0.0;
-#pragma unroll 4
-            for (int i = t0 - 1; i >= s0; --i) {               // backward: three upper diagonals
-                const size_t o = (size_t)i * n;
-                const double u0 = U0[o], u1 = U1[o], u2 = U2[o];
-                double r = yv[o];
-                if (i + 1 < t0) r -= u1 * x1 + u2 * x2;
-                r /= u0;
-                x[o] = r;
-                xm = fmax(xm, fabs(r));
-                x2 = x1;
-                x1 = r;
-            }
-            return xm;
-        };
-        // (c4) normalised copy into row j of Z^T
-        auto inv_store = [&](const int j, const double xm) {
-            const int s0 = bs[j], t0 = be[j];
-            const double *x = ws + j + 5 * nn;
-            double nr = 0.0;
-            const double sc = xm > 0.0 ? 1.0 / xm : 1.0;
-            for (int i = s0; i < t0; ++i) { const double v = x[(size_t)i * n] * sc; nr += v * v; }
-            const double inv = sc / sqrt(nr);
-            for (int i = s0; i < t0; ++i) Zt[(size_t)j * n + i] = x[(size_t)i * n] * inv;
-        };
+        // ---- (c) inverse iteration (InvIt, tridiag_eig.h): vector j owns column j of the seven n x n scratch arrays.  The
+        // struct is set up where ONE lane uses it: held across the wave-wide steps of the repair path, its pointers cost
+        // a VGPR in every instantiation (spilled SGPRs).
+        auto invit = [&](const int j) { return InvIt<false>(n, n, j, j, dl, el, bs, be, bnorm, ws); };
         for (int j = tid; j < n; j += NT) {
             const int s0 = bs[j], t0 = be[j], m = t0 - s0, kk = j - s0;
             if (m == 1) {
@@ -457,49 +349,22 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
                 continue;
             }
             const double tn = bnorm[j];
-            // ---- (b) bisection on the Sturm count over the block's Gershgorin interval (tridiag_bisect.h)
+            // ---- (b) bisection on the Sturm count over the block's Gershgorin interval
             const double lm = dmk_bisect_eigenvalue(dl, el, e2, s0, t0, kk, tn);
             lam[j] = lm;
-            inv_factor(j, lm);
-            inv_seed(j, 0ull);
-            double xm = inv_xmax(j);
+            auto it = invit(j);
+            it.factor(lm);
+            double xm = it.seed(b, j, 0ull);
             // two solves: the shift is an eigenvalue to rounding, so ONE step already leaves the eigenvector with relative error
             // ~ eps |T| / gap and the second is the safety margin dstein's growth test usually stops at; every vector goes through
             // the acceptance test of phase (e) below, which repairs the rare one that needed more (the third solve cost a quarter of
             // the 5.9 GB this phase moves through its lane-major scratch)
-            for (int iter = 0; iter < 2; ++iter) xm = inv_solve(j, xm);
-            inv_store(j, xm);
+            for (int iter = 0; iter < 2; ++iter) xm = it.solve(xm);
+            it.store(xm, Zt + (size_t)j * n);
         }
         __syncthreads();
         // ---- (d) clusters: one wave each, members in ascending order
-        {
-            int cluster = -1;
-            for (int j = 0; j < n; ++j) {
-                const bool first = (j == bs[j]) || (lam[j] - lam[j - 1] > 1e-3 * bnorm[j]);
-                if (!first) continue;
-                ++cluster;
-                if (cluster % NW != wave) continue;
-                const int s0 = bs[j], t0 = be[j];
-                int last = j;
-                while (last + 1 < t0 && lam[last + 1] - lam[last] <= 1e-3 * bnorm[j]) ++last;
-                for (int q = j + 1; q <= last; ++q) {
-                    double *zq = Zt + (size_t)q * n;
-                    for (int pass = 0; pass < 2; ++pass)
-                        for (int p = j; p < q; ++p) {
-                            const double *zp = Zt + (size_t)p * n;
-                            double dot = 0.0;
-                            for (int i = s0 + lane; i < t0; i += 64) dot += zp[i] * zq[i];
-                            dot = wave_sum(dot);
-                            for (int i = s0 + lane; i < t0; i += 64) zq[i] -= dot * zp[i];
-                        }
-                    double nr = 0.0;
-                    for (int i = s0 + lane; i < t0; i += 64) nr += zq[i] * zq[i];
-                    nr = wave_sum(nr);
-                    const double inv = nr > 0.0 ? 1.0 / sqrt(nr) : 0.0;
-                    for (int i = s0 + lane; i < t0; i += 64) zq[i] *= inv;
-                }
-            }
-        }
+        dmk_tri_cluster_mgs<NW>(n, lane, wave, bs, be, lam, bnorm, Zt);
         __syncthreads();
         // ---- (e) acceptance test and repair.  Three fixed solves from a random start are enough for every spectrum met so
         // far, but nothing above PROVES an eigenvector: an unlucky start, near-duplicate shifts inside one unreduced block or
@@ -509,25 +374,10 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
         // re-orthogonalisation against the accepted members of its cluster INSIDE the iteration; if that fails as well the
         // launch reports DMK_ERR_NOCONV instead of returning a wrong basis.
         int *bad = reinterpret_cast<int *>(pbuf);             // [n] (the Householder buffer is idle in this phase)
-        const double rtol = 64.0 * n * eps;
+        const double rtol = 64.0 * n * DMK_EPS;
         auto residual_ok = [&](const int j) {                 // wave-cooperative; every lane returns the verdict
             const int s0 = bs[j], t0 = be[j];
-            if (t0 - s0 == 1) return true;
-            const double *z = Zt + (size_t)j * n;
-            const double lj = lam[j];
-            double r = 0.0, zn = 0.0;
-            for (int i = s0 + lane; i < t0; i += 64) {
-                const double zi = z[i];
-                double t = (dl[i] - lj) * zi;
-                if (i > s0) t += el[i - 1] * z[i - 1];
-                if (i + 1 < t0) t += el[i] * z[i + 1];
-                r = fmax(r, fabs(t));
-                if (!(fabs(t) <= 1.7e308)) r = 1.7e308;        // NaN / Inf: fmax would drop a NaN
-                zn += zi * zi;
-            }
-            r = wave_max(r);
-            zn = wave_sum(zn);
-            return r <= rtol * fmax(bnorm[j], 1e-300) && fabs(zn - 1.0) <= 1e-8;
+            return t0 - s0 == 1 || dmk_tri_accept(lane, s0, t0, dl, el, bnorm[j], lam[j], Zt + (size_t)j * n, rtol);
         };
         for (int j = wave; j < n; j += NW) {
             bool ok = residual_ok(j);
@@ -541,19 +391,20 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
                 const int s0 = bs[j], t0 = be[j];
                 const double tn = bnorm[j], lj = lam[j];
                 double *zj = Zt + (size_t)j * n;
-                double *x = ws + j + 5 * nn;
+                double *x = invit(j).x;
                 bool fixed = false;
                 for (int attempt = 1; attempt <= 3 && !fixed; ++attempt) {
                     double xm = 0.0;
                     if (lane == 0) {
-                        inv_factor(j, lj + ((attempt & 1) ? 4.0 : -4.0) * attempt * eps * tn);
-                        inv_seed(j, (unsigned long long)attempt);
-                        xm = inv_xmax(j);
+                        auto it = invit(j);
+                        it.factor(lj + ((attempt & 1) ? 4.0 : -4.0) * attempt * DMK_EPS * tn);
+                        xm = it.seed(b, j, (unsigned long long)attempt);
                     }
                     for (int iter = 0; iter < 5 && !fixed; ++iter) {
                         if (lane == 0) {
-                            xm = inv_solve(j, xm);
-                            inv_store(j, xm);
+                            auto it = invit(j);
+                            xm = it.solve(xm);
+                            it.store(xm, zj);
                         }
                         __threadfence_block();
                         // orthogonalise against the accepted vectors of j's cluster (twice), renormalise, feed back
@@ -600,17 +451,7 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
     // ---- phase 3: sort + back-transformation ------------------------------------------------------
     // rank[j] = position of eigenvalue j in ascending order (stable); kept in cs[] as ints
     int *rank = reinterpret_cast<int *>(cs);
-    for (int j = tid; j < n; j += NT) {
-        const double dj = d[j];
-        int rk = 0;
-        for (int q = 0; q < n; ++q) {
-            const double dq = d[q];
-            rk += (dq < dj || (dq == dj && q < j)) ? 1 : 0;
-        }
-        rank[j] = rk;
-        g.w[(size_t)b * n + rk] = dj;
-        if (g.rank_out) g.rank_out[(size_t)b * n + j] = rk;
-    }
+    dmk_tri_rank_sort<NT>(n, tid, d, g.w + (size_t)b * n, rank, g.rank_out ? g.rank_out + (size_t)b * n : nullptr);
     __syncthreads();
     if (g.rank_out) {
         if (b == 0 && tid == 0) {
@@ -690,16 +531,6 @@ __global__ __launch_bounds__(NT) void eigh_kernel(const EighArgs g) {
     }
 }
 
-}  // namespace
-int launch_tridiag_resident(dmk_ctx *ctx, int n, int batch, const void *A, const double *add, int add_group, void *Vh, void *tau,
-                            double *d, double *e);
-int launch_backtransform(dmk_ctx *ctx, int n, int batch, const double *Zt, const void *Vh, const void *tau, const int *rank, void *Vt,
-                         void *Tws);
-int launch_tri_eigpairs(dmk_ctx *ctx, int n, int batch, const double *d, const double *e, double *Zt, double *w, int *rank_out,
-                        int *flags, int inject);
-int launch_eigh_large_all(dmk_ctx *ctx, int n, const double *A, double *w, double *Vt);      // eigh_large.hip
-namespace {
-
 int launch_eigh(dmk_ctx *ctx, int n, int batch, const void *A, int a_real, const double *add, int add_group, double *w,
                 void *Vt, int v_real) {
     if (n <= 0 || batch <= 0) return DMK_OK;
@@ -767,22 +598,12 @@ int launch_eigh(dmk_ctx *ctx, int n, int batch, const void *A, int a_real, const
         if (!g.skip_tridiag) DMK_HIP(ctx, hipMemsetAsync(g.Vh, 0, nn * 16 * batch, ctx->stream));
         // HR (rows in flight per wave in the Householder matrix-vector product): see the kernel
         const bool few = batch <= 256;
-        const void *fn = n <= 64 ? (few ? reinterpret_cast<const void *>(eigh_kernel<1, 4>) : reinterpret_cast<const void *>(eigh_kernel<1, 2>))
-                         : n <= 256 ? (few ? reinterpret_cast<const void *>(eigh_kernel<4, 4>) : reinterpret_cast<const void *>(eigh_kernel<4, 2>))
-                         : n <= 1024 ? reinterpret_cast<const void *>(eigh_kernel<16, 2>)
-                                     : reinterpret_cast<const void *>(eigh_kernel<32, 2>);
-        if (lds > 48 * 1024) DMK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (n <= 64) {
-            if (few) hipLaunchKernelGGL((eigh_kernel<1, 4>), dim3(batch), dim3(NT), lds, ctx->stream, g);
-            else hipLaunchKernelGGL((eigh_kernel<1, 2>), dim3(batch), dim3(NT), lds, ctx->stream, g);
-        } else if (n <= 256) {
-            if (few) hipLaunchKernelGGL((eigh_kernel<4, 4>), dim3(batch), dim3(NT), lds, ctx->stream, g);
-            else hipLaunchKernelGGL((eigh_kernel<4, 2>), dim3(batch), dim3(NT), lds, ctx->stream, g);
-        } else if (n <= 1024) {
-            hipLaunchKernelGGL((eigh_kernel<16, 2>), dim3(batch), dim3(NT), lds, ctx->stream, g);
-        } else {
-            hipLaunchKernelGGL((eigh_kernel<32, 2>), dim3(batch), dim3(NT), lds, ctx->stream, g);
-        }
+        void (*const kern)(EighArgs) = n <= 64 ? (few ? eigh_kernel<1, 4> : eigh_kernel<1, 2>)
+                                       : n <= 256 ? (few ? eigh_kernel<4, 4> : eigh_kernel<4, 2>)
+                                       : n <= 1024 ? eigh_kernel<16, 2> : eigh_kernel<32, 2>;
+        if (lds > 48 * 1024)
+            DMK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(batch), dim3(NT), lds, ctx->stream, g);
         DMK_CHECK_LAUNCH(ctx);
         if (g.rank_out) {
             const int rb = launch_backtransform(ctx, n, batch, g.Zt, g.Vh, g.tau, g.rank_out, Vt, g.W);   // W is idle on this path: T factors
@@ -805,11 +626,6 @@ int launch_eigh(dmk_ctx *ctx, int n, int batch, const void *A, int a_real, const
 }
 
 }  // namespace
-
-int launch_eigh_public(dmk_ctx *ctx, int n, int batch, const void *A, int a_real, const double *add, int add_group,
-                       double *w, void *Vt, int v_real) {
-    return launch_eigh(ctx, n, batch, A, a_real, add, add_group, w, Vt, v_real);
-}
 
 extern "C" {
 

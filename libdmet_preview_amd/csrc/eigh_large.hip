@@ -13,7 +13,7 @@
 //      synchronisation inside the column loop.  The working copy of A (full symmetric storage) ends up holding the reflectors,
 //      v_k in row k.  Traffic: the trailing block is read and written once per column, 16 (n - k)^2 bytes.
 //   2. all eigenvalues: T is cut into unreduced blocks (host, O(n)), one lane per eigenvalue bisects on the Sturm count
-//      (tridiag_bisect.h), the host sorts.
+//      (tridiag_eig.h), the host sorts.
 //   3. selected eigenvectors of T: one lane per vector runs inverse iteration (pivoted elimination of T - lam I kept lane-major
 //      in scratch, hashed start that depends on the eigenvalue's position only, three solves); eigenvalues of a block chained by
 //      gaps <= 1e-3 |T| (dstein's criterion) form a cluster, owned by one workgroup: row by row classical Gram-Schmidt applied twice
@@ -24,7 +24,7 @@
 //   4. back-transformation of the m selected vectors: panels of NB = 32 reflectors in compact WY form, Y -= V T (V^T Y), every
 //      product a C += alpha X^T Y contraction on the f64 matrix cores (dgemm_tn.hip); O(n^2 m).
 #include "common.h"
-#include "tridiag_bisect.h"
+#include "tridiag_eig.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -50,13 +50,6 @@ constexpr int HNW = HNT / 64;
 constexpr int UNT = 256;          // threads of the trailing-block kernel
 constexpr int ROWS = 4;           // rows per wave and pass
 constexpr int MAXGRID = 2048;
-constexpr double EPS = 2.220446049250313e-16;
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // sum over the workgroup, every thread gets it; partials are combined in wave order (deterministic)
 template <int NWAVES>
@@ -200,98 +193,6 @@ __global__ void bisect_kernel(int n, const double *__restrict__ d, const double 
     lam[j] = t0 - s0 == 1 ? d[s0] : dmk_bisect_eigenvalue(d, e, e2, s0, t0, j - s0, bnorm[j]);
 }
 
-// ---- inverse iteration for one vector, run by ONE lane.  Scratch is lane-major: element i of array a of row r at
-// ws[a n m + i m + r] (arrays: three upper diagonals, multipliers, swap flags, x, y).
-struct InvIt {
-    int s0, t0;
-    size_t sm;
-    double *U0, *U1, *U2, *Lm, *Pv, *x, *yv;
-    const double *dl, *el;
-    double pert;
-    __device__ InvIt(int n, int m, int r, int j, const double *dl_, const double *el_, const int *bs, const int *be, const double *bnorm,
-                     double *ws)
-        : s0(bs[j]), t0(be[j]), sm((size_t)m), dl(dl_), el(el_) {
-        const size_t nm = (size_t)n * m;
-        U0 = ws + r; U1 = U0 + nm; U2 = U1 + nm; Lm = U2 + nm; Pv = Lm + nm; x = Pv + nm; yv = x + nm;
-        pert = fmax(EPS * bnorm[j], 1e-300);
-    }
-    // elimination with partial pivoting of T - lm I; tiny pivots -> eps |T|
-    __device__ void factor(const double lm) {
-        double cd = dl[s0] - lm, cu = el[s0];
-        for (int i = s0; i + 1 < t0; ++i) {
-            const double sub = el[i], nd = dl[i + 1] - lm, nu = (i + 2 < t0) ? el[i + 1] : 0.0;
-            const size_t o = (size_t)i * sm;
-            if (fabs(cd) >= fabs(sub)) {
-                if (fabs(cd) < pert) cd = cd >= 0.0 ? pert : -pert;
-                const double mlt = sub / cd;
-                U0[o] = cd; U1[o] = cu; U2[o] = 0.0; Lm[o] = mlt; Pv[o] = 0.0;
-                cd = nd - mlt * cu;
-                cu = nu;
-            } else {
-                const double mlt = cd / sub;
-                U0[o] = sub; U1[o] = nd; U2[o] = nu; Lm[o] = mlt; Pv[o] = 1.0;
-                cd = cu - mlt * nd;
-                cu = -mlt * nu;
-            }
-        }
-        if (fabs(cd) < pert) cd = cd >= 0.0 ? pert : -pert;
-        U0[(size_t)(t0 - 1) * sm] = cd;
-    }
-    // start vector: hashed uniform numbers in (-1, 1), a function of the position j, the row index and the attempt only (a vector
-    // does not depend on which other vectors were asked for); returns max |x|
-    __device__ double seed(const int j, const unsigned long long salt) {
-        unsigned long long h = ((unsigned long long)(j + 1) * 0xC2B2AE3D27D4EB4Full) ^ (salt * 0xD6E8FEB86659FD93ull);
-        double xm = 0.0;
-        for (int i = s0; i < t0; ++i) {
-            h += 0x9E3779B97F4A7C15ull;
-            unsigned long long q = h;
-            q = (q ^ (q >> 30)) * 0xBF58476D1CE4E5B9ull;
-            q = (q ^ (q >> 27)) * 0x94D049BB133111EBull;
-            q ^= q >> 31;
-            const double v = (double)(long long)(q >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-            x[(size_t)i * sm] = v;
-            xm = fmax(xm, fabs(v));
-        }
-        return xm;
-    }
-    // one solve (T - lm I) x_new = x / xm_in; returns max |x_new|
-    __device__ double solve(const double xm_in) {
-        const double sc = xm_in > 0.0 ? 1.0 / xm_in : 1.0;
-        double cur = x[(size_t)s0 * sm] * sc;
-#pragma unroll 4
-        for (int i = s0; i + 1 < t0; ++i) {                // forward: row swaps and multipliers
-            const size_t o = (size_t)i * sm;
-            double nxt = x[o + sm] * sc;
-            const double pv = Pv[o], ml = Lm[o];
-            if (pv != 0.0) { const double tsw = cur; cur = nxt; nxt = tsw; }
-            yv[o] = cur;
-            cur = nxt - ml * cur;
-        }
-        yv[(size_t)(t0 - 1) * sm] = cur;
-        double x1 = 0.0, x2 = 0.0, xm = 0.0;
-#pragma unroll 4
-        for (int i = t0 - 1; i >= s0; --i) {               // backward: three upper diagonals
-            const size_t o = (size_t)i * sm;
-            double rr = yv[o];
-            if (i + 1 < t0) rr -= U1[o] * x1 + U2[o] * x2;
-            rr /= U0[o];
-            x[o] = rr;
-            xm = fmax(xm, fabs(rr));
-            x2 = x1;
-            x1 = rr;
-        }
-        return xm;
-    }
-    // normalised copy into z (a row of Z)
-    __device__ void store(const double xm, double *z) {
-        const double sc = xm > 0.0 ? 1.0 / xm : 1.0;
-        double nr = 0.0;
-        for (int i = s0; i < t0; ++i) { const double v = x[(size_t)i * sm] * sc; nr += v * v; }
-        const double inv = sc / sqrt(nr);
-        for (int i = s0; i < t0; ++i) z[i] = x[(size_t)i * sm] * inv;
-    }
-};
-
 // first pass: one lane per selected vector (row r of Z, position pos[r] in T), three solves from the hashed start
 __global__ void invit_kernel(int n, int m, const int *__restrict__ pos, const double *__restrict__ dl, const double *__restrict__ el,
                              const int *__restrict__ bs, const int *__restrict__ be, const double *__restrict__ bnorm,
@@ -301,9 +202,9 @@ __global__ void invit_kernel(int n, int m, const int *__restrict__ pos, const do
     const int j = pos[r];
     double *z = Z + (size_t)r * n;
     if (be[j] - bs[j] == 1) { z[bs[j]] = 1.0; return; }
-    InvIt it(n, m, r, j, dl, el, bs, be, bnorm, ws);
+    InvIt<true> it(n, m, r, j, dl, el, bs, be, bnorm, ws);
     it.factor(lam[j]);
-    double xm = it.seed(j, 0ull);
+    double xm = it.seed(0, j, 0ull);
     for (int iter = 0; iter < 3; ++iter) xm = it.solve(xm);
     it.store(xm, z);
 }
@@ -357,7 +258,7 @@ __global__ __launch_bounds__(HNT) void cluster_kernel(int n, int m, const int *_
             if (!(kept < 0.5) || round == 4) break;                   // uniform: every thread holds the same sum
             if (tid == 0) {
                 const int r = r0 + q;
-                InvIt it(n, m, r, pos[r], dl, el, bs, be, bnorm, ws);
+                InvIt<true> it(n, m, r, pos[r], dl, el, bs, be, bnorm, ws);
                 double xm = 0.0;
                 for (int i = s0; i < t0; ++i) { const double v = zq[i]; it.x[(size_t)i * it.sm] = v; xm = fmax(xm, fabs(v)); }
                 xm = it.solve(xm);
@@ -374,26 +275,6 @@ __global__ __launch_bounds__(HNT) void cluster_kernel(int n, int m, const int *_
     }
 }
 
-// acceptance test of one vector by one wave: |T z - lam z|_inf <= rtol |T| and | |z|^2 - 1 | <= 1e-8 (NaN fails both); every lane
-// returns the verdict, *ratio (optional) the residual in units of |T|
-__device__ __forceinline__ bool vector_ok(const int lane, const int s0, const int t0, const double *dl, const double *el, const double tn,
-                                          const double lj, const double *z, const double rtol, double *ratio) {
-    double res = 0.0, zn = 0.0;
-    for (int i = s0 + lane; i < t0; i += 64) {
-        const double zi = z[i];
-        double t = (dl[i] - lj) * zi;
-        if (i > s0) t += el[i - 1] * z[i - 1];
-        if (i + 1 < t0) t += el[i] * z[i + 1];
-        res = fmax(res, fabs(t));
-        if (!(fabs(t) <= 1.7e308)) res = 1.7e308;
-        zn += zi * zi;
-    }
-    res = wave_max(res);
-    zn = dmk_wave_sum(zn);
-    if (ratio) *ratio = res / fmax(tn, 1e-300);
-    return res <= rtol * fmax(tn, 1e-300) && fabs(zn - 1.0) <= 1e-8;
-}
-
 // one wave per vector: bad[r] = 1 when the vector fails the acceptance test; status[1] counts the flagged rows
 __global__ __launch_bounds__(256) void verify_kernel(int n, int m, const int *__restrict__ pos, const double *__restrict__ dl,
                                                      const double *__restrict__ el, const int *__restrict__ bs, const int *__restrict__ be,
@@ -404,8 +285,10 @@ __global__ __launch_bounds__(256) void verify_kernel(int n, int m, const int *__
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= m) return;
     const int j = pos[r], s0 = bs[j], t0 = be[j];
-    double rt = 0.0;
-    const bool ok = t0 - s0 == 1 || vector_ok(lane, s0, t0, dl, el, bnorm[j], lam[j], Z + (size_t)r * n, rtol, &rt);
+    const double tn = bnorm[j];
+    double res = 0.0;
+    const bool ok = t0 - s0 == 1 || dmk_tri_accept(lane, s0, t0, dl, el, tn, lam[j], Z + (size_t)r * n, rtol, &res);
+    const double rt = res / fmax(tn, 1e-300);          // the residual in units of |T|
     if (lane == 0) {
         const int b = (ok && !bad[r]) ? 0 : 1;         // a row the cluster pass flagged stays flagged
         bad[r] = b;
@@ -429,13 +312,13 @@ __global__ __launch_bounds__(64) void repair_kernel(int n, int m, const int *__r
         const int j = pos[r], s0 = bs[j], t0 = be[j];
         const double tn = bnorm[j], lj = lam[j];
         double *zj = Z + (size_t)r * n;
-        InvIt it(n, m, r, j, dl, el, bs, be, bnorm, ws);
+        InvIt<true> it(n, m, r, j, dl, el, bs, be, bnorm, ws);
         bool fixed = false;
         for (int attempt = 1; attempt <= 3 && !fixed; ++attempt) {
             double xm = 0.0;
             if (lane == 0) {
-                it.factor(lj + ((attempt & 1) ? 4.0 : -4.0) * attempt * EPS * tn);
-                xm = it.seed(j, (unsigned long long)attempt);
+                it.factor(lj + ((attempt & 1) ? 4.0 : -4.0) * attempt * DMK_EPS * tn);
+                xm = it.seed(0, j, (unsigned long long)attempt);
             }
             for (int iter = 0; iter < 5 && !fixed; ++iter) {
                 if (lane == 0) {
@@ -469,7 +352,7 @@ __global__ __launch_bounds__(64) void repair_kernel(int n, int m, const int *__r
                     __threadfence_block();
                 }
                 xm = 1.0;
-                fixed = iter >= 1 && worst <= otol && vector_ok(lane, s0, t0, dl, el, tn, lj, zj, rtol, nullptr);
+                fixed = iter >= 1 && worst <= otol && dmk_tri_accept(lane, s0, t0, dl, el, tn, lj, zj, rtol);
             }
         }
         if (lane == 0) {
@@ -592,16 +475,7 @@ int factor(dmk_ctx *ctx, int n, const double *A, int64_t lda, double *w, dmk_eig
         return dmk_fail(ctx, DMK_ERR_NOCONV, "eigh_large: the tridiagonal form of the %d x %d matrix is not finite (NaN / Inf in the input?)", n, n);
     // ---- phase 2: unreduced blocks (negligible couplings are set to zero), bisection, sort
     h->bs.assign(n, 0); h->be.assign(n, 0); h->bnorm.assign(n, 0.0);
-    for (int i = 0, s0 = 0; i < n; ++i) {
-        const bool cut = (i == n - 1) || std::fabs(he[i]) <= EPS * (std::fabs(hd[i]) + std::fabs(hd[i + 1]));
-        if (!cut) continue;
-        he[i] = 0.0;
-        double nrm = 0.0;
-        for (int q = s0; q <= i; ++q)
-            nrm = std::max(nrm, std::fabs(hd[q]) + (q > s0 ? std::fabs(he[q - 1]) : 0.0) + (q < i ? std::fabs(he[q]) : 0.0));
-        for (int q = s0; q <= i; ++q) { h->bs[q] = s0; h->be[q] = i + 1; h->bnorm[q] = nrm; }
-        s0 = i + 1;
-    }
+    dmk_tri_split(n, hd.data(), he.data(), h->bs.data(), h->be.data(), h->bnorm.data());
     for (int i = 0; i < n; ++i) he2[i] = he[i] * he[i];
     DMK_HIP(ctx, hipMemcpyAsync(e, he.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
     DMK_HIP(ctx, hipMemcpyAsync(e2, he2.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
@@ -699,7 +573,7 @@ int vectors(dmk_eighl *h, int m, const int32_t *idx, double *Vt) {
     // ---- phase 3
     hipLaunchKernelGGL(invit_kernel, dim3((m + 63) / 64), dim3(64), 0, st, n, m, d_pos, d, e, bs, be, bnorm, lam, ws, Z);
     DMK_CHECK_LAUNCH(ctx);
-    const double otol = 64.0 * EPS * std::sqrt((double)n), rtol = 64.0 * n * EPS;
+    const double otol = 64.0 * DMK_EPS * std::sqrt((double)n), rtol = 64.0 * n * DMK_EPS;
     if (ncl) {
         hipLaunchKernelGGL(cluster_kernel, dim3(ncl), dim3(HNT), 0, st, n, m, d_r0, d_cnt, d_pos, d, e, bs, be, bnorm, ws, Z, dots, otol, d_bad);
         DMK_CHECK_LAUNCH(ctx);

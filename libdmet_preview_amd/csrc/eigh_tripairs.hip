@@ -7,8 +7,9 @@
 // HBM traffic (rocprofv3 PMC, profiles/r03_d_*) for an arithmetically tiny amount of work.
 //
 // Here one 256-thread workgroup per matrix keeps everything in LDS:
-//   (a) block splitting at negligible couplings, (b) the k-th eigenvalue of its block by bisection on the Sturm count -- both
-//       exactly as in eigh_kernel (one lane per eigenvalue, d / e / e^2 in LDS);
+//   (a) block splitting at negligible couplings, (b) the k-th eigenvalue of its block by bisection on the Sturm count (one lane
+//       per eigenvalue, d / e / e^2 in LDS) -- these, the cluster rule, the acceptance test and the sort are the shared pieces of
+//       tridiag_eig.h;
 //   (c) the eigenvector from the TWISTED FACTORISATION of T - lam I (Parlett & Dhillon; LAPACK dlar1v without its RRR shifts):
 //         forward   D+_1 = d_1 - lam,  D+_{i+1} = (d_{i+1} - lam) - e_i^2 / D+_i          (L+ D+ L+^T from the top)
 //         backward  D-_n = d_n - lam,  D-_i     = (d_i - lam)     - e_i^2 / D-_{i+1}      (U- D- U-^T from the bottom)
@@ -22,13 +23,14 @@
 //       chains (a 16-column slab, one workgroup per CU, measured 2.5 ms for 432 x 200: 0.65 ms of bisection + 0.35 ms of
 //       vectors per matrix with nothing to hide the latencies behind, and two rounds of workgroups).
 //       With lam accurate to eps |T| the residual is |gamma_r| |z_r| / |z| = O(n eps |T|); eigenvalues of one block closer than
-//       1e-3 |T| form a cluster whose vectors are re-orthogonalised (modified Gram-Schmidt, twice), the same rule as before;
-//   (d) the ACCEPTANCE TEST of eigh_kernel on every vector (|T z - lam z|_inf <= 64 n eps |T|, |z| = 1; NaN fails): a matrix with
+//       1e-3 |T| form a cluster whose vectors are re-orthogonalised (modified Gram-Schmidt, twice);
+//   (d) the ACCEPTANCE TEST on every vector (|T z - lam z|_inf <= 64 n eps |T|, |z| = 1; NaN fails): a matrix with
 //       a failed vector is only FLAGGED -- the caller then runs eigh_kernel's phase 2 (pivoted inverse iteration with its
 //       dstein-style repair path) on the flagged matrices, so nothing is ever accepted on trust;
 //   (e) rank sort, eigenvalues out.
 // HBM traffic: d, e in; Z^T (n^2 doubles per matrix) out and once more through L2 for clusters / the acceptance test.
 #include "common.h"
+#include "tridiag_eig.h"
 #include <cstdlib>
 #include <vector>
 
@@ -50,18 +52,6 @@ struct TpArgs {
     double *debug;           // optional batch x 4: first failed vector j, its residual / (rtol |T|), |z|^2 - 1, twist index (DMK_EIGH_DEBUG)
 };
 
-__device__ __forceinline__ double tp_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double tp_rcp(double q) {          // 1 / q: hardware estimate + two Newton steps (full precision for normal q)
-    double r = __builtin_amdgcn_rcp(q);
-    r = r * (2.0 - q * r);
-    r = r * (2.0 - q * r);
-    return r;
-}
-
 __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int n = g.n, b = blockIdx.x;
@@ -71,7 +61,6 @@ __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
     double *Wk = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(rank + n) + 15) & ~static_cast<uintptr_t>(15));   // [n][TP_LD]
     const double *d = g.d + (size_t)b * n, *e = g.e + (size_t)b * n;
     double *Zt = g.Zt + (size_t)b * n * n;
-    const double eps = 2.220446049250313e-16;
     long long tph[7];
     tph[0] = wall_clock64();
 
@@ -81,19 +70,7 @@ __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
     }
     __syncthreads();
     // ---- (a) unreduced blocks ----------------------------------------------------------------------------------------------
-    if (tid == 0) {
-        int s0 = 0;
-        for (int i = 0; i < n; ++i) {
-            const bool cut = (i == n - 1) || fabs(el[i]) <= eps * (fabs(dl[i]) + fabs(dl[i + 1]));
-            if (!cut) continue;
-            el[i] = 0.0;
-            double nrm = 0.0;
-            for (int q = s0; q <= i; ++q)
-                nrm = fmax(nrm, fabs(dl[q]) + (q > s0 ? fabs(el[q - 1]) : 0.0) + (q < i ? fabs(el[q]) : 0.0));
-            for (int q = s0; q <= i; ++q) { bs[q] = s0; be[q] = i + 1; bnorm[q] = nrm; }
-            s0 = i + 1;
-        }
-    }
+    if (tid == 0) dmk_tri_split(n, dl, el, bs, be, bnorm);
     __syncthreads();
     for (int t = tid; t < n; t += TP_NT) e2[t] = el[t] * el[t];
     __syncthreads();
@@ -101,38 +78,8 @@ __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
     tph[1] = wall_clock64();
     // ---- (b) eigenvalues: bisection on the Sturm count, one lane per eigenvalue ----------------------------------------------
     for (int j = tid; j < n; j += TP_NT) {
-        const int s0 = bs[j], t0 = be[j], m = t0 - s0, kk = j - s0;
-        if (m == 1) { lam[j] = dl[s0]; continue; }
-        const double tn = bnorm[j];
-        double emax2 = 0.0, lo = dl[s0], hi = dl[s0];
-        for (int i = s0; i < t0; ++i) {
-            const double rad = (i > s0 ? fabs(el[i - 1]) : 0.0) + (i + 1 < t0 ? fabs(el[i]) : 0.0);
-            lo = fmin(lo, dl[i] - rad);
-            hi = fmax(hi, dl[i] + rad);
-            if (i + 1 < t0) emax2 = fmax(emax2, e2[i]);
-        }
-        const double pivmin = 2.2250738585072014e-308 * fmax(1.0, emax2);
-        lo -= 2.0 * eps * tn * m + 2.0 * pivmin;
-        hi += 2.0 * eps * tn * m + 2.0 * pivmin;
-        // plain bisection (measured: a quadrisection with three interleaved Sturm recurrences per lane is SLOWER, 0.75 vs 0.67 ms per
-        // 200 x 200 matrix -- the loop is bound by f64 instruction issue (v_rcp_f64 + two Newton steps per pivot), not by latency)
-        for (int it = 0; it < 200; ++it) {
-            const double mid = 0.5 * (lo + hi);
-            if (!(mid > lo && mid < hi)) break;
-            int cnt = 0;
-            double q = dl[s0] - mid;
-            if (fabs(q) < pivmin) q = -pivmin;
-            cnt += q < 0.0 ? 1 : 0;
-#pragma unroll 4
-            for (int i = s0 + 1; i < t0; ++i) {
-                q = (dl[i] - mid) - e2[i - 1] * tp_rcp(q);
-                if (fabs(q) < pivmin) q = -pivmin;
-                cnt += q < 0.0 ? 1 : 0;
-            }
-            if (cnt > kk) hi = mid; else lo = mid;
-            if (hi - lo <= eps * (fabs(lo) + fabs(hi)) + 2.0 * pivmin) break;
-        }
-        lam[j] = 0.5 * (lo + hi);
+        const int s0 = bs[j], t0 = be[j];
+        lam[j] = t0 - s0 == 1 ? dl[s0] : dmk_bisect_eigenvalue(dl, el, e2, s0, t0, j - s0, bnorm[j]);
     }
     __syncthreads();
 
@@ -154,14 +101,14 @@ __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
                     inv = 1.0;
                 } else {
                     const double lm = lam[j];
-                    const double pert = fmax(eps * bnorm[j], 1e-300);
+                    const double pert = fmax(DMK_EPS * bnorm[j], 1e-300);
                     auto guard = [&](double v) { return fabs(v) < pert ? (v >= 0.0 ? pert : -pert) : v; };
                     // forward: D+_i into slot i.  (Storing the multipliers e_i / D+_i instead, so that the upward z recurrence is a bare
                     // multiply, measured slower: 0.63 vs 0.56 ms -- the extra multiply and fma in the two long passes cost more.)
                     double dp = guard(dl[s0] - lm);
                     x[(size_t)s0 * TP_LD] = dp;
                     for (int i = s0; i + 1 < t0; ++i) {
-                        dp = guard((dl[i + 1] - lm) - e2[i] * tp_rcp(dp));
+                        dp = guard((dl[i + 1] - lm) - e2[i] * dmk_rcp_nr2(dp));
                         x[(size_t)(i + 1) * TP_LD] = dp;
                     }
                     // backward 1: D-_i on the fly, gamma_i against the stored D+_i, argmin
@@ -169,21 +116,21 @@ __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
                     double gmin = fabs(x[(size_t)(t0 - 1) * TP_LD] + dm - (dl[t0 - 1] - lm));
                     int r = t0 - 1;
                     for (int i = t0 - 2; i >= s0; --i) {
-                        dm = guard((dl[i] - lm) - e2[i] * tp_rcp(dm));
+                        dm = guard((dl[i] - lm) - e2[i] * dmk_rcp_nr2(dm));
                         const double gm = fabs(x[(size_t)i * TP_LD] + dm - (dl[i] - lm));
                         if (gm < gmin) { gmin = gm; r = i; }
                     }
                     // backward 2: bottom -> r + 1, slot i <- e_{i-1} / D-_i  (the multiplier of z_{i-1} -> z_i)
                     dm = guard(dl[t0 - 1] - lm);
                     for (int i = t0 - 1; i > r; --i) {
-                        const double rd = tp_rcp(dm);
+                        const double rd = dmk_rcp_nr2(dm);
                         x[(size_t)i * TP_LD] = el[i - 1] * rd;
                         dm = guard((dl[i - 1] - lm) - e2[i - 1] * rd);
                     }
                     // z: twist at r, up with D+, down with the stored multipliers; z overwrites the slots
                     double nr = 1.0, zc = 1.0;
                     for (int i = r - 1; i >= s0; --i) {
-                        zc = -(el[i] * tp_rcp(x[(size_t)i * TP_LD])) * zc;
+                        zc = -(el[i] * dmk_rcp_nr2(x[(size_t)i * TP_LD])) * zc;
                         x[(size_t)i * TP_LD] = zc;
                         nr = fma(zc, zc, nr);
                     }
@@ -212,84 +159,30 @@ __global__ __launch_bounds__(TP_NT) void tri_eigpairs_kernel(const TpArgs g) {
     __syncthreads();
 
     tph[3] = wall_clock64();
-    // ---- clusters: one wave each, members in ascending order (as in eigh_kernel) ----------------------------------------------
-    {
-        int cluster = -1;
-        for (int j = 0; j < n; ++j) {
-            const bool first = (j == bs[j]) || (lam[j] - lam[j - 1] > 1e-3 * bnorm[j]);
-            if (!first) continue;
-            ++cluster;
-            if (cluster % TP_NW != wave) continue;
-            const int s0 = bs[j], t0 = be[j];
-            int last = j;
-            while (last + 1 < t0 && lam[last + 1] - lam[last] <= 1e-3 * bnorm[j]) ++last;
-            for (int q = j + 1; q <= last; ++q) {
-                double *zq = Zt + (size_t)q * n;
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int p = j; p < q; ++p) {
-                        const double *zp = Zt + (size_t)p * n;
-                        double dot = 0.0;
-                        for (int i = s0 + lane; i < t0; i += 64) dot += zp[i] * zq[i];
-                        dot = dmk_wave_sum(dot);
-                        for (int i = s0 + lane; i < t0; i += 64) zq[i] -= dot * zp[i];
-                    }
-                double nr = 0.0;
-                for (int i = s0 + lane; i < t0; i += 64) nr += zq[i] * zq[i];
-                nr = dmk_wave_sum(nr);
-                const double invn = nr > 0.0 ? 1.0 / sqrt(nr) : 0.0;
-                for (int i = s0 + lane; i < t0; i += 64) zq[i] *= invn;
-            }
-        }
-    }
+    // ---- clusters: one wave each, members in ascending order -------------------------------------------------------------------
+    dmk_tri_cluster_mgs<TP_NW>(n, lane, wave, bs, be, lam, bnorm, Zt);
     __threadfence_block();
     __syncthreads();
 
     tph[4] = wall_clock64();
     // ---- (d) acceptance test, one wave per vector -------------------------------------------------------------------------------
-    const double rtol = 64.0 * n * eps;
+    const double rtol = 64.0 * n * DMK_EPS;
     for (int j = wave; j < n; j += TP_NW) {
         const int s0 = bs[j], t0 = be[j];
-        bool ok = true;
-        double dbg_r = 0.0, dbg_z = 0.0;
-        if (t0 - s0 > 1) {
-            const double *z = Zt + (size_t)j * n;
-            const double lj = lam[j];
-            double r = 0.0, zn = 0.0;
-            for (int i = s0 + lane; i < t0; i += 64) {
-                const double zi = z[i];
-                double t = (dl[i] - lj) * zi;
-                if (i > s0) t += el[i - 1] * z[i - 1];
-                if (i + 1 < t0) t += el[i] * z[i + 1];
-                r = fmax(r, fabs(t));
-                if (!(fabs(t) <= 1.7e308)) r = 1.7e308;
-                zn += zi * zi;
-            }
-            r = tp_wave_max(r);
-            zn = dmk_wave_sum(zn);
-            ok = r <= rtol * fmax(bnorm[j], 1e-300) && fabs(zn - 1.0) <= 1e-8;
-            dbg_r = r / (rtol * fmax(bnorm[j], 1e-300));
-            dbg_z = zn - 1.0;
-        }
+        double res = 0.0, zn = 1.0;                             // what a 1 x 1 block has by construction
+        bool ok = t0 - s0 == 1 || dmk_tri_accept(lane, s0, t0, dl, el, bnorm[j], lam[j], Zt + (size_t)j * n, rtol, &res, &zn);
         if (g.inject > 0 && (j % g.inject) == g.inject - 1) ok = false;
         if (!ok && lane == 0) {
             if (atomicAdd(&g.flags[b], 1) == 0 && g.debug) {
-                g.debug[4 * b] = j; g.debug[4 * b + 1] = dbg_r; g.debug[4 * b + 2] = dbg_z; g.debug[4 * b + 3] = (double)(t0 - s0);
+                g.debug[4 * b] = j; g.debug[4 * b + 1] = res / (rtol * fmax(bnorm[j], 1e-300)); g.debug[4 * b + 2] = zn - 1.0;
+                g.debug[4 * b + 3] = (double)(t0 - s0);
             }
         }
     }
 
     tph[5] = wall_clock64();
     // ---- (e) rank sort (ascending, stable) -----------------------------------------------------------------------------------------
-    for (int j = tid; j < n; j += TP_NT) {
-        const double dj = lam[j];
-        int rk = 0;
-        for (int q = 0; q < n; ++q) {
-            const double dq = lam[q];
-            rk += (dq < dj || (dq == dj && q < j)) ? 1 : 0;
-        }
-        g.w[(size_t)b * n + rk] = dj;
-        g.rank_out[(size_t)b * n + j] = rk;
-    }
+    dmk_tri_rank_sort<TP_NT>(n, tid, lam, g.w + (size_t)b * n, g.rank_out + (size_t)b * n, nullptr);
     if (g.debug && b == 0 && tid == 0) {                     // phase clocks of matrix 0 (100 MHz wall clock)
         tph[6] = wall_clock64();
         for (int q = 0; q < 6; ++q) g.debug[4 * (size_t)g.batch + q] = (double)(tph[q + 1] - tph[q]);

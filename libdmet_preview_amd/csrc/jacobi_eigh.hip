@@ -60,12 +60,6 @@ __device__ __forceinline__ bool matrix_barrier(unsigned *bar, unsigned target, i
     return ok != 0;
 }
 
-__device__ __forceinline__ double fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = r * (2.0 - x * r);
-    r = r * (2.0 - x * r);
-    return r;
-}
 __device__ __forceinline__ double fast_rsqrt(double x) {
     double y = __builtin_amdgcn_rsq(x);
     y = y * (1.5 - 0.5 * x * y * y);
@@ -105,10 +99,10 @@ __device__ __forceinline__ bool rotate_pairs(double *Gs, double *Vs, int n, cons
         // approximations + two Newton steps (full double precision, a fraction of the IEEE division / sqrt sequences)
         rot[k] = (c[k] * c[k] > tol * tol * (a[k] * b[k])) && c[k] != 0.0;
         const double cc = rot[k] ? c[k] : 1.0;
-        const double zeta = 0.5 * (b[k] - a[k]) * fast_rcp(cc);
+        const double zeta = 0.5 * (b[k] - a[k]) * dmk_rcp_nr2(cc);
         const double h2 = fma(zeta, zeta, 1.0);
         const double hyp = h2 * fast_rsqrt(h2);                 // sqrt(1 + zeta^2)
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) * fast_rcp(fabs(zeta) + hyp);
+        const double t = (zeta >= 0.0 ? 1.0 : -1.0) * dmk_rcp_nr2(fabs(zeta) + hyp);
         cs[k] = fast_rsqrt(fma(t, t, 1.0));
         sn[k] = cs[k] * t;
         any |= rot[k];
@@ -659,7 +653,7 @@ __global__ __launch_bounds__(1024) void rf_analyse_kernel(RfAnalyse g) {
                 const double num = fma(la, r, sv);
                 maxres = (fabs(num) <= 1.7e308) ? fmax(maxres, fabs(num)) : INFINITY;     // NaN / Inf must not vanish in fmax
                 if (fabs(gap) > delta) {
-                    f = num * fast_rcp(gap);
+                    f = num * dmk_rcp_nr2(gap);
                 } else {
                     f = 0.5 * r;
                     maxresc = fmax(maxresc, fabs(num));
@@ -822,7 +816,7 @@ __global__ __launch_bounds__(RF_T) void rf_update_kernel(RfUpdate g) {
                 const double num = fma(la, r, sv);
                 maxres = (fabs(num) <= 1.7e308) ? fmax(maxres, fabs(num)) : INFINITY;
                 if (fabs(gap) > delta) {
-                    f = num * fast_rcp(gap);
+                    f = num * dmk_rcp_nr2(gap);
                 } else {
                     f = 0.5 * r;
                     maxresc = fmax(maxresc, fabs(num));

@@ -535,6 +535,56 @@ def test_eigh_clustered_tridiagonal(ctx, inject, monkeypatch):
         assert np.abs(T @ V - V * w).max() < 1e-12 * scale * max(1, n / 10)
 
 
+def _clustered_mats():
+    return [_wilkinson(10), _glued([_wilkinson(10)] * 9, 1e-9), _glued([_wilkinson(10)] * 4, 1e-13),
+            _glued([np.diag([1.0, 1.0, 1.0]) + 1e-7 * (np.eye(3, k=1) + np.eye(3, k=-1))] * 5, 1e-7)]
+
+
+def _check_clustered(T, w, V):
+    """the bounds of test_eigh_clustered_tridiagonal; the figures are printed before they are asserted"""
+    n = T.shape[0]
+    wr = np.linalg.eigvalsh(T)
+    scale = np.abs(wr).max()
+    f = max(1, n / 10)
+    errs = (np.abs(w - wr).max() / scale, np.abs(V.conj().T @ V - np.eye(n)).max(), np.abs(T @ V - V * w).max() / scale)
+    print("n = %d: eigenvalues %.2e (bound %.1e), orthonormality %.2e (%.1e), residual %.2e (%.1e)"
+          % (n, errs[0], 1e-13 * f, errs[1], 1e-12 * f, errs[2], 1e-12 * f))
+    assert errs[0] < 1e-13 * f
+    assert errs[1] < 1e-12 * f
+    assert errs[2] < 1e-12 * f
+
+
+@pytest.mark.parametrize("inject", [0, 3])
+def test_eigh_clustered_tridiagonal_real_route(ctx, inject, monkeypatch):
+    """The clustered matrices of test_eigh_clustered_tridiagonal through dmk_eigh_batched_real: eigh_kernel runs every phase
+    alone (n = 189 on the <4, *> instantiation), so its own inverse iteration, cluster Gram-Schmidt, acceptance test and --
+    with DMK_EIGH_INJECT -- repair path meet clustered spectra directly."""
+    from libdmet_preview_amd._lib import lib
+    if inject:
+        monkeypatch.setenv("DMK_EIGH_INJECT", str(inject))
+    else:
+        monkeypatch.delenv("DMK_EIGH_INJECT", raising=False)
+    for T in _clustered_mats():
+        n = T.shape[0]
+        dA = ctx.to_device(T[None])
+        dw, dV = ctx.empty((1, n), np.float64), ctx.empty((1, n, n), np.float64)
+        ctx.check(lib.dmk_eigh_batched_real(ctx.h, n, 1, dA.ptr, dw.ptr, dV.ptr))
+        _check_clustered(T, dw.get()[0], dV.get()[0].T)
+
+
+def test_eigh_clustered_tridiagonal_without_tripairs(ctx, monkeypatch):
+    """DMK_EIGH_TRIPAIRS=0 (read on every call): behind the resident tridiagonalisation the first pass of eigh_kernel's
+    phase 2 then computes every eigenpair of the n = 84 and n = 189 clustered matrices, not only those of flagged matrices."""
+    from libdmet_preview_amd.routine import mfd
+    monkeypatch.setenv("DMK_EIGH_TRIPAIRS", "0")
+    monkeypatch.delenv("DMK_EIGH_INJECT", raising=False)
+    mats = _clustered_mats()
+    for T in (mats[2], mats[1]):
+        n = T.shape[0]
+        dw, dVt = mfd.eigh_dev(ctx, ctx.to_device(T[None].astype(np.complex128)), n, 1)
+        _check_clustered(T, dw.get()[0], dVt.get()[0].T)
+
+
 def test_eigh_above_1024(ctx):
     """One real symmetric 1100 x 1100 matrix: the R = 32 column-slice variant behind the eig-flavoured bath of larger
     model lattices (routine/slater.py:224-318 has no size limit; here n <= 2000, one workgroup per matrix)."""
