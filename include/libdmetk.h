@@ -710,6 +710,49 @@ int dmk_mp2_uhf(dmk_ctx *ctx, int nocc_a, int nvir_a, int nocc_b, int nvir_b, co
                 const double *e_occ_a, const double *e_vir_a, const double *e_occ_b, const double *e_vir_b, double *e_corr_dev,
                 double *doo_a, double *dvv_a, double *doo_b, double *dvv_b, double *t2aa, double *t2ab, double *t2bb);
 
+/* ---- restricted CCSD (solver/cc.py:905-906, :1029 of the reference) ------------------------------
+ * The particle-particle ladder on the 4-fold packed (vv|vv) block, never unpacked:
+ *     out[r][a][b] = beta out[r][a][b] + alpha sum_cd tau[r][c][d] (ac|bd)          r < m; tau, out: m x nvir x nvir, contiguous
+ * vvvv_s4 is what dmk_ao2mo_s4 writes with DMK_AO2MO_PACK_BRA | DMK_AO2MO_PACK_KET for four virtual column ranges: rows pair(a,c),
+ * columns pair(b,d), pitch ld >= npair_v.  v_mfma_f64_16x16x4_f64; the operand loader expands the packed triangle on the fly.
+ * No symmetry of tau is assumed.  Fixed-order sums, no atomics: bit-reproducible.  m >= 1, 1 <= nvir <= 512, ld >= npair_v (others:
+ * DMK_ERR_INVALID before any launch).  All offsets 64-bit.  The launch is enqueued on the context's stream. */
+int dmk_cc_ladder_s4(dmk_ctx *ctx, int64_t m, int nvir, const double *vvvv_s4, int64_t ld, const double *tau, double alpha, double beta,
+                     double *out);
+/* Closed-shell CCSD amplitudes and correlation energy with a general (non-canonical) Fock matrix; the equations are stated in
+ * DESIGN.md K21.  fock_mo (n x n, n = nocc + nvir, [occupied | virtual] order) is copied at create; the integral blocks are
+ * BORROWED and must outlive the handle: oooo, ovoo, ovov, oovv, ovvo, ovvv unpacked as dmk_ao2mo_s4 writes them ((pq|rs) at
+ * [p][q][r][s] of the named ranges) and the packed (vv|vv) block of dmk_cc_ladder_s4.  Amplitudes: t1 (nocc, nvir), t2 (nocc, nocc,
+ * nvir, nvir) with t2[i][j][a][b] = t_ij^ab.  Denominators from the Fock diagonal.  0 <= diis_dim <= 12 (0: plain iteration).
+ *   dmk_rccsd_plan   (HOST, no context) bytes_host[2]: bytes of the handle's own allocation and of its contraction workspace, both
+ *                    made at create; DMK_ERR_INVALID for nocc, nvir outside [1, 512] or diis_dim outside [0, 12]
+ *   dmk_rccsd_init   t1 = f_ia / D_ia, t2 = (ia|jb) / D_ijab (the MP2 guess); DMK_RCCSD_EMP2 of dmk_rccsd_get is then the
+ *                    MP2 energy sum (2 (ia|jb) - (ib|ja)) t_ij^ab of its doubles
+ *   dmk_rccsd_set    device amplitudes of the caller
+ *   dmk_rccsd_energy *e_dev = 2 sum f_ia t_ia + sum (2 (ia|jb) - (ib|ja)) (t_ij^ab + t_i^a t_j^b) of the current amplitudes
+ *   dmk_rccsd_update ONE application of the amplitude equations to the current amplitudes (no DIIS)
+ *   dmk_rccsd_run    per iteration: update, energy, DIIS on the concatenated (t1, t2) vector with the steps new - old as error vectors
+ *                    (ring and Gram row on the device, dmk_diis_coeffs on the host, the extrapolation a device linear combination);
+ *                    ONE record of at most 13 doubles is read back per iteration.  Starts from the current amplitudes (the MP2
+ *                    guess when there are none).  Converged when |dE| < tol_e and |dt|_2 < tol_normt; the amplitudes kept are then
+ *                    the un-extrapolated ones the energy belongs to.  result_host[5]: e_corr, converged (0 | 1), iterations, |dt|,
+ *                    last dE
+ *   dmk_rccsd_get    copies to device memory of the caller: DMK_RCCSD_T1, DMK_RCCSD_T2, DMK_RCCSD_EMP2 (one double; set by init)
+ * Every call returns after the stream drained.  DMK_ERR_STATE where amplitudes are needed and there are none. */
+typedef struct dmk_rccsd dmk_rccsd;
+enum { DMK_RCCSD_T1 = 0, DMK_RCCSD_T2 = 1, DMK_RCCSD_EMP2 = 2 };
+int dmk_rccsd_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host /*[2]*/);
+int dmk_rccsd_create(dmk_ctx *ctx, int nocc, int nvir, const double *fock_mo, const double *oooo, const double *ovoo, const double *ovov,
+                     const double *oovv, const double *ovvo, const double *ovvv, const double *vvvv_s4, int64_t ld_vvvv, int diis_dim,
+                     dmk_rccsd **out);
+int dmk_rccsd_init(dmk_rccsd *h);
+int dmk_rccsd_set(dmk_rccsd *h, const double *t1, const double *t2);
+int dmk_rccsd_energy(dmk_rccsd *h, double *e_dev);
+int dmk_rccsd_update(dmk_rccsd *h);
+int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, double *result_host /*[5]*/);
+int dmk_rccsd_get(dmk_rccsd *h, int what, double *out);
+int dmk_rccsd_free(dmk_rccsd *h);
+
 /* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
  * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the
  * indicator of the nimp impurity indices imp_idx_host (host int32, inside [0, n), no repeats; nimp = 0 is legal):

@@ -150,6 +150,16 @@ PROTOTYPES = {
     "dmk_mp2_rhf": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "dmk_mp2_uhf": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                             c_vp, c_vp, c_vp]),
+    "dmk_cc_ladder_s4": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_dbl, c_dbl, c_vp]),
+    "dmk_rccsd_plan": (c_int, [c_int, c_int, c_int, P(c_i64)]),
+    "dmk_rccsd_create": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, P(c_vp)]),
+    "dmk_rccsd_init": (c_int, [c_vp]),
+    "dmk_rccsd_set": (c_int, [c_vp, c_vp, c_vp]),
+    "dmk_rccsd_energy": (c_int, [c_vp, c_vp]),
+    "dmk_rccsd_update": (c_int, [c_vp]),
+    "dmk_rccsd_run": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_vp]),
+    "dmk_rccsd_get": (c_int, [c_vp, c_int, c_vp]),
+    "dmk_rccsd_free": (c_int, [c_vp]),
     "dmk_dmet_h2_scaled":(c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
     "dmk_rho_glob": (c_int, [c_vp, _int3, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "dmk_sym_norm_bound": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),

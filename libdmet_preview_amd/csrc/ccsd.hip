@@ -1,0 +1,716 @@
+// K21 -- restricted (closed-shell) CCSD on the device: the T1 / T2 amplitude equations with a general, non-canonical Fock matrix
+// and the correlation energy, over the MO blocks that dmk_ao2mo_s4 writes.  Replaces cc.CCSD(mf).kernel() behind the reference's
+// CCSD.run (solver/cc.py:905-906, :1029) for a restricted Hamiltonian.  The equations are stated in DESIGN.md K21.
+//
+// cc_ladder_kernel   THE HOT KERNEL, the particle-particle ladder out[r][a][b] (+)= sum_cd tau[r][c][d] (ac|bd), the only
+//                    O(o^2 v^4) term, on the 4-fold PACKED (vv|vv) block (rows pair(a,c), columns pair(b,d)); the v^4 tensor is never
+//                    unpacked to memory.  For fixed a (the batch) it is a GEMM  M = rows r, N = b, K = (c, d)  whose B operand
+//                    B[(c,d)][b] = row pair(a,c) at pair(max(b,d), min(b,d)) the loader expands from the packed triangle on the fly
+//                    through LDS.  The tile geometry is the one of ao2mo.hip (K19): 64 x 64 workgroup tile, K tile 16, four waves of
+//                    2 x 2 v_mfma_f64_16x16x4_f64 accumulators, k-major LDS tiles of pitch 81 doubles, two stages, one barrier per K
+//                    tile.  K runs over c (outer) and 16-wide chunks of d (inner), so c and the chunk are workgroup-uniform and the
+//                    loader divides nothing.  Where the chunk of d lies at or above the tile's b (d >= b: the triangle is contiguous
+//                    along b) the lanes of a load run along b, elsewhere along d.  Fixed-order sums, no atomics.
+// cc_perm_*_kernel   out = alpha perm(in) + beta out for any order of up to four indices: 32 x 32 transposes through LDS between
+//                    the fastest index of the source and the fastest index of the destination (256-byte runs on both sides), or a
+//                    plain strided copy where the two are the same index.
+// Contract           every other term: a two-operand contraction named by its index letters is  permute (only where the operand is
+//                    not already [free, summed] or [summed, free])  ->  dmk_dgemm_batched  ->  permute-accumulate (only where the
+//                    product's index order differs from the destination's).  No host loops over elements, no host round trips.
+// dmk_rccsd          the handle: amplitudes, intermediates, DIIS ring (one allocation) and the contraction workspace (another).
+#include "devres.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+namespace {
+
+constexpr int NT = 256, BM = 64, BN = 64, BK = 16, LDT = 81;
+constexpr int DOT_GRID = 1024, DIIS_MAX = 12;
+
+long long pair_of(long long k) { return k * (k + 1) / 2; }
+
+struct Ladder {
+    long long m; int v;
+    const double *W; long long ld;
+    const double *tau; double alpha, beta; double *out;
+};
+
+__global__ __launch_bounds__(NT) void cc_ladder_kernel(Ladder g) {
+    __shared__ double As[2][BK][LDT], Bs[2][BK][LDT];
+    const int v = g.v;
+    const long long vv = (long long)v * v;
+    const int tilesN = (v + BN - 1) / BN;
+    const long long tilesM = (g.m + BM - 1) / BM;
+    long long bid = blockIdx.x;
+    const int tn = (int)(bid % tilesN); bid /= tilesN;
+    const long long tm = bid % tilesM;
+    const int a = (int)(bid / tilesM);
+    const long long m0 = tm * BM;
+    const int n0 = tn * BN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x = lane & 15, q = lane >> 4;
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+    const int c64 = tid & 63, k4 = tid >> 6;          // lanes along b: k = k4 + 4 j
+    const int kg = tid & 15, mg = tid >> 4;           // lanes along k: row / column mg + 16 j
+    const int nd = (v + BK - 1) / BK;                 // chunks of d per c
+    const int nk = v * nd;
+
+    double ra[4], rb[4];
+    auto along_b = [&](int d0) { return d0 >= n0 + BN / 2; };
+    auto load = [&](int t) {
+        const int c = t / nd, d0 = (t - c * nd) * BK;
+        const int hi = a > c ? a : c, lo = a > c ? c : a;
+        const double *row = g.W + ((long long)hi * (hi + 1) / 2 + lo) * g.ld;
+        const double *ta = g.tau + (long long)c * v + d0 + kg;
+        const bool ab = along_b(d0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long m = m0 + mg + 16 * j;
+            ra[j] = (m < g.m && d0 + kg < v) ? ta[m * vv] : 0.0;
+            const int d = ab ? d0 + k4 + 4 * j : d0 + kg;
+            const int b = ab ? n0 + c64 : n0 + mg + 16 * j;
+            const int h = b > d ? b : d, l = b > d ? d : b;
+            rb[j] = (b < v && d < v) ? row[(long long)h * (h + 1) / 2 + l] : 0.0;
+        }
+    };
+    auto stage = [&](int buf, int t) {
+        const int c = t / nd, d0 = (t - c * nd) * BK;
+        const bool ab = along_b(d0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            As[buf][kg][mg + 16 * j] = ra[j];
+            if (ab) Bs[buf][k4 + 4 * j][c64] = rb[j];
+            else Bs[buf][kg][mg + 16 * j] = rb[j];
+        }
+    };
+
+    d4_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
+    load(0);
+    stage(0, 0);
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < nk; ++t) {
+        const int buf = t & 1;
+        if (t + 1 < nk) load(t + 1);
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+            double fa[2], fb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                fa[i] = As[buf][4 * kk + q][wm + 16 * i + x];
+                fb[i] = Bs[buf][4 * kk + q][wn + 16 * i + x];
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        }
+        if (t + 1 < nk) stage(buf ^ 1, t + 1);      // the other stage was last read before the previous barrier
+        __syncthreads();
+    }
+    // D layout: row = (lane >> 4) + 4 r, column = lane & 15
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long m = m0 + wm + 16 * i + q + 4 * r;
+                const int b = n0 + wn + 16 * j + x;
+                if (m >= g.m || b >= v) continue;
+                double *p = g.out + m * vv + (long long)a * v + b;
+                const double s = g.alpha * acc[i][j][r];
+                *p = g.beta != 0.0 ? s + g.beta * *p : s;
+            }
+}
+
+int ladder_launch(dmk_ctx *ctx, const Ladder &g) {
+    const long long tilesM = (g.m + BM - 1) / BM, tilesN = (g.v + BN - 1) / BN;
+    const long long blocks = tilesM * tilesN * g.v;
+    if (blocks > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4: a launch of %lld workgroups", blocks);
+    FamScope fs(ctx, DMK_FAM_DGEMM);
+    fs.mfma_flops(2.0 * BM * BN * BK * (double)g.v * ((g.v + BK - 1) / BK) * (double)blocks);
+    hipLaunchKernelGGL(cc_ladder_kernel, dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, g);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+// ---- permute-and-combine -------------------------------------------------------------------------------------------------------
+// Source axes 0..3 (row-major, axis 3 fastest) of extents d[], each with the stride os[] it has in the destination.
+struct PermLin { long long d[4], os[4]; };
+
+__global__ __launch_bounds__(NT) void cc_perm_lin_kernel(long long total, PermLin p, double alpha, const double *__restrict__ in, double beta,
+                                                         double *__restrict__ out) {
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
+        long long r = e;
+        const long long i3 = r % p.d[3]; r /= p.d[3];
+        const long long i2 = r % p.d[2]; r /= p.d[2];
+        const long long i1 = r % p.d[1], i0 = r / p.d[1];
+        double *q = out + i0 * p.os[0] + i1 * p.os[1] + i2 * p.os[2] + i3 * p.os[3];
+        const double s = alpha * in[e];
+        *q = beta != 0.0 ? s + beta * *q : s;
+    }
+}
+
+// plane (x: fastest axis of the source, y: fastest axis of the destination), the other two axes r, s are the batch
+struct PermTile { long long dx, dy, dr, ds, isy, isr, iss, osx, osr, oss; };
+
+__global__ __launch_bounds__(NT) void cc_perm_tile_kernel(PermTile p, double alpha, const double *__restrict__ in, double beta,
+                                                          double *__restrict__ out) {
+    __shared__ double tile[32][33];
+    const long long tcx = (p.dx + 31) / 32, tcy = (p.dy + 31) / 32;
+    long long bid = blockIdx.x;
+    const long long x0 = (bid % tcx) * 32; bid /= tcx;
+    const long long y0 = (bid % tcy) * 32; bid /= tcy;
+    const long long s = bid % p.ds, r = bid / p.ds;
+    in += r * p.isr + s * p.iss;
+    out += r * p.osr + s * p.oss;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long y = y0 + ty + 8 * k, xx = x0 + tx;
+        if (y < p.dy && xx < p.dx) tile[ty + 8 * k][tx] = in[y * p.isy + xx];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long xx = x0 + ty + 8 * k, y = y0 + tx;
+        if (y < p.dy && xx < p.dx) {
+            double *q = out + xx * p.osx + y;
+            const double w = alpha * tile[tx][ty + 8 * k];
+            *q = beta != 0.0 ? w + beta * *q : w;
+        }
+    }
+}
+
+// ---- elementwise ---------------------------------------------------------------------------------------------------------------
+// out[i][j][a][b] = c2 t2[i][j][a][b] + c1 t1[i][a] t1[j][b]
+__global__ __launch_bounds__(NT) void cc_tau_kernel(int o, int v, double c2, double c1, const double *__restrict__ t1,
+                                                    const double *__restrict__ t2, double *__restrict__ out) {
+    const long long vv = (long long)v * v, total = (long long)o * o * vv;
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
+        const long long ij = e / vv, ab = e % vv;
+        const int i = (int)(ij / o), j = (int)(ij % o), a = (int)(ab / v), b = (int)(ab % v);
+        out[e] = c2 * t2[e] + c1 * t1[(long long)i * v + a] * t1[(long long)j * v + b];
+    }
+}
+
+// out = in / D: D_ia = e_i - e_a (two == 0, in (o, v)) or D_ijab = e_i + e_j - e_a - e_b (in (o, o, v, v))
+__global__ __launch_bounds__(NT) void cc_div_kernel(int o, int v, int two, const double *__restrict__ in, const double *__restrict__ eo,
+                                                    const double *__restrict__ ev, double *__restrict__ out) {
+    const long long vv = two ? (long long)v * v : v, total = (two ? (long long)o * o : o) * vv;
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
+        const long long ij = e / vv, ab = e % vv;
+        double d;
+        if (two) d = (eo[ij / o] + eo[ij % o]) - (ev[ab / v] + ev[ab % v]);
+        else d = eo[ij] - ev[ab];
+        out[e] = in[e] / d;
+    }
+}
+
+// the Fock matrix (n x n) cut into f_oo and f_vv without their diagonals, f_ov, and the diagonals
+__global__ __launch_bounds__(NT) void cc_fock_split_kernel(int o, int v, const double *__restrict__ f, double *__restrict__ foo,
+                                                           double *__restrict__ fvv, double *__restrict__ fov, double *__restrict__ eo,
+                                                           double *__restrict__ ev) {
+    const int n = o + v;
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < (long long)n * n; e += (long long)gridDim.x * NT) {
+        const int p = (int)(e / n), q = (int)(e % n);
+        const double x = f[e];
+        if (p < o && q < o) { foo[(long long)p * o + q] = p == q ? 0.0 : x; if (p == q) eo[p] = x; }
+        else if (p >= o && q >= o) { fvv[(long long)(p - o) * v + q - o] = p == q ? 0.0 : x; if (p == q) ev[p - o] = x; }
+        else if (p < o) fov[(long long)p * v + q - o] = x;
+    }
+}
+
+// partial[block] = sum x y over a fixed grid; then *out = (acc ? *out : 0) + scale sum partial, one workgroup, fixed order
+__global__ __launch_bounds__(NT) void cc_dot_kernel(long long n, const double *__restrict__ x, const double *__restrict__ y,
+                                                    double *__restrict__ partial) {
+    __shared__ double red[NT];
+    double s = 0.0;
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < n; e += (long long)gridDim.x * NT) s = fma(x[e], y[e], s);
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = NT / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(NT) void cc_sum_kernel(int count, const double *__restrict__ partial, double scale, int acc, double *__restrict__ out) {
+    __shared__ double red[NT];
+    double s = 0.0;
+    for (int t = threadIdx.x; t < count; t += NT) s += partial[t];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = NT / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = (acc ? *out : 0.0) + scale * red[0];
+}
+
+// out = sum_q c[q] x_q, x_q = base + q stride
+struct LinComb { int m; double c[DIIS_MAX]; };
+__global__ __launch_bounds__(NT) void cc_lincomb_kernel(long long n, LinComb L, const double *__restrict__ base, long long stride,
+                                                        double *__restrict__ out) {
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < n; e += (long long)gridDim.x * NT) {
+        double s = 0.0;
+        for (int q = 0; q < L.m; ++q) s = fma(L.c[q], base[q * stride + e], s);
+        out[e] = s;
+    }
+}
+
+int grid_of(long long n) { return std::max(1, dmk_grid1d(n, 4096)); }
+
+// ---- the contraction engine ------------------------------------------------------------------------------------------------------
+// Index letters: i j k l occupied, a b c d virtual.  Tensors are row-major in the order of their letters.
+struct Engine {
+    dmk_ctx *ctx = nullptr;
+    int o = 0, v = 0;
+    double *PA = nullptr, *PB = nullptr, *PC = nullptr;      // scratch of `big` doubles each
+
+    long long dim(char c) const { return c >= 'i' ? o : v; }
+    long long count(const std::string &s) const { long long n = 1; for (char c : s) n *= dim(c); return n; }
+
+    // out (order so) = alpha in (order si) + beta out
+    int perm(double alpha, const double *in, const char *si, double beta, double *out, const char *so) const {
+        const int nd = (int)std::strlen(si), off = 4 - nd;
+        if (nd < 1 || nd > 4 || (int)std::strlen(so) != nd) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: permute '%s' -> '%s'", si, so);
+        long long d[4] = {1, 1, 1, 1}, is[4] = {0, 0, 0, 0}, os[4] = {0, 0, 0, 0}, ost[4];
+        for (int k = 0; k < nd; ++k) d[off + k] = dim(si[k]);
+        is[3] = 1;
+        for (int k = 2; k >= 0; --k) is[k] = is[k + 1] * d[k + 1];
+        long long run = 1;
+        for (int q = nd - 1; q >= 0; --q) { ost[q] = run; run *= dim(so[q]); }
+        for (int k = 0; k < nd; ++k) {
+            const char *w = std::strchr(so, si[k]);
+            if (!w) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: permute '%s' -> '%s'", si, so);
+            os[off + k] = ost[w - so];
+        }
+        const long long total = d[0] * d[1] * d[2] * d[3];
+        FamScope fs(ctx, DMK_FAM_MISC);
+        if (os[3] == 1) {
+            PermLin p;
+            for (int k = 0; k < 4; ++k) { p.d[k] = d[k]; p.os[k] = os[k]; }
+            hipLaunchKernelGGL(cc_perm_lin_kernel, dim3(grid_of(total)), dim3(NT), 0, ctx->stream, total, p, alpha, in, beta, out);
+        } else {
+            int y = -1, rs[2], nrs = 0;
+            for (int k = 0; k < 3; ++k) { if (os[k] == 1 && d[k] > 1 && y < 0) y = k; }
+            if (y < 0) for (int k = 0; k < 3; ++k) if (os[k] == 1 && y < 0) y = k;
+            if (y < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: permute '%s' -> '%s' has no unit stride", si, so);
+            for (int k = 0; k < 3; ++k) if (k != y) rs[nrs++] = k;
+            PermTile p{d[3], d[y], d[rs[0]], d[rs[1]], is[y], is[rs[0]], is[rs[1]], os[3], os[rs[0]], os[rs[1]]};
+            const long long blocks = ((p.dx + 31) / 32) * ((p.dy + 31) / 32) * p.dr * p.ds;
+            if (blocks > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: a permute of %lld tiles", blocks);
+            hipLaunchKernelGGL(cc_perm_tile_kernel, dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, p, alpha, in, beta, out);
+        }
+        DMK_CHECK_LAUNCH(ctx);
+        return DMK_OK;
+    }
+
+    // C = alpha op(A) op(B) + beta C with M cut so that no launch exceeds the grid's second dimension
+    int gemm(int opA, int opB, long long M, long long N, long long K, double alpha, const double *A, const double *B, double beta,
+             double *C) const {
+        if (N > 0x7fffffffLL || K > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: a product of %lld x %lld x %lld", M, N, K);
+        const long long lda = opA ? M : K, ldb = opB ? K : N, chunk = 32LL * 65535;
+        for (long long m0 = 0; m0 < M; m0 += chunk) {
+            const int mc = (int)std::min(chunk, M - m0);
+            const int rc = dmk_dgemm_batched(ctx, opA, opB, mc, (int)N, (int)K, 1, alpha, A + (opA ? m0 : m0 * lda), lda, 0, B, ldb, 0, beta,
+                                             C + m0 * N, N, 0);
+            if (rc) return rc;
+        }
+        return DMK_OK;
+    }
+
+    // C[sc] = alpha sum_(letters shared by sa and sb) A[sa] B[sb] + beta C[sc]
+    int contract(double alpha, const double *A, const char *sa, const double *B, const char *sb, double beta, double *C,
+                 const char *sc) const {
+        std::string FA, K, FB;
+        for (const char *p = sa; *p; ++p) (std::strchr(sb, *p) ? K : FA) += *p;
+        for (const char *p = sb; *p; ++p) if (!std::strchr(sa, *p)) FB += *p;
+        int opA = 0, opB = 0, rc;
+        if (FA + K == sa) opA = 0;
+        else if (K + FA == sa) opA = 1;
+        else { if ((rc = perm(1.0, A, sa, 0.0, PA, (FA + K).c_str()))) return rc; A = PA; }
+        if (K + FB == sb) opB = 0;
+        else if (FB + K == sb) opB = 1;
+        else { if ((rc = perm(1.0, B, sb, 0.0, PB, (K + FB).c_str()))) return rc; B = PB; }
+        const long long M = count(FA), N = count(FB), Kd = count(K);
+        const std::string prod = FA + FB;
+        if (prod == sc) return gemm(opA, opB, M, N, Kd, alpha, A, B, beta, C);
+        if ((rc = gemm(opA, opB, M, N, Kd, alpha, A, B, 0.0, PC))) return rc;
+        return perm(1.0, PC, prod.c_str(), beta, C, sc);
+    }
+};
+
+long long pad32(long long k) { return (k + 31) / 32 * 32; }
+long long big_of(long long o, long long v) { return std::max(std::max(o * o * o * o, o * o * o * v), std::max(o * o * v * v, o * v * v * v)); }
+
+struct Carver {
+    char *p;
+    explicit Carver(void *base) : p(static_cast<char *>(base)) {}
+    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += dmk_align256((size_t)std::max<long long>(count, 1) * 8); return q; }
+};
+
+}  // namespace
+
+struct dmk_rccsd {
+    dmk_ctx *ctx = nullptr;
+    int o = 0, v = 0, diis = 0;
+    long long nx = 0, t2off = 0;
+    const double *oooo = nullptr, *ovoo = nullptr, *ovov = nullptr, *oovv = nullptr, *ovvo = nullptr, *ovvv = nullptr, *vvvv = nullptr;
+    long long ld_vvvv = 0;
+    DevMem mem, ws;
+    Engine E;
+    double *x = nullptr, *xnew = nullptr, *ring_x = nullptr, *ring_e = nullptr;
+    double *Lovov, *Lt, *tau, *tau2, *R, *S, *Wvoov, *Wvovo, *Woooo, *Y, *Q;
+    double *foo, *Foo, *Loo, *X1, *X2, *fvv, *Fvv, *Lvv, *fov, *Fov, *n1, *eo, *ev, *part, *rec;
+    bool have_amps = false;
+
+    // what the carve lays out; with a null base: the bytes
+    size_t carve(void *base) {
+        Carver c(base);
+        const long long oo = (long long)o * o, vv = (long long)v * v, ov = (long long)o * v, t2n = oo * vv;
+        x = c.take(nx); xnew = c.take(nx);
+        ring_x = reinterpret_cast<double *>(c.p);
+        for (int q = 0; q < diis; ++q) c.take(nx);
+        ring_e = reinterpret_cast<double *>(c.p);
+        for (int q = 0; q < diis; ++q) c.take(nx);
+        Lovov = c.take(t2n); Lt = c.take(t2n); tau = c.take(t2n); tau2 = c.take(t2n); R = c.take(t2n); S = c.take(t2n);
+        Wvoov = c.take(t2n); Wvovo = c.take(t2n);
+        Woooo = c.take(oo * oo); Y = c.take(oo * ov); Q = c.take(oo * ov);
+        foo = c.take(oo); Foo = c.take(oo); Loo = c.take(oo); X1 = c.take(oo); X2 = c.take(oo);
+        fvv = c.take(vv); Fvv = c.take(vv); Lvv = c.take(vv);
+        fov = c.take(ov); Fov = c.take(ov); n1 = c.take(ov);
+        eo = c.take(o); ev = c.take(v);
+        part = c.take(2048); rec = c.take(16);
+        return (size_t)(c.p - static_cast<char *>(base));
+    }
+    long long ring_stride() const { return (long long)(dmk_align256((size_t)nx * 8) / 8); }
+};
+
+namespace {
+
+void plan_bytes(int o, int v, int diis, int64_t *bytes) {
+    dmk_rccsd h;
+    h.o = o; h.v = v; h.diis = diis;
+    h.nx = pad32((long long)o * v) + (long long)o * o * v * v;
+    bytes[0] = (int64_t)h.carve(nullptr);
+    bytes[1] = 3 * (int64_t)dmk_align256((size_t)big_of(o, v) * 8);
+}
+
+int cc_dot(dmk_rccsd *h, long long n, const double *x, const double *y, double scale, int acc, double *out) {
+    dmk_ctx *ctx = h->ctx;
+    FamScope fs(ctx, DMK_FAM_MISC);
+    const int grid = (int)std::min<long long>(DOT_GRID, (n + NT - 1) / NT);
+    hipLaunchKernelGGL(cc_dot_kernel, dim3(grid), dim3(NT), 0, ctx->stream, n, x, y, h->part);
+    hipLaunchKernelGGL(cc_sum_kernel, dim3(1), dim3(NT), 0, ctx->stream, grid, h->part, scale, acc, out);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+int cc_tau(dmk_rccsd *h, double c2, double c1, const double *amp, double *out) {
+    dmk_ctx *ctx = h->ctx;
+    FamScope fs(ctx, DMK_FAM_MISC);
+    hipLaunchKernelGGL(cc_tau_kernel, dim3(grid_of((long long)h->o * h->o * h->v * h->v)), dim3(NT), 0, ctx->stream, h->o, h->v, c2, c1, amp,
+                       amp + h->t2off, out);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+int cc_div(dmk_rccsd *h, int two, const double *in, double *out) {
+    dmk_ctx *ctx = h->ctx;
+    FamScope fs(ctx, DMK_FAM_MISC);
+    const long long n = two ? (long long)h->o * h->o * h->v * h->v : (long long)h->o * h->v;
+    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(n)), dim3(NT), 0, ctx->stream, h->o, h->v, two, in, h->eo, h->ev, out);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+// *e_dev = 2 f_ia t_ia + sum (2 (ia|jb) - (ib|ja)) tau_ij^ab of the amplitude vector `amp` (h->tau is overwritten)
+int cc_energy(dmk_rccsd *h, const double *amp, double *e_dev) {
+    int rc;
+    if ((rc = cc_tau(h, 1.0, 1.0, amp, h->tau))) return rc;
+    if ((rc = cc_dot(h, (long long)h->o * h->v, h->fov, amp, 2.0, 0, e_dev))) return rc;
+    return cc_dot(h, (long long)h->o * h->o * h->v * h->v, h->Lt, h->tau, 1.0, 1, e_dev);
+}
+
+#define CT(alpha, A, sa, B, sb, beta, C, sc) do { if ((rc = E.contract(alpha, A, sa, B, sb, beta, C, sc))) return rc; } while (0)
+#define PM(alpha, in, si, beta, out, so) do { if ((rc = E.perm(alpha, in, si, beta, out, so))) return rc; } while (0)
+
+// one application of the amplitude equations to the vector `src`, the new amplitudes into `dst`
+int cc_update(dmk_rccsd *h, const double *src, double *dst) {
+    const Engine &E = h->E;
+    const double *t1 = src, *t2 = src + h->t2off;
+    const double *oooo = h->oooo, *ovoo = h->ovoo, *ovov = h->ovov, *oovv = h->oovv, *ovvo = h->ovvo, *ovvv = h->ovvv;
+    double *tau = h->tau, *tau2 = h->tau2, *R = h->R, *S = h->S, *Wvoov = h->Wvoov, *Wvovo = h->Wvovo, *Woooo = h->Woooo, *Y = h->Y, *Q = h->Q;
+    double *Foo = h->Foo, *Loo = h->Loo, *X1 = h->X1, *X2 = h->X2, *Fvv = h->Fvv, *Lvv = h->Lvv, *Fov = h->Fov, *n1 = h->n1;
+    const double *fov = h->fov, *L = h->Lovov;
+    int rc;
+    if ((rc = cc_tau(h, 1.0, 1.0, src, tau))) return rc;
+    if ((rc = cc_tau(h, 0.5, 1.0, src, tau2))) return rc;
+    // Fock-like intermediates (the diagonals of f_oo / f_vv are on the other side: the denominators)
+    PM(1.0, fov, "kc", 0.0, Fov, "kc");       CT(1.0, L, "kcld", t1, "ld", 1.0, Fov, "kc");
+    PM(1.0, h->foo, "ki", 0.0, Foo, "ki");    CT(1.0, L, "kcld", tau, "ilcd", 1.0, Foo, "ki");
+    PM(1.0, h->fvv, "ac", 0.0, Fvv, "ac");    CT(-1.0, L, "kcld", tau, "klad", 1.0, Fvv, "ac");
+    CT(1.0, fov, "kc", t1, "ic", 0.0, X1, "ki");
+    PM(1.0, Foo, "ki", 0.0, Loo, "ki");       PM(1.0, X1, "ki", 1.0, Loo, "ki");
+    CT(2.0, ovoo, "lcki", t1, "lc", 1.0, Loo, "ki");    CT(-1.0, ovoo, "kcli", t1, "lc", 1.0, Loo, "ki");
+    PM(1.0, Fvv, "ac", 0.0, Lvv, "ac");       CT(-1.0, fov, "kc", t1, "ka", 1.0, Lvv, "ac");
+    CT(2.0, ovvv, "kdac", t1, "kd", 1.0, Lvv, "ac");    CT(-1.0, ovvv, "kcad", t1, "kd", 1.0, Lvv, "ac");
+    CT(1.0, Fov, "kc", t1, "ic", 0.0, X2, "ki");
+    // T1
+    PM(1.0, fov, "ia", 0.0, n1, "ia");
+    CT(-2.0, X1, "ki", t1, "ka", 1.0, n1, "ia");
+    CT(1.0, Fvv, "ac", t1, "ic", 1.0, n1, "ia");
+    CT(-1.0, Foo, "ki", t1, "ka", 1.0, n1, "ia");
+    CT(2.0, Fov, "kc", t2, "kica", 1.0, n1, "ia");      CT(-1.0, Fov, "kc", t2, "ikca", 1.0, n1, "ia");
+    CT(1.0, X2, "ki", t1, "ka", 1.0, n1, "ia");
+    CT(2.0, ovvo, "kcai", t1, "kc", 1.0, n1, "ia");     CT(-1.0, oovv, "kiac", t1, "kc", 1.0, n1, "ia");
+    CT(2.0, ovvv, "kdac", tau, "ikcd", 1.0, n1, "ia");  CT(-1.0, ovvv, "kcad", tau, "ikcd", 1.0, n1, "ia");
+    CT(-2.0, ovoo, "lcki", tau, "klac", 1.0, n1, "ia"); CT(1.0, ovoo, "kcli", tau, "klac", 1.0, n1, "ia");
+    // T2: R holds the terms that are symmetric under (i a) <-> (j b) as they stand, S those that are symmetrised at the end
+    PM(1.0, ovov, "iajb", 0.0, R, "ijab");
+    CT(1.0, ovvv, "iacb", t1, "jc", 0.0, S, "ijab");
+    CT(1.0, oovv, "kibc", t1, "jc", 0.0, Q, "kibj");    CT(-1.0, Q, "kibj", t1, "ka", 1.0, S, "ijab");
+    CT(-1.0, ovoo, "iajk", t1, "kb", 1.0, S, "ijab");
+    CT(1.0, ovvo, "kcai", t1, "jc", 0.0, Q, "akij");    CT(-1.0, Q, "akij", t1, "kb", 1.0, S, "ijab");
+    PM(1.0, oooo, "kilj", 0.0, Woooo, "klij");
+    CT(1.0, ovoo, "lcki", t1, "jc", 1.0, Woooo, "klij"); CT(1.0, ovoo, "kclj", t1, "ic", 1.0, Woooo, "klij");
+    CT(1.0, ovov, "kcld", tau, "ijcd", 1.0, Woooo, "klij");
+    CT(1.0, Woooo, "klij", tau, "klab", 1.0, R, "ijab");                                  // hole-hole ladder
+    Ladder lad{(long long)h->o * h->o, h->v, h->vvvv, h->ld_vvvv, tau, 1.0, 1.0, R};         // particle-particle ladder
+    if ((rc = ladder_launch(h->ctx, lad))) return rc;
+    CT(1.0, ovvv, "kcbd", tau, "ijcd", 0.0, Y, "ijkb"); CT(-1.0, t1, "ka", Y, "ijkb", 1.0, S, "ijab");
+    CT(1.0, Lvv, "ac", t2, "ijcb", 1.0, S, "ijab");
+    CT(-1.0, Loo, "ki", t2, "kjab", 1.0, S, "ijab");
+    PM(1.0, ovvo, "kcai", 0.0, Wvoov, "akic");
+    CT(1.0, ovvv, "kcad", t1, "id", 1.0, Wvoov, "akic");  CT(-1.0, ovoo, "kcli", t1, "la", 1.0, Wvoov, "akic");
+    CT(-1.0, ovov, "ldkc", tau2, "ilda", 1.0, Wvoov, "akic"); CT(0.5, L, "ldkc", t2, "ilad", 1.0, Wvoov, "akic");
+    PM(1.0, oovv, "kiac", 0.0, Wvovo, "akci");
+    CT(1.0, ovvv, "kdac", t1, "id", 1.0, Wvovo, "akci");  CT(-1.0, ovoo, "lcki", t1, "la", 1.0, Wvovo, "akci");
+    CT(-1.0, ovov, "lckd", tau2, "ilda", 1.0, Wvovo, "akci");
+    CT(2.0, Wvoov, "akic", t2, "kjcb", 1.0, S, "ijab");   CT(-1.0, Wvovo, "akci", t2, "kjcb", 1.0, S, "ijab");
+    CT(-1.0, Wvoov, "akic", t2, "kjbc", 1.0, S, "ijab");
+    CT(-1.0, Wvovo, "bkci", t2, "kjac", 1.0, S, "ijab");
+    PM(1.0, S, "ijab", 1.0, R, "ijab");
+    PM(1.0, S, "jiba", 1.0, R, "ijab");
+    if ((rc = cc_div(h, 0, n1, dst))) return rc;
+    return cc_div(h, 1, R, dst + h->t2off);
+}
+
+int cc_init(dmk_rccsd *h) {
+    const Engine &E = h->E;
+    int rc;
+    if ((rc = cc_div(h, 0, h->fov, h->x))) return rc;
+    PM(1.0, h->ovov, "iajb", 0.0, h->R, "ijab");
+    if ((rc = cc_div(h, 1, h->R, h->x + h->t2off))) return rc;
+    // E(MP2) = sum (2 (ia|jb) - (ib|ja)) t_ij^ab: the doubles alone, as PySCF's init_amps reports it
+    if ((rc = cc_dot(h, h->nx - h->t2off, h->Lt, h->x + h->t2off, 1.0, 0, h->rec + 15))) return rc;
+    h->have_amps = true;
+    return DMK_OK;
+}
+
+#undef CT
+#undef PM
+
+}  // namespace
+
+extern "C" {
+
+int dmk_cc_ladder_s4(dmk_ctx *ctx, int64_t m, int nvir, const double *vvvv_s4, int64_t ld, const double *tau, double alpha, double beta,
+                     double *out) {
+    if (!ctx) return DMK_ERR_INVALID;
+    if (m < 1 || nvir < 1 || nvir > 512 || !vvvv_s4 || !tau || !out)
+        return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4: bad arguments (m >= 1, 1 <= nvir <= 512; block, tau and out)");
+    if (ld < pair_of(nvir)) return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4: row pitch %lld below npair = %lld", (long long)ld, pair_of(nvir));
+    return ladder_launch(ctx, Ladder{(long long)m, nvir, vvvv_s4, (long long)ld, tau, alpha, beta, out});
+}
+
+int dmk_rccsd_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host) {
+    if (!bytes_host || nocc < 1 || nvir < 1 || nvir > 512 || nocc > 512 || diis_dim < 0 || diis_dim > DIIS_MAX) return DMK_ERR_INVALID;
+    plan_bytes(nocc, nvir, diis_dim, bytes_host);
+    return DMK_OK;
+}
+
+int dmk_rccsd_create(dmk_ctx *ctx, int nocc, int nvir, const double *fock_mo, const double *oooo, const double *ovoo, const double *ovov,
+                     const double *oovv, const double *ovvo, const double *ovvv, const double *vvvv_s4, int64_t ld_vvvv, int diis_dim,
+                     dmk_rccsd **out) {
+    if (!ctx) return DMK_ERR_INVALID;
+    if (!out || nocc < 1 || nvir < 1 || nocc > 512 || nvir > 512 || !fock_mo || !oooo || !ovoo || !ovov || !oovv || !ovvo || !ovvv || !vvvv_s4)
+        return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_create: bad arguments (1 <= nocc, nvir <= 512; Fock matrix and seven blocks)");
+    if (diis_dim < 0 || diis_dim > DIIS_MAX) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_create: diis_dim %d outside [0, %d]", diis_dim, DIIS_MAX);
+    if (ld_vvvv < pair_of(nvir)) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_create: pitch of the (vv|vv) block below npair");
+    *out = nullptr;
+    dmk_rccsd *h = new dmk_rccsd;
+    h->ctx = ctx; h->o = nocc; h->v = nvir; h->diis = diis_dim;
+    h->t2off = pad32((long long)nocc * nvir);
+    h->nx = h->t2off + (long long)nocc * nocc * nvir * nvir;
+    h->oooo = oooo; h->ovoo = ovoo; h->ovov = ovov; h->oovv = oovv; h->ovvo = ovvo; h->ovvv = ovvv; h->vvvv = vvvv_s4; h->ld_vvvv = ld_vvvv;
+    int64_t bytes[2];
+    plan_bytes(nocc, nvir, diis_dim, bytes);
+    if (h->mem.alloc(ctx, (size_t)bytes[0]) != hipSuccess || h->ws.alloc(ctx, (size_t)bytes[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        delete h;
+        return dmk_fail(ctx, DMK_ERR_NOMEM, "rccsd_create: no device memory for %lld + %lld bytes", (long long)bytes[0], (long long)bytes[1]);
+    }
+    h->carve(h->mem.get<void>());
+    const size_t third = (size_t)bytes[1] / 3;
+    h->E.ctx = ctx; h->E.o = nocc; h->E.v = nvir;
+    h->E.PA = h->ws.get<double>();
+    h->E.PB = reinterpret_cast<double *>(h->ws.get<char>() + third);
+    h->E.PC = reinterpret_cast<double *>(h->ws.get<char>() + 2 * third);
+    int rc = DMK_OK;
+    auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); delete h; return code; };
+    if (hipMemsetAsync(h->mem.get<void>(), 0, (size_t)bytes[0], ctx->stream) != hipSuccess)
+        return fail(dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: memset failed"));
+    {
+        FamScope fs(ctx, DMK_FAM_MISC);
+        const int n = nocc + nvir;
+        hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)n * n)), dim3(NT), 0, ctx->stream, nocc, nvir, fock_mo, h->foo, h->fvv,
+                           h->fov, h->eo, h->ev);
+        if (hipGetLastError() != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: kernel launch failed"));
+    }
+    // L_kcld = 2 (kc|ld) - (kd|lc), and the same in (k, l, c, d) order for the energy
+    if ((rc = h->E.perm(2.0, ovov, "kcld", 0.0, h->Lovov, "kcld"))) return fail(rc);
+    if ((rc = h->E.perm(-1.0, ovov, "kdlc", 1.0, h->Lovov, "kcld"))) return fail(rc);
+    if ((rc = h->E.perm(1.0, h->Lovov, "iajb", 0.0, h->Lt, "ijab"))) return fail(rc);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: the stream failed"));
+    *out = h;
+    return DMK_OK;
+}
+
+int dmk_rccsd_free(dmk_rccsd *h) {
+    if (!h) return DMK_OK;
+    (void)hipStreamSynchronize(h->ctx->stream);      // work that reads the handle's memory may still be queued
+    delete h;
+    return DMK_OK;
+}
+
+int dmk_rccsd_init(dmk_rccsd *h) {
+    if (!h) return DMK_ERR_INVALID;
+    const int rc = cc_init(h);
+    if (rc) return rc;
+    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
+    return DMK_OK;
+}
+
+int dmk_rccsd_set(dmk_rccsd *h, const double *t1, const double *t2) {
+    if (!h) return DMK_ERR_INVALID;
+    if (!t1 || !t2) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_set: NULL amplitudes");
+    dmk_ctx *ctx = h->ctx;
+    DMK_HIP(ctx, hipMemcpyAsync(h->x, t1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipMemcpyAsync(h->x + h->t2off, t2, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h->have_amps = true;
+    return DMK_OK;
+}
+
+int dmk_rccsd_energy(dmk_rccsd *h, double *e_dev) {
+    if (!h) return DMK_ERR_INVALID;
+    if (!e_dev || !h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_energy: no amplitudes yet (init or set first), or a NULL result");
+    const int rc = cc_energy(h, h->x, e_dev);
+    if (rc) return rc;
+    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
+    return DMK_OK;
+}
+
+int dmk_rccsd_update(dmk_rccsd *h) {
+    if (!h) return DMK_ERR_INVALID;
+    if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_update: no amplitudes yet (init or set first)");
+    const int rc = cc_update(h, h->x, h->xnew);
+    if (rc) return rc;
+    std::swap(h->x, h->xnew);
+    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
+    return DMK_OK;
+}
+
+int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, double *result_host) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!result_host || max_iter < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_run: bad arguments");
+    int rc;
+    if (!h->have_amps && (rc = cc_init(h))) return rc;
+    const int dim = h->diis;
+    const long long nx = h->nx, rs = h->ring_stride();
+    double B[DIIS_MAX][DIIS_MAX] = {{0.0}}, rec[16], e_old, e = 0.0, dE = 0.0, dt = 0.0;
+    if ((rc = cc_energy(h, h->x, h->rec))) return rc;
+    DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    e = rec[0];
+    int it = 0, converged = 0, stored = 0;
+    while (it < max_iter) {
+        ++it;
+        const int slot = dim ? (stored % dim) : 0;
+        double *dst = dim ? h->ring_x + slot * rs : h->xnew;
+        // the step new - old: a ring slot (the padding between t1 and t2 is zero in every vector), or n1 / tau2, free between updates
+        double *e1 = dim ? h->ring_e + slot * rs : h->n1, *e2 = dim ? e1 + h->t2off : h->tau2;
+        if ((rc = cc_update(h, h->x, dst))) return rc;
+        if ((rc = cc_energy(h, dst, h->rec))) return rc;
+        if ((rc = h->E.perm(1.0, dst, "ia", 0.0, e1, "ia"))) return rc;
+        if ((rc = h->E.perm(-1.0, h->x, "ia", 1.0, e1, "ia"))) return rc;
+        if ((rc = h->E.perm(1.0, dst + h->t2off, "ijab", 0.0, e2, "ijab"))) return rc;
+        if ((rc = h->E.perm(-1.0, h->x + h->t2off, "ijab", 1.0, e2, "ijab"))) return rc;
+        const int m = dim ? std::min(stored + 1, dim) : 1;
+        if (dim) {
+            for (int q = 0; q < m; ++q)
+                if ((rc = cc_dot(h, nx, e1, h->ring_e + q * rs, 1.0, 0, h->rec + 1 + q))) return rc;
+        } else {
+            if ((rc = cc_dot(h, (long long)h->o * h->v, e1, e1, 1.0, 0, h->rec + 1))) return rc;
+            if ((rc = cc_dot(h, nx - h->t2off, e2, e2, 1.0, 1, h->rec + 1))) return rc;
+        }
+        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, (size_t)(1 + m) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        e_old = e;
+        e = rec[0];
+        dE = e - e_old;
+        dt = std::sqrt(rec[1 + (dim ? slot : 0)]);
+        if (!std::isfinite(e) || !std::isfinite(dt)) return dmk_fail(ctx, DMK_ERR_NOCONV, "rccsd_run: non-finite energy or amplitudes in iteration %d", it);
+        if (std::fabs(dE) < tol_e && dt < tol_normt) converged = 1;
+        if (!dim || converged) {
+            if (dim) DMK_HIP(ctx, hipMemcpyAsync(h->x, dst, (size_t)nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            else std::swap(h->x, h->xnew);
+            if (converged) break;
+            continue;
+        }
+        for (int q = 0; q < m; ++q) B[slot][q] = B[q][slot] = rec[1 + q];
+        ++stored;
+        double Bm[DIIS_MAX * DIIS_MAX];
+        LinComb L{};
+        L.m = m;
+        for (int p = 0; p < m; ++p)
+            for (int q = 0; q < m; ++q) Bm[p * m + q] = B[p][q];
+        if (dmk_diis_coeffs(m, Bm, L.c) != DMK_OK) {          // no usable extrapolation: the newest vector
+            for (int q = 0; q < m; ++q) L.c[q] = q == slot ? 1.0 : 0.0;
+        }
+        {
+            FamScope fs(ctx, DMK_FAM_MISC);
+            hipLaunchKernelGGL(cc_lincomb_kernel, dim3(grid_of(nx)), dim3(NT), 0, ctx->stream, nx, L, h->ring_x, rs, h->x);
+            DMK_CHECK_LAUNCH(ctx);
+        }
+    }
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    result_host[0] = e; result_host[1] = converged; result_host[2] = it; result_host[3] = dt; result_host[4] = dE;
+    return DMK_OK;
+}
+
+int dmk_rccsd_get(dmk_rccsd *h, int what, double *out) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!out || what < DMK_RCCSD_T1 || what > DMK_RCCSD_EMP2) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_get: bad arguments");
+    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_get: no amplitudes yet (init or set first)");
+    const double *src = what == DMK_RCCSD_T1 ? h->x : what == DMK_RCCSD_T2 ? h->x + h->t2off : h->rec + 15;
+    const size_t cnt = what == DMK_RCCSD_T1 ? (size_t)h->o * h->v : what == DMK_RCCSD_T2 ? (size_t)(h->nx - h->t2off) : 1;
+    DMK_HIP(ctx, hipMemcpyAsync(out, src, cnt * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DMK_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,263 @@
+"""
+Restricted (closed-shell) CCSD on the device, over the Hartree-Fock object of solver/scf.py (DeviceHF): DESIGN.md K21.
+
+  RCCSD     the T1 / T2 amplitude equations with a general (non-canonical) Fock matrix and the correlation energy: what
+            cc.CCSD(mf).kernel() does behind the reference's CCSD.run for a restricted Hamiltonian (solver/cc.py:905-906, :1029)
+  run_ccsd  (e_corr, t1, t2) over a solver.scf.SCF whose HF() has run, shaped like mp.run_mp2
+
+The seven MO blocks come from dmk_ao2mo_s4 applied to the ERI block the DeviceHF already holds (the ERI is not uploaded again; the
+(vv|vv) block stays 4-fold packed and is never unpacked), the iteration is dmk_rccsd_run.  Not built, each refusing by name: the
+Lambda equations and the densities (and with them CCSD.run / run_dmet_ham, which return a density), UCCSD and GCCSD, (T), frozen
+orbitals, Brueckner and tailored CC, a level shift other than 0 and a damping other than 1.  The module imports without a GPU.
+"""
+import ctypes as C
+
+import numpy as np
+
+from libdmet_preview_amd._lib import lib, c_vp, c_dbl, c_i64
+from libdmet_preview_amd.solver import scf
+from libdmet_preview_amd.solver._posthf import PostHFBase
+from libdmet_preview_amd.utils import logger as log
+
+_T1, _T2, _EMP2 = range(3)
+_PACK_BOTH = 3          # DMK_AO2MO_PACK_BRA | DMK_AO2MO_PACK_KET
+
+_BLOCKS = ("oooo", "ovoo", "ovov", "oovv", "ovvo", "ovvv", "vvvv")
+
+
+def _not_built(what):
+    raise NotImplementedError("%s is not built (solver.cc has the restricted T equations and the correlation energy only)" % what)
+
+
+def plan_bytes(nocc, nvir, diis_space):
+    """(bytes of the dmk_rccsd handle, bytes of its contraction workspace): dmk_rccsd_plan, host arithmetic."""
+    out = (c_i64 * 2)()
+    rc = lib.dmk_rccsd_plan(int(nocc), int(nvir), int(diis_space), out)
+    if rc != 0:
+        raise ValueError("dmk_rccsd_plan refuses (nocc, nvir, diis_space) = (%d, %d, %d)" % (nocc, nvir, diis_space))
+    return int(out[0]), int(out[1])
+
+
+class _ERIS(object):
+    """What ao2mo() hands back: the MO blocks as device arrays, (pq|rs) at row (p, q), column (r, s); vvvv packed on both sides."""
+    fock = None
+
+
+class RCCSD(PostHFBase):
+    _restricted = True
+    _method = "CCSD"
+
+    def __init__(self, mf, frozen=None, mo_coeff=None, mo_occ=None):
+        PostHFBase.__init__(self, mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+        # the reference's defaults (solver/cc.py:569-572)
+        self.conv_tol, self.conv_tol_normt, self.diis_space, self.max_cycle = 1e-7, 1e-5, 8, 200
+        self.level_shift, self.iterative_damping = 0.0, 1.0
+        self.max_memory = None          # MB of device memory the solver may plan with (None: what is free when it starts)
+        self.converged, self.cycles = False, 0
+        self.emp2 = self.t1 = self.t2 = None
+        self._h = self._eris = None
+
+    # ---- what is not built -------------------------------------------------------------------------------------------------------
+    def _check_options(self):
+        if self.level_shift != 0:
+            _not_built("CCSD with a level shift (level_shift = %r)" % (self.level_shift,))
+        if self.iterative_damping != 1:
+            _not_built("CCSD with damping (iterative_damping = %r)" % (self.iterative_damping,))
+        if not 0 <= int(self.diis_space) <= 12:
+            raise ValueError("diis_space = %r outside [0, 12]" % (self.diis_space,))
+
+    def solve_lambda(self, *args, **kwargs):
+        _not_built("The Lambda equations (solve_lambda)")
+
+    def make_rdm1(self, *args, **kwargs):
+        _not_built("The CCSD one-particle density (make_rdm1, it needs the Lambda equations)")
+
+    def make_rdm2(self, *args, **kwargs):
+        _not_built("The CCSD two-particle density (make_rdm2, it needs the Lambda equations)")
+
+    def ccsd_t(self, *args, **kwargs):
+        _not_built("The perturbative triples (T) (ccsd_t)")
+
+    # ---- life time ---------------------------------------------------------------------------------------------------------------
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and self._scf._ctx.h:
+            lib.dmk_rccsd_free(h)
+        self._eris = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- memory ------------------------------------------------------------------------------------------------------------------
+    def memory_plan(self):
+        """Bytes the solver will hold on the device, from host arithmetic alone: {"handle", "workspace", "integrals", "transform"}
+        (the transform's workspace is released before the handle is made)."""
+        n, o = self._scf._n, self._nocc[0]
+        v = n - o
+        handle, ws = plan_bytes(o, v, self.diis_space)
+        npv = v * (v + 1) // 2
+        integrals = 8 * (o ** 4 + o ** 3 * v + 3 * o * o * v * v + o * v ** 3 + npv * npv + n * n)
+        transform = 0
+        for w, flags in (((o, v, v, v), 0), ((v, v, v, v), _PACK_BOTH)):
+            p = (c_i64 * 3)()
+            lib.dmk_ao2mo_plan(n, w[0], w[1], w[2], w[3], flags, 0, p)
+            transform = max(transform, int(p[1]))
+        return {"handle": handle, "workspace": ws, "integrals": integrals, "transform": transform}
+
+    def _check_memory(self):
+        plan = self.memory_plan()
+        need = plan["integrals"] + max(plan["transform"], plan["handle"] + plan["workspace"])
+        if self.max_memory is None:
+            have, what = self._scf._ctx.mem_info()[0], "free on the device"
+        else:
+            have, what = int(float(self.max_memory) * (1 << 20)), "allowed by max_memory"
+        if need > have:
+            raise MemoryError("RCCSD with nocc = %d, nvir = %d, diis_space = %d plans %d bytes of device memory (integral blocks %d, "
+                              "handle %d, contraction workspace %d, transform workspace %d); %d bytes are %s"
+                              % (self._nocc[0], self._scf._n - self._nocc[0], self.diis_space, need, plan["integrals"],
+                                 plan["handle"], plan["workspace"], plan["transform"], have, what))
+
+    # ---- the integrals -----------------------------------------------------------------------------------------------------------
+    def ao2mo(self, mo_coeff=None):
+        """The seven MO blocks (device) and the Fock matrix C^T F C of the density of these orbitals (host, [occupied | virtual])."""
+        if mo_coeff is not None:
+            self.mo_coeff = mo_coeff
+            self._set_orbitals(mo_coeff)
+        mf = self._scf
+        ctx, n, ld, o = mf._ctx, mf._n, mf._ld, self._nocc[0]
+        d_c = self._dev_coeff()[0]
+        rng = {"o": (d_c, 0, o), "v": (d_c, o, n - o)}
+        eris = _ERIS()
+        for name in _BLOCKS:
+            setattr(eris, name, scf.ao2mo_block_dev(ctx, n, mf._blocks[0], [rng[x] for x in name], compact=(name == "vvvv"), ld=ld))
+        dm = mf.make_rdm1(self.mo_coeff, self.mo_occ)
+        cs = self._c[0][:, self._order[0]]
+        eris.fock = cs.T @ np.asarray(mf.get_fock(dm=dm), dtype=np.float64) @ cs
+        return eris
+
+    def _handle(self):
+        if self._h is None:
+            self._check_options()
+            self._check_memory()
+            mf = self._scf
+            ctx, n, o = mf._ctx, mf._n, self._nocc[0]
+            v = n - o
+            eris = self.ao2mo()
+            d_f = ctx.to_device(eris.fock)
+            h = c_vp()
+            ctx.check(lib.dmk_rccsd_create(ctx.h, o, v, d_f.ptr, eris.oooo.ptr, eris.ovoo.ptr, eris.ovov.ptr, eris.oovv.ptr, eris.ovvo.ptr,
+                                           eris.ovvv.ptr, eris.vvvv.ptr, v * (v + 1) // 2, int(self.diis_space), C.byref(h)))
+            self._h, self._eris = h, eris          # the blocks are borrowed by the handle: kept alive here
+        return self._h
+
+    # ---- amplitudes --------------------------------------------------------------------------------------------------------------
+    def _shapes(self):
+        o = self._nocc[0]
+        v = self._scf._n - o
+        return (o, v), (o, o, v, v)
+
+    def _set(self, t1, t2):
+        ctx = self._scf._ctx
+        s1, s2 = self._shapes()
+        t1, t2 = np.asarray(t1, dtype=np.float64), np.asarray(t2, dtype=np.float64)
+        if t1.shape != s1 or t2.shape != s2:
+            raise ValueError("amplitudes of shapes %s, %s; expected %s, %s" % (t1.shape, t2.shape, s1, s2))
+        d1, d2 = ctx.to_device(t1), ctx.to_device(t2)
+        ctx.check(lib.dmk_rccsd_set(self._handle(), d1.ptr, d2.ptr))
+
+    def _get(self, what):
+        ctx = self._scf._ctx
+        d = ctx.empty((self._shapes() + ((1,),))[what], np.float64)
+        ctx.check(lib.dmk_rccsd_get(self._handle(), what, d.ptr))
+        return d.get()
+
+    def energy(self, t1=None, t2=None):
+        """e_corr of the given amplitudes (default: the current ones)."""
+        ctx = self._scf._ctx
+        if t1 is not None or t2 is not None:
+            self._set(t1, t2)
+        d_e = ctx.empty((1,), np.float64)
+        ctx.check(lib.dmk_rccsd_energy(self._handle(), d_e.ptr))
+        return float(d_e.get()[0])
+
+    def update_amps(self, t1, t2):
+        """ONE application of the amplitude equations: -> (t1new, t2new)."""
+        self._set(t1, t2)
+        self._scf._ctx.check(lib.dmk_rccsd_update(self._handle()))
+        return self._get(_T1), self._get(_T2)
+
+    def kernel(self, t1=None, t2=None, mo_coeff=None):
+        """-> (e_corr, t1, t2), the amplitudes on the host in (i, a) and (i, j, a, b) order; starts from t1 / t2 when both are given,
+        else from the MP2 guess."""
+        if (t1 is None) != (t2 is None):
+            raise ValueError("a restart needs both t1 and t2")
+        if mo_coeff is not None:
+            self.close()
+            self.mo_coeff = mo_coeff
+            self._set_orbitals(mo_coeff)
+        ctx = self._scf._ctx
+        h = self._handle()
+        ctx.check(lib.dmk_rccsd_init(h))
+        self.emp2 = float(self._get(_EMP2)[0])
+        if t1 is not None:
+            self._set(t1, t2)
+        res = (c_dbl * 5)()
+        ctx.check(lib.dmk_rccsd_run(h, int(self.max_cycle), float(self.conv_tol), float(self.conv_tol_normt), res))
+        self.e_corr, self.converged, self.cycles = float(res[0]), bool(res[1]), int(res[2])
+        self.t1, self.t2 = self._get(_T1), self._get(_T2)
+        log.debug(0, "RCCSD: e_corr = %.12f after %d iterations (|dt| = %.2e, dE = %.2e)%s", self.e_corr, self.cycles, res[3], res[4],
+                  "" if self.converged else ", NOT converged")
+        return self.e_corr, self.t1, self.t2
+
+
+CCSD = RCCSD
+
+
+def UCCSD(*args, **kwargs):
+    _not_built("Unrestricted CCSD (UCCSD)")
+
+
+def GCCSD(*args, **kwargs):
+    _not_built("Generalised CCSD (GCCSD)")
+
+
+_RUN_OPTIONS = ("conv_tol", "conv_tol_normt", "max_cycle", "diis_space", "level_shift", "iterative_damping", "max_memory")
+_UNBUILT_RUN_OPTIONS = {"ccsdt": "The perturbative triples (T) (ccsdt)", "ccsdt_energy": "The perturbative triples (T) (ccsdt_energy)",
+                        "bcc": "Brueckner CC (bcc)", "tcc": "Tailored CC (tcc)", "calc_rdm2": "The CCSD two-particle density (calc_rdm2)",
+                        "approx_l": "The Lambda equations (approx_l)", "restart": "Restart files (restart)"}
+
+
+def run_ccsd(scfsolver, t1=None, t2=None, mo_coeff=None, mo_occ=None, frozen=None, **opts):
+    """The T part of the reference's CCSD.run (solver/cc.py:618-1153) over a solver.scf.SCF whose HF() has run: -> (e_corr, t1, t2).
+    The solver's `.cc` holds the RCCSD object afterwards.  Options: conv_tol, conv_tol_normt, max_cycle, diis_space, max_memory
+    (level_shift and iterative_damping only at their neutral values)."""
+    for key, val in opts.items():
+        if key in _UNBUILT_RUN_OPTIONS:
+            if val:
+                _not_built(_UNBUILT_RUN_OPTIONS[key])
+        elif key not in _RUN_OPTIONS:
+            raise TypeError("run_ccsd: unknown option %r" % key)
+    if not scfsolver.doneHF:
+        log.warn("running HF first with default settings")
+        scfsolver.HF()
+    log.check(scfsolver.mf.converged, "Hartree-Fock calculation has not converged")
+    if not scfsolver.spinRestricted:
+        _not_built("Unrestricted CCSD (UCCSD)")
+    log.result("Restricted CCSD on the device")
+    cc = RCCSD(scfsolver.mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+    for key in _RUN_OPTIONS:
+        if key in opts:
+            setattr(cc, key, opts[key])
+    scfsolver.cc = cc
+    return cc.kernel(t1=t1, t2=t2)
+
+
+def run(*args, **kwargs):
+    _not_built("CCSD.run (it returns a density, which needs the Lambda equations)")
+
+
+def run_dmet_ham(*args, **kwargs):
+    _not_built("CCSD.run_dmet_ham (it needs the CCSD densities)")
