@@ -735,8 +735,10 @@ int dmk_cc_ladder_s4(dmk_ctx *ctx, int64_t m, int nvir, const double *vvvv_s4, i
  *                    (ring and Gram row on the device, dmk_diis_coeffs on the host, the extrapolation a device linear combination);
  *                    ONE record of at most 13 doubles is read back per iteration.  Starts from the current amplitudes (the MP2
  *                    guess when there are none).  Converged when |dE| < tol_e and |dt|_2 < tol_normt; the amplitudes kept are then
- *                    the un-extrapolated ones the energy belongs to.  result_host[5]: e_corr, converged (0 | 1), iterations, |dt|,
- *                    last dE
+ *                    the un-extrapolated ones the energy belongs to.  Left at max_iter without convergence, the amplitudes kept are
+ *                    the last ones made (with a ring: the DIIS combination) and e_corr is evaluated for exactly those: result[0] is
+ *                    always the dmk_rccsd_energy of what dmk_rccsd_get returns.  max_iter = 0: the energy of the current amplitudes.
+ *                    result_host[5]: e_corr, converged (0 | 1), iterations, |dt|, last dE (of the convergence test)
  *   dmk_rccsd_get    copies to device memory of the caller: DMK_RCCSD_T1, DMK_RCCSD_T2, DMK_RCCSD_EMP2 (one double; set by init)
  * Every call returns after the stream drained.  DMK_ERR_STATE where amplitudes are needed and there are none. */
 typedef struct dmk_rccsd dmk_rccsd;

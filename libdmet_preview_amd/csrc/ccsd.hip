@@ -696,6 +696,14 @@ int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, do
             DMK_CHECK_LAUNCH(ctx);
         }
     }
+    if (dim && !converged && it > 0) {
+        // left unconverged with a ring: h->x is the extrapolated vector, not the update whose energy `e` is.  The energy reported
+        // is the one of the amplitudes dmk_rccsd_get returns (dE stays the difference the convergence test saw)
+        if ((rc = cc_energy(h, h->x, h->rec))) return rc;
+        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        e = rec[0];
+    }
     DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     result_host[0] = e; result_host[1] = converged; result_host[2] = it; result_host[3] = dt; result_host[4] = dE;
     return DMK_OK;

@@ -13,6 +13,10 @@ t_ij^ab = t_ji^ba) maps to spin-orbital amplitudes as   aa = t - t^T(ab),   ab =
     solve(so, tol)                DIIS-free iteration from the MP2 guess until the amplitudes move by less than tol
     to_so / from_so               the maps between restricted and spin-orbital amplitudes
     r_update / r_energy / r_solve the same through the maps, on restricted amplitudes
+    converged_reference(so)       DIIS-free solution at |dt| < 1e-11 with its own convergence uncertainty (against |dt| < 1e-9)
+    uneven_system(o, v)           the host system and orbitals of the uneven-shape tests (no device SCF)
+    restricted_blocks / restricted_energy   the Fock matrix and the seven SPATIAL blocks in the layout of dmk_rccsd_create, and the
+                                  closed-shell energy over them: what a test hands to the C ABI without a device SCF or transform
     exact_two_electron_singlet    lowest singlet eigenvalue of H in the n^2 space of (alpha, beta) determinants
 """
 import numpy as np
@@ -158,6 +162,58 @@ def r_energy(so, t1, t2):
 def r_solve(so, tol, max_iter=500):
     e, T1, T2, it = solve(so, tol, max_iter)
     return (e,) + from_so(T1, T2) + (it,)
+
+
+def converged_reference(so):
+    """DIIS-free reference at |dt| < 1e-9 and on to 1e-11: ((e, t1, t2) of the tighter run, delta_e, delta_t), the deltas between the
+    two runs being the reference's own convergence uncertainty."""
+    e9, T1, T2, _ = solve(so, 1e-9)
+    e11, U1, U2, _ = solve(so, 1e-11, T1=T1, T2=T2)
+    a9, a11 = from_so(T1, T2), from_so(U1, U2)
+    dt = max(np.abs(a9[0] - a11[0]).max(), np.abs(a9[1] - a11[1]).max())
+    return (e11,) + a11, abs(e9 - e11), dt
+
+
+BLOCKS = ("oooo", "ovoo", "ovov", "oovv", "ovvo", "ovvv", "vvvv")
+
+
+def restricted_blocks(sysm, C, o, pad=0):
+    """(fock_mo, blocks) as dmk_rccsd_create takes them, at the orbitals C (columns, the o occupied first): fock_mo = C^T F C (n, n)
+    with F the closed-shell Fock matrix of the density of the occupied columns; blocks[name] for oooo, ovoo, ovov, oovv, ovvo, ovvv the
+    spatial (pq|rs) row-major in the order of the letters, and vvvv packed on both sides (rows pair(a, c), columns pair(b, d)) with a
+    row pitch of npair + pad whose pad columns are NaN (never to be read)."""
+    n, v = sysm.n, sysm.n - o
+    C = np.asarray(C, dtype=np.float64)
+    D = 2.0 * C[:, :o] @ C[:, :o].T
+    f = C.T @ (sysm.h1 + sysm.veff_rhf(D)) @ C
+    part = {"o": C[:, :o], "v": C[:, o:]}
+    blocks = {}
+    for name in BLOCKS[:-1]:
+        c = [part[x] for x in name]
+        blocks[name] = M.transform(sysm, "aa", *c).reshape([x.shape[1] for x in c])
+    g = M.pack_cols(M.pack_rows(M.transform(sysm, "aa", *([part["v"]] * 4)), v), v)
+    npair = v * (v + 1) // 2
+    blocks["vvvv"] = np.full((npair, npair + pad), np.nan)
+    blocks["vvvv"][:, :npair] = g
+    return f, blocks
+
+
+def uneven_system(o, v):
+    """(system, canonical host orbitals) of the o-occupied, v-virtual case of tests/test_gpu_ccsd_shapes.py: System(o + v, 500 + 37 o
+    + v, [o]) and the orbitals of the numpy SCF of tests/scf_ref.py on it."""
+    from tests import scf_ref as R
+    sysm = R.System(o + v, 500 + 37 * o + v, [o])
+    ref = R.scf(sysm.h1[None], sysm.veff_rhf, [o], True)
+    assert ref["converged"], (o, v)
+    return sysm, ref["mo_coeff"]
+
+
+def restricted_energy(fock_mo, blocks, t1, t2):
+    """2 f_ia t_ia + sum (2 (ia|jb) - (ib|ja)) (t_ij^ab + t_i^a t_j^b) over the blocks of restricted_blocks, plain numpy."""
+    o = t1.shape[0]
+    g = blocks["ovov"]                                                   # g[i, a, j, b] = (ia|jb)
+    tau = t2 + np.einsum("ia,jb->ijab", t1, t1)
+    return float(2.0 * np.sum(fock_mo[:o, o:] * t1) + np.einsum("iajb,ijab", 2.0 * g - g.transpose(0, 3, 2, 1), tau))
 
 
 def random_amplitudes(rng, o, v, scale=0.1):

@@ -77,12 +77,7 @@ def _reference(n, rotated):
 @functools.lru_cache(maxsize=None)
 def _converged_reference(n):
     """DIIS-free reference at |dt| < 1e-9 and on to 1e-11: (tight result, delta_e, delta_t)."""
-    so = _reference(n, False)[0]
-    e9, T1, T2, _ = CR.solve(so, 1e-9)
-    e11, U1, U2, _ = CR.solve(so, 1e-11, T1=T1, T2=T2)
-    a9, a11 = CR.from_so(T1, T2), CR.from_so(U1, U2)
-    dt = max(np.abs(a9[0] - a11[0]).max(), np.abs(a9[1] - a11[1]).max())
-    return (e11,) + a11, abs(e9 - e11), dt
+    return CR.converged_reference(_reference(n, False)[0])
 
 
 @pytest.mark.parametrize("n,rotated", [(6, False), (17, False), (65, False), (17, True)])

@@ -9,6 +9,15 @@ Bound      per element, computed here in np.longdouble with eps = 2^-52 (c = 1 a
              + eps (|alpha| S + |beta out_0|)   only where beta != 0       the scaling by beta and the final addition
 Shapes     one element; v below, at and above the K chunk of 16 and the 64-wide tile; m off the 64-row tile and over many
            workgroups; v = 65 (two column tiles, chunks on both sides of the diagonal of the triangle).
+
+Wide, exactly  v = 64, 97, 113, 129 with INTEGER data: the packed block, tau and out_0 are integers in [-8, 8] held as float64, so
+           every partial sum is an integer below 64 v^2 < 2^21: any summation order, the fused-multiply-add chain of the matrix
+           cores included, is exact, and the device must return the bits of a plain float64 numpy reference (one a at a time: the
+           rows pair(a, c) gathered, their columns expanded through an index table to [(c, d)][b], one matrix product with tau; v^4
+           is never held).  The loader runs its lanes along b only where a chunk starts at d0 >= n0 + 32, which at v <= 65 happens
+           in column tile n0 = 0 alone: v = 97 and 113 put such chunks (d0 = 96, 112) into tile n0 = 64, v = 129 adds a third column
+           tile with a single valid column, v = 64 is the full tile without an edge.  (alpha, beta) = (1, 0) and (-2, 1); pitch
+           npair + 3 with a NaN pad.
 """
 import functools
 
@@ -84,6 +93,47 @@ def test_ladder_against_the_unpacked_einsum(ctx, m, v, alpha, beta):
     assert np.all(np.isfinite(got)) and ratio <= 1.0
     again = _ladder(ctx, m, v, d_W, npair + PAD, d_tau, alpha, beta, start)
     assert np.array_equal(got.view(np.uint64), again.view(np.uint64))     # two calls, the same bits
+
+
+def _integers(rng, shape):
+    return rng.integers(-8, 9, size=shape).astype(np.float64)
+
+
+def _exact_ladder(Wp, tau, v):
+    """sum_cd tau[r][c][d] (ac|bd) as (m, v, v) in float64, from the packed block, one a at a time."""
+    m = tau.shape[0]
+    idx = np.zeros((v, v), dtype=np.int64)
+    i, j = np.tril_indices(v)
+    idx[i, j] = idx[j, i] = np.arange(len(i))
+    T = tau.reshape(m, v * v)
+    out = np.empty((m, v, v))
+    for a in range(v):
+        B = Wp[idx[a]][:, idx.reshape(-1)]                            # B[c][(d, b)] = (ac|bd): row pair(a, c), column pair(b, d)
+        out[:, a, :] = T @ B.reshape(v * v, v)
+    return out
+
+
+@pytest.mark.parametrize("v,ms", [(64, (2, 65)), (97, (2, 65)), (113, (2,)), (129, (2,))])
+def test_wide_ladder_is_exact_on_integers(ctx, v, ms):
+    rng = np.random.default_rng(7000 + v)
+    npair = v * (v + 1) // 2
+    Wp = np.full((npair, npair + PAD), np.nan)
+    Wp[:, :npair] = _integers(rng, (npair, npair))
+    d_W = ctx.to_device(Wp)
+    for m in ms:
+        tau, out0 = _integers(rng, (m, v, v)), _integers(rng, (m, v, v))
+        ref = _exact_ladder(Wp, tau, v)
+        assert np.abs(ref).max() < 2.0 ** 21 and np.array_equal(ref, np.rint(ref))
+        d_tau = ctx.to_device(tau)
+        for alpha, beta in ((1.0, 0.0), (-2.0, 1.0)):
+            start = out0 if beta != 0.0 else np.full_like(out0, np.nan)   # beta = 0 never reads out
+            got = _ladder(ctx, m, v, d_W, npair + PAD, d_tau, alpha, beta, start)
+            want = alpha * ref + (beta * out0 if beta != 0.0 else 0.0)
+            bad = got != want                                             # (NaN counts as different)
+            print("m = %d, v = %d, alpha = %g, beta = %g: %d of %d elements differ, max |err| = %s, columns b of the differences: %s"
+                  % (m, v, alpha, beta, bad.sum(), bad.size, np.abs(got - want).max(), np.unique(np.nonzero(bad)[2])[:8]))
+            assert np.all(np.isfinite(got)) and not bad.any()
+            assert np.array_equal((got + 0.0).view(np.uint64), (want + 0.0).view(np.uint64))      # the same bits (-0 + 0 = +0)
 
 
 def test_ladder_refuses_bad_arguments(ctx):

@@ -1,6 +1,7 @@
 """
 Host-side checks of the CCSD layer, no GPU: the spin-orbital reference of tests/ccsd_ref.py validates itself against
-exact diagonalisation (CCSD is exact for two electrons), the planner dmk_rccsd_plan returns the byte counts of K21's formula, and
+exact diagonalisation (CCSD is exact for two electrons), the restricted blocks and energy that tests/test_gpu_ccsd_shapes.py hands to
+the C ABI agree with it (so that a mistake in that helper is not blamed on the device), the planner dmk_rccsd_plan returns the byte counts of K21's formula, and
 solver/cc.py imports without a GPU and refuses by name what is not built.
 """
 import ctypes as C
@@ -48,6 +49,33 @@ def test_reference_maps_and_symmetry():
     M1, M2 = CR.to_so(n1, n2)
     assert np.abs(M1 - N1).max() <= 1e-14 and np.abs(M2 - N2).max() <= 1e-14
     assert np.abs(n2 - n2.transpose(1, 0, 3, 2)).max() <= 1e-14
+
+
+@pytest.mark.parametrize("rotated", [False, True])
+@pytest.mark.parametrize("o,v", [(2, 5), (5, 2)])
+def test_restricted_blocks_and_energy_agree_with_the_spin_orbital_reference(o, v, rotated):
+    sysm, C = CR.uneven_system(o, v)
+    if rotated:
+        C = CR.rotate_ov(C, o)
+    so = CR.spin_orbital(sysm, C, o)
+    fock, blocks = CR.restricted_blocks(sysm, C, o, pad=3)
+    n, npair = o + v, v * (v + 1) // 2
+    assert np.array_equal(fock, so.f_mo) and fock.shape == (n, n)
+    assert [blocks[k].shape for k in CR.BLOCKS[:-1]] == [tuple({"o": o, "v": v}[x] for x in k) for k in CR.BLOCKS[:-1]]
+    g = sysm.lam * np.einsum("Ppq,Prs->pqrs", sysm.A, sysm.A)                             # the AO (pq|rs), literally
+    for name in CR.BLOCKS[:-1]:
+        c = [C[:, :o] if x == "o" else C[:, o:] for x in name]
+        assert np.abs(blocks[name] - np.einsum("pqrs,pi,qj,rk,sl->ijkl", g, *c)).max() <= 1e-13, name
+    vvvv = np.einsum("pqrs,pi,qj,rk,sl->ijkl", g, *([C[:, o:]] * 4))
+    packed = blocks["vvvv"]
+    assert packed.shape == (npair, npair + 3) and np.all(np.isnan(packed[:, npair:]))
+    assert np.abs(R.restore_s1(packed[:, :npair], v) - vvvv).max() <= 1e-13
+    for t1, t2 in (CR.random_amplitudes(np.random.default_rng(100 + n), o, v), CR.from_so(*CR.mp2_guess(so))):
+        e, e_so = CR.restricted_energy(fock, blocks, t1, t2), CR.r_energy(so, t1, t2)
+        print("(o, v) = (%d, %d)%s: restricted %.15f, spin-orbital %.15f" % (o, v, " rotated" if rotated else "", e, e_so))
+        assert abs(e - e_so) <= 1e-12
+    if rotated:
+        assert np.abs(fock[:o, o:]).max() > 1e-3
 
 
 def _a256(count):
