@@ -60,7 +60,8 @@ int dmk_set_oom_hook(dmk_ctx *ctx, void (*hook)(void *user), void *user);
 const char *dmk_last_error(const dmk_ctx *ctx);
 const char *dmk_version(void);
 
-/* free / total device memory in bytes (hipMemGetInfo): sizes the plane stack of the ERI pipeline */
+/* free / total device memory in bytes (hipMemGetInfo): sizes the plane stack of the ERI pipeline.  The driver gives the pages of a
+ * freed block back a moment after hipFree returns, so the free figure is the one two readings 2 ms apart agree on (at most ten) */
 int dmk_mem_info(dmk_ctx *ctx, size_t *free_bytes_host, size_t *total_bytes_host);
 int dmk_malloc(dmk_ctx *ctx, size_t bytes, void **out);
 int dmk_free(dmk_ctx *ctx, void *p);      /* drains the context stream first */
@@ -754,6 +755,38 @@ int dmk_rccsd_update(dmk_rccsd *h);
 int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, double *result_host /*[5]*/);
 int dmk_rccsd_get(dmk_rccsd *h, int what, double *out);
 int dmk_rccsd_free(dmk_rccsd *h);
+/* The Lambda equations, the one-particle density and the expectation value of another Hamiltonian ("Lambda").
+ * With the projected residual r(t) = R_od(t) - d t (R_od: what dmk_rccsd_update divides by d, the Fock-diagonal denominators) the
+ * restricted Lagrangian is  L(t, l) = E_corr(t) + 2 sum l1_ia r1_ia + sum (2 l2_ijab - l2_ijba) r2_ijab;  l1, l2 (shaped and
+ * symmetric as t1, t2) make it stationary in t: PySCF's RCCSD l1 / l2.  One application is the REVERSE SWEEP of the amplitude
+ * equations: with l~ = (2 l1, 2 l2 - l2^T(ab)),  l~_new = ((dR_od/dt)^T l~ + dE/dt) / d,  the (vv|vv) term being the ladder kernel
+ * itself applied to the adjoint of R.  The Lambda state (l, its DIIS ring, the T-only intermediates kept across sweeps) is a second
+ * allocation made by the first of these calls; what dmk_rccsd_create allocates does not change.
+ *   dmk_rccsd_lambda_plan   (HOST, no context) bytes_host[1]: bytes of that second allocation; refuses as dmk_rccsd_plan
+ *   dmk_rccsd_lambda_init   l = t (the lowest order, and the answer of approx_l)
+ *   dmk_rccsd_lambda_set    device Lambda amplitudes of the caller
+ *   dmk_rccsd_lambda_update ONE application to the current l (no DIIS) at the current t
+ *   dmk_rccsd_lambda_run    iterates from the current l (l = t when there is none) with DIIS on the (l1, l2) vector exactly as
+ *                           dmk_rccsd_run does for t; ONE record read back per iteration; converged when |dl|_2 < tol_normt.
+ *                           result_host[3]: converged (0 | 1), iterations, |dl|_2
+ *   dmk_rccsd_get           also DMK_RCCSD_L1, DMK_RCCSD_L2
+ *   dmk_rccsd_rdm1          gamma_dev (n x n, [occupied | virtual], spin-summed, symmetric, WITH the 2 on the occupied diagonal
+ *                           of the reference determinant) of the current (t, l)
+ *   dmk_rccsd_residual      r1_dev (nocc, nvir), r2_dev (nocc, nocc, nvir, nvir) = R_od - d t of the current t over THIS handle's
+ *                           integrals; nothing is divided (a handle made over another Hamiltonian may have vanishing denominators)
+ *   dmk_rccsd_lagrangian    *out_dev = E_corr(t) + <l~, r(t)> over this handle's integrals at this handle's current t, with the
+ *                           caller's device l1, l2: the correlation part of the expectation value of the handle's Hamiltonian in
+ *                           the CCSD state (t, l); needs no Lambda allocation
+ * Fixed-order sums and no atomics throughout: repeated calls give the same bits.  DMK_ERR_STATE where t or l is needed and absent. */
+enum { DMK_RCCSD_L1 = 3, DMK_RCCSD_L2 = 4 };
+int dmk_rccsd_lambda_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host /*[1]*/);
+int dmk_rccsd_lambda_init(dmk_rccsd *h);
+int dmk_rccsd_lambda_set(dmk_rccsd *h, const double *l1, const double *l2);
+int dmk_rccsd_lambda_update(dmk_rccsd *h);
+int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *result_host /*[3]*/);
+int dmk_rccsd_rdm1(dmk_rccsd *h, double *gamma_dev);
+int dmk_rccsd_residual(dmk_rccsd *h, double *r1_dev, double *r2_dev);
+int dmk_rccsd_lagrangian(dmk_rccsd *h, const double *l1, const double *l2, double *out_dev);
 
 /* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
  * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the

@@ -160,6 +160,14 @@ PROTOTYPES = {
     "dmk_rccsd_run": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_vp]),
     "dmk_rccsd_get": (c_int, [c_vp, c_int, c_vp]),
     "dmk_rccsd_free": (c_int, [c_vp]),
+    "dmk_rccsd_lambda_plan": (c_int, [c_int, c_int, c_int, P(c_i64)]),
+    "dmk_rccsd_lambda_init": (c_int, [c_vp]),
+    "dmk_rccsd_lambda_set": (c_int, [c_vp, c_vp, c_vp]),
+    "dmk_rccsd_lambda_update": (c_int, [c_vp]),
+    "dmk_rccsd_lambda_run": (c_int, [c_vp, c_int, c_dbl, c_vp]),
+    "dmk_rccsd_rdm1": (c_int, [c_vp, c_vp]),
+    "dmk_rccsd_residual": (c_int, [c_vp, c_vp, c_vp]),
+    "dmk_rccsd_lagrangian": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "dmk_dmet_h2_scaled":(c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
     "dmk_rho_glob": (c_int, [c_vp, _int3, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "dmk_sym_norm_bound": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),

@@ -7,6 +7,8 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <algorithm>
+#include <chrono>
+#include <thread>
 
 // =============================================================================================
 // context / errors / memory
@@ -118,6 +120,17 @@ int dmk_set_stream(dmk_ctx *ctx, void *stream) {
 int dmk_mem_info(dmk_ctx *ctx, size_t *free_bytes, size_t *total_bytes) {
     if (!ctx || !free_bytes || !total_bytes) return DMK_ERR_INVALID;
     DMK_HIP(ctx, hipMemGetInfo(free_bytes, total_bytes));
+    // hipFree returns before the driver has given every page back: a block freed just before the call can still count as used
+    // (measured: 18 MiB of a freed 17.8 MB block, back about 1 ms later with nothing done in between).  The figure handed out is
+    // the one that two readings 2 ms apart agree on, at most ten readings.
+    for (int k = 0; k < 10; ++k) {
+        std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        size_t again = 0;
+        DMK_HIP(ctx, hipMemGetInfo(&again, total_bytes));
+        const bool settled = again == *free_bytes;
+        *free_bytes = again;
+        if (settled) break;
+    }
     return DMK_OK;
 }
 

@@ -18,6 +18,10 @@
 //                    not already [free, summed] or [summed, free])  ->  dmk_dgemm_batched  ->  permute-accumulate (only where the
 //                    product's index order differs from the destination's).  No host loops over elements, no host round trips.
 // dmk_rccsd          the handle: amplitudes, intermediates, DIIS ring (one allocation) and the contraction workspace (another).
+// Lambda             ("Lambda") the Lambda equations as the REVERSE SWEEP of the amplitude equations (lambda_update: the
+//                    adjoint of every line of cc_rod in the reverse order, the (vv|vv) term being cc_ladder_kernel itself on the adjoint
+//                    of R), the one-particle density (cc_rdm1_kernel assembles it), the residual without a division (cc_resid_kernel)
+//                    and the Lagrangian E_corr + <l~, r> of a probe handle; their state is a third allocation, made on first use.
 #include "devres.h"
 #include <algorithm>
 #include <cmath>
@@ -214,6 +218,37 @@ __global__ __launch_bounds__(NT) void cc_div_kernel(int o, int v, int two, const
     }
 }
 
+// out = in - D t with the D of cc_div_kernel: the projected residual R_od - d t, nothing divided (in and out may be the same array)
+__global__ __launch_bounds__(NT) void cc_resid_kernel(int o, int v, int two, const double *in, const double *__restrict__ t,
+                                                      const double *__restrict__ eo, const double *__restrict__ ev, double *out) {
+    const long long vv = two ? (long long)v * v : v, total = (two ? (long long)o * o : o) * vv;
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
+        const long long ij = e / vv, ab = e % vv;
+        double d;
+        if (two) d = (eo[ij / o] + eo[ij % o]) - (ev[ab / v] + ev[ab % v]);
+        else d = eo[ij] - ev[ab];
+        out[e] = in[e] - d * t[e];
+    }
+}
+
+// gamma (n x n, [occ | vir]) = [[doo + doo^T + 2 1, dov + dvo^T], [(dov + dvo^T)^T, dvv + dvv^T]]; dvo is handed over as (i, a)
+__global__ __launch_bounds__(NT) void cc_rdm1_kernel(int o, int v, const double *__restrict__ doo, const double *__restrict__ dvv,
+                                                     const double *__restrict__ dov, const double *__restrict__ dvo_ia,
+                                                     double *__restrict__ gamma) {
+    const int n = o + v;
+    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < (long long)n * n; e += (long long)gridDim.x * NT) {
+        const int p = (int)(e / n), q = (int)(e % n);
+        double x;
+        if (p < o && q < o) x = doo[(long long)p * o + q] + doo[(long long)q * o + p] + (p == q ? 2.0 : 0.0);
+        else if (p >= o && q >= o) x = dvv[(long long)(p - o) * v + q - o] + dvv[(long long)(q - o) * v + p - o];
+        else {
+            const long long ia = p < o ? (long long)p * v + q - o : (long long)q * v + p - o;
+            x = dov[ia] + dvo_ia[ia];
+        }
+        gamma[e] = x;
+    }
+}
+
 // the Fock matrix (n x n) cut into f_oo and f_vv without their diagonals, f_ov, and the diagonals
 __global__ __launch_bounds__(NT) void cc_fock_split_kernel(int o, int v, const double *__restrict__ f, double *__restrict__ foo,
                                                            double *__restrict__ fvv, double *__restrict__ fov, double *__restrict__ eo,
@@ -394,6 +429,34 @@ struct dmk_rccsd {
         return (size_t)(c.p - static_cast<char *>(base));
     }
     long long ring_stride() const { return (long long)(dmk_align256((size_t)nx * 8) / 8); }
+
+    // ---- Lambda ("Lambda"): a second allocation, made by the first Lambda call ------------------------------------
+    // l / lnew and the ring as x / xnew above; k*: the T-only intermediates of cc_rod at the current t, kept across sweeps; *b: the
+    // adjoints that have no home in the first allocation (those of R, S, tau, tau2, Wvoov, Wvovo, Woooo live in the buffers of those
+    // names, which hold nothing between two applications of cc_rod); g1 the t1 gradient of the energy; d* / xt*: density pieces.
+    DevMem lmem;
+    double *l = nullptr, *lnew = nullptr, *lring_x = nullptr, *lring_e = nullptr;
+    double *ktau, *ktau2, *kWvoov, *kWvovo, *kWoooo, *kFov, *kFoo, *kFvv, *kLoo, *kLvv, *kX1, *kX2;
+    double *t2b, *Qb, *Yb, *t1b, *n1b, *Fovb, *Foob, *Loob, *X1b, *X2b, *Fvvb, *Lvvb, *g1;
+    double *doo, *dvv, *dvo, *xt1, *xt2;
+    bool have_l = false, kept = false;          // kept: the k* arrays belong to the amplitudes in x
+
+    size_t lambda_carve(void *base) {
+        Carver c(base);
+        const long long oo = (long long)o * o, vv = (long long)v * v, ov = (long long)o * v, t2n = oo * vv;
+        l = c.take(nx); lnew = c.take(nx);
+        lring_x = reinterpret_cast<double *>(c.p);
+        for (int q = 0; q < diis; ++q) c.take(nx);
+        lring_e = reinterpret_cast<double *>(c.p);
+        for (int q = 0; q < diis; ++q) c.take(nx);
+        ktau = c.take(t2n); ktau2 = c.take(t2n); kWvoov = c.take(t2n); kWvovo = c.take(t2n); t2b = c.take(t2n);
+        kWoooo = c.take(oo * oo); Qb = c.take(oo * ov); Yb = c.take(oo * ov);
+        kFoo = c.take(oo); kLoo = c.take(oo); kX1 = c.take(oo); kX2 = c.take(oo);
+        Foob = c.take(oo); Loob = c.take(oo); X1b = c.take(oo); X2b = c.take(oo); doo = c.take(oo); xt1 = c.take(oo);
+        kFvv = c.take(vv); kLvv = c.take(vv); Fvvb = c.take(vv); Lvvb = c.take(vv); dvv = c.take(vv); xt2 = c.take(vv);
+        kFov = c.take(ov); Fovb = c.take(ov); t1b = c.take(ov); n1b = c.take(ov); g1 = c.take(ov); dvo = c.take(ov);
+        return (size_t)(c.p - static_cast<char *>(base));
+    }
 };
 
 namespace {
@@ -445,8 +508,9 @@ int cc_energy(dmk_rccsd *h, const double *amp, double *e_dev) {
 #define CT(alpha, A, sa, B, sb, beta, C, sc) do { if ((rc = E.contract(alpha, A, sa, B, sb, beta, C, sc))) return rc; } while (0)
 #define PM(alpha, in, si, beta, out, so) do { if ((rc = E.perm(alpha, in, si, beta, out, so))) return rc; } while (0)
 
-// one application of the amplitude equations (DESIGN.md K21) to the vector `src`, the new amplitudes into `dst`
-int cc_update(dmk_rccsd *h, const double *src, double *dst) {
+// the right-hand sides of the amplitude equations at the vector `src`, before the division: R_od of t1 into h->n1,
+// of t2 into h->R.  Every intermediate named in the handle is left as the equations define it at `src`.
+int cc_rod(dmk_rccsd *h, const double *src) {
     const Engine &E = h->E;
     const double *t1 = src, *t2 = src + h->t2off;
     const double *oooo = h->oooo, *ovoo = h->ovoo, *ovov = h->ovov, *oovv = h->oovv, *ovvo = h->ovvo, *ovvv = h->ovvv;
@@ -502,8 +566,15 @@ int cc_update(dmk_rccsd *h, const double *src, double *dst) {
     CT(-1.0, Wvovo, "bkci", t2, "kjac", 1.0, S, "ijab");
     PM(1.0, S, "ijab", 1.0, R, "ijab");
     PM(1.0, S, "jiba", 1.0, R, "ijab");
-    if ((rc = cc_div(h, 0, n1, dst))) return rc;
-    return cc_div(h, 1, R, dst + h->t2off);
+    return DMK_OK;
+}
+
+// one application of the amplitude equations to the vector `src`, the new amplitudes into `dst`
+int cc_update(dmk_rccsd *h, const double *src, double *dst) {
+    int rc;
+    if ((rc = cc_rod(h, src))) return rc;
+    if ((rc = cc_div(h, 0, h->n1, dst))) return rc;
+    return cc_div(h, 1, h->R, dst + h->t2off);
 }
 
 int cc_init(dmk_rccsd *h) {
@@ -518,8 +589,292 @@ int cc_init(dmk_rccsd *h) {
     return DMK_OK;
 }
 
+// ---- Lambda -----------------------------------------------------------------------------------------------------------------------
+int cc_resid(dmk_rccsd *h, int two, const double *in, const double *t, double *out) {
+    dmk_ctx *ctx = h->ctx;
+    FamScope fs(ctx, DMK_FAM_MISC);
+    const long long n = two ? (long long)h->o * h->o * h->v * h->v : (long long)h->o * h->v;
+    hipLaunchKernelGGL(cc_resid_kernel, dim3(grid_of(n)), dim3(NT), 0, ctx->stream, h->o, h->v, two, in, t, h->eo, h->ev, out);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+// r1 = R_od - d t1 into h->n1, r2 into h->R, of the current amplitudes
+int cc_residual(dmk_rccsd *h) {
+    int rc;
+    if ((rc = cc_rod(h, h->x))) return rc;
+    if ((rc = cc_resid(h, 0, h->n1, h->x, h->n1))) return rc;
+    return cc_resid(h, 1, h->R, h->x + h->t2off, h->R);
+}
+
+int lambda_alloc(dmk_rccsd *h) {
+    if (h->lmem.get<void>()) return DMK_OK;
+    dmk_ctx *ctx = h->ctx;
+    const size_t bytes = h->lambda_carve(nullptr);
+    if (h->lmem.alloc(ctx, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return dmk_fail(ctx, DMK_ERR_NOMEM, "rccsd_lambda: no device memory for %lld bytes", (long long)bytes);
+    }
+    h->lambda_carve(h->lmem.get<void>());
+    DMK_HIP(ctx, hipMemsetAsync(h->lmem.get<void>(), 0, bytes, ctx->stream));
+    return DMK_OK;
+}
+
+// the T-only quantities of the reverse sweep, once per set of amplitudes: the intermediates of cc_rod at t, and
+// g1_ia = 2 f_ia + 2 sum_jb (2 (ia|jb) - (ib|ja)) t_jb
+int lambda_prepare(dmk_rccsd *h) {
+    if (h->kept) return DMK_OK;
+    dmk_ctx *ctx = h->ctx;
+    const Engine &E = h->E;
+    int rc;
+    if ((rc = cc_rod(h, h->x))) return rc;
+    const long long oo = (long long)h->o * h->o, vv = (long long)h->v * h->v, ov = (long long)h->o * h->v, t2n = oo * vv;
+    const struct { double *dst; const double *src; long long n; } keep[] = {
+        {h->ktau, h->tau, t2n}, {h->ktau2, h->tau2, t2n}, {h->kWvoov, h->Wvoov, t2n}, {h->kWvovo, h->Wvovo, t2n}, {h->kWoooo, h->Woooo, oo * oo},
+        {h->kFov, h->Fov, ov}, {h->kFoo, h->Foo, oo}, {h->kFvv, h->Fvv, vv}, {h->kLoo, h->Loo, oo}, {h->kLvv, h->Lvv, vv},
+        {h->kX1, h->X1, oo}, {h->kX2, h->X2, oo}};
+    for (const auto &k : keep) DMK_HIP(ctx, hipMemcpyAsync(k.dst, k.src, (size_t)k.n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    PM(2.0, h->fov, "ia", 0.0, h->g1, "ia");
+    CT(2.0, h->Lovov, "iajb", h->x, "jb", 1.0, h->g1, "ia");
+    h->kept = true;
+    return DMK_OK;
+}
+
+#define LADDER(in, b, dst) do { if ((rc = ladder_launch(h->ctx, Ladder{(long long)h->o * h->o, h->v, h->vvvv, h->ld_vvvv, in, 1.0, b, dst}))) return rc; } while (0)
+
+// one application of the Lambda equations to the vector `src` = (l1, l2), the new (l1, l2) into `dst`: the weights
+// l~1 = 2 l1, l~2 = 2 l2 - l2^T(ab) go BACKWARDS through cc_rod (every CT(alpha, A, B -> C) gives Ab += alpha Cb . B and
+// Bb += alpha Cb . A for the operands that depend on t, in the reverse order; a buffer's adjoint starts with beta = 0 where it is
+// first written), then l~ = (z + g) / d and l from l~.  lambda_prepare must have run for the amplitudes in h->x.
+int lambda_update(dmk_rccsd *h, const double *src, double *dst) {
+    const Engine &E = h->E;
+    const double *t1 = h->x, *t2 = h->x + h->t2off, *l1 = src, *l2 = src + h->t2off;
+    const double *ovoo = h->ovoo, *ovov = h->ovov, *oovv = h->oovv, *ovvo = h->ovvo, *ovvv = h->ovvv;
+    const double *fov = h->fov, *Lovov = h->Lovov;
+    const double *ktau = h->ktau, *kWvoov = h->kWvoov, *kWvovo = h->kWvovo, *kWoooo = h->kWoooo, *kFov = h->kFov, *kFoo = h->kFoo,
+                 *kFvv = h->kFvv, *kLoo = h->kLoo, *kLvv = h->kLvv, *kX1 = h->kX1, *kX2 = h->kX2;
+    double *Rb = h->R, *Sb = h->S, *taub = h->tau, *tau2b = h->tau2, *Wvoovb = h->Wvoov, *Wvovob = h->Wvovo, *Woooob = h->Woooo;
+    double *Q = h->Q, *Y = h->Y, *Qb = h->Qb, *Yb = h->Yb, *t1b = h->t1b, *t2b = h->t2b, *n1b = h->n1b;
+    double *Fovb = h->Fovb, *Foob = h->Foob, *Loob = h->Loob, *X1b = h->X1b, *X2b = h->X2b, *Fvvb = h->Fvvb, *Lvvb = h->Lvvb;
+    int rc;
+    PM(2.0, l1, "ia", 0.0, n1b, "ia");
+    PM(2.0, l2, "ijab", 0.0, Rb, "ijab");
+    PM(-1.0, l2, "ijba", 1.0, Rb, "ijab");
+    // R += S + S^T
+    PM(1.0, Rb, "ijab", 0.0, Sb, "jiba");
+    PM(1.0, Rb, "ijab", 1.0, Sb, "ijab");
+    // the ring terms and their W
+    CT(-1.0, Sb, "ijab", t2, "kjac", 0.0, Wvovob, "bkci");
+    CT(-1.0, kWvovo, "bkci", Sb, "ijab", 0.0, t2b, "kjac");
+    CT(-1.0, Sb, "ijab", t2, "kjbc", 0.0, Wvoovb, "akic");
+    CT(-1.0, kWvoov, "akic", Sb, "ijab", 1.0, t2b, "kjbc");
+    CT(-1.0, Sb, "ijab", t2, "kjcb", 1.0, Wvovob, "akci");
+    CT(-1.0, kWvovo, "akci", Sb, "ijab", 1.0, t2b, "kjcb");
+    CT(2.0, Sb, "ijab", t2, "kjcb", 1.0, Wvoovb, "akic");
+    CT(2.0, kWvoov, "akic", Sb, "ijab", 1.0, t2b, "kjcb");
+    CT(-1.0, ovov, "lckd", Wvovob, "akci", 0.0, tau2b, "ilda");
+    CT(-1.0, ovoo, "lcki", Wvovob, "akci", 0.0, t1b, "la");
+    CT(1.0, Wvovob, "akci", ovvv, "kdac", 1.0, t1b, "id");
+    CT(0.5, Lovov, "ldkc", Wvoovb, "akic", 1.0, t2b, "ilad");
+    CT(-1.0, ovov, "ldkc", Wvoovb, "akic", 1.0, tau2b, "ilda");
+    CT(-1.0, ovoo, "kcli", Wvoovb, "akic", 1.0, t1b, "la");
+    CT(1.0, ovvv, "kcad", Wvoovb, "akic", 1.0, t1b, "id");
+    // Loo, Lvv
+    CT(-1.0, t2, "kjab", Sb, "ijab", 0.0, Loob, "ki");
+    CT(-1.0, kLoo, "ki", Sb, "ijab", 1.0, t2b, "kjab");
+    CT(1.0, Sb, "ijab", t2, "ijcb", 0.0, Lvvb, "ac");
+    CT(1.0, kLvv, "ac", Sb, "ijab", 1.0, t2b, "ijcb");
+    // Y (made again: it is not kept), the two ladders, Woooo
+    CT(1.0, ovvv, "kcbd", ktau, "ijcd", 0.0, Y, "ijkb");
+    CT(-1.0, Y, "ijkb", Sb, "ijab", 1.0, t1b, "ka");
+    CT(-1.0, t1, "ka", Sb, "ijab", 0.0, Yb, "ijkb");
+    CT(1.0, Yb, "ijkb", ovvv, "kcbd", 0.0, taub, "ijcd");
+    LADDER(Rb, 1.0, taub);                                                                   // (ac|bd) = (ca|db): its own adjoint
+    CT(1.0, ktau, "klab", Rb, "ijab", 0.0, Woooob, "klij");
+    CT(1.0, kWoooo, "klij", Rb, "ijab", 1.0, taub, "klab");
+    CT(1.0, Woooob, "klij", ovov, "kcld", 1.0, taub, "ijcd");
+    CT(1.0, Woooob, "klij", ovoo, "kclj", 1.0, t1b, "ic");
+    CT(1.0, Woooob, "klij", ovoo, "lcki", 1.0, t1b, "jc");
+    // the t1 terms of S (Q made again, twice)
+    CT(1.0, ovvo, "kcai", t1, "jc", 0.0, Q, "akij");
+    CT(-1.0, Sb, "ijab", t1, "kb", 0.0, Qb, "akij");
+    CT(-1.0, Q, "akij", Sb, "ijab", 1.0, t1b, "kb");
+    CT(1.0, Qb, "akij", ovvo, "kcai", 1.0, t1b, "jc");
+    CT(-1.0, ovoo, "iajk", Sb, "ijab", 1.0, t1b, "kb");
+    CT(1.0, oovv, "kibc", t1, "jc", 0.0, Q, "kibj");
+    CT(-1.0, Sb, "ijab", t1, "ka", 0.0, Qb, "kibj");
+    CT(-1.0, Q, "kibj", Sb, "ijab", 1.0, t1b, "ka");
+    CT(1.0, Qb, "kibj", oovv, "kibc", 1.0, t1b, "jc");
+    CT(1.0, Sb, "ijab", ovvv, "iacb", 1.0, t1b, "jc");
+    // T1
+    CT(1.0, ovoo, "kcli", n1b, "ia", 1.0, taub, "klac");
+    CT(-2.0, ovoo, "lcki", n1b, "ia", 1.0, taub, "klac");
+    CT(-1.0, n1b, "ia", ovvv, "kcad", 1.0, taub, "ikcd");
+    CT(2.0, ovvv, "kdac", n1b, "ia", 1.0, taub, "ikcd");
+    CT(-1.0, oovv, "kiac", n1b, "ia", 1.0, t1b, "kc");
+    CT(2.0, ovvo, "kcai", n1b, "ia", 1.0, t1b, "kc");
+    CT(1.0, t1, "ka", n1b, "ia", 0.0, X2b, "ki");
+    CT(1.0, kX2, "ki", n1b, "ia", 1.0, t1b, "ka");
+    CT(-1.0, n1b, "ia", t2, "ikca", 0.0, Fovb, "kc");
+    CT(-1.0, kFov, "kc", n1b, "ia", 1.0, t2b, "ikca");
+    CT(2.0, n1b, "ia", t2, "kica", 1.0, Fovb, "kc");
+    CT(2.0, kFov, "kc", n1b, "ia", 1.0, t2b, "kica");
+    CT(-1.0, t1, "ka", n1b, "ia", 0.0, Foob, "ki");
+    CT(-1.0, kFoo, "ki", n1b, "ia", 1.0, t1b, "ka");
+    CT(1.0, n1b, "ia", t1, "ic", 0.0, Fvvb, "ac");
+    CT(1.0, n1b, "ia", kFvv, "ac", 1.0, t1b, "ic");
+    CT(-2.0, t1, "ka", n1b, "ia", 0.0, X1b, "ki");
+    CT(-2.0, kX1, "ki", n1b, "ia", 1.0, t1b, "ka");
+    // the Fock-like intermediates
+    CT(1.0, X2b, "ki", t1, "ic", 1.0, Fovb, "kc");
+    CT(1.0, X2b, "ki", kFov, "kc", 1.0, t1b, "ic");
+    CT(-1.0, Lvvb, "ac", ovvv, "kcad", 1.0, t1b, "kd");
+    CT(2.0, ovvv, "kdac", Lvvb, "ac", 1.0, t1b, "kd");
+    CT(-1.0, fov, "kc", Lvvb, "ac", 1.0, t1b, "ka");
+    PM(1.0, Lvvb, "ac", 1.0, Fvvb, "ac");
+    CT(-1.0, ovoo, "kcli", Loob, "ki", 1.0, t1b, "lc");
+    CT(2.0, ovoo, "lcki", Loob, "ki", 1.0, t1b, "lc");
+    PM(1.0, Loob, "ki", 1.0, X1b, "ki");
+    PM(1.0, Loob, "ki", 1.0, Foob, "ki");
+    CT(1.0, X1b, "ki", fov, "kc", 1.0, t1b, "ic");
+    CT(-1.0, Lovov, "kcld", Fvvb, "ac", 1.0, taub, "klad");
+    CT(1.0, Lovov, "kcld", Foob, "ki", 1.0, taub, "ilcd");
+    CT(1.0, Lovov, "kcld", Fovb, "kc", 1.0, t1b, "ld");
+    // tau = t2 + t1 t1, tau2 = t2 / 2 + t1 t1
+    PM(1.0, taub, "ijab", 1.0, t2b, "ijab");
+    PM(0.5, tau2b, "ijab", 1.0, t2b, "ijab");
+    PM(1.0, tau2b, "ijab", 1.0, taub, "ijab");
+    CT(1.0, taub, "ijab", t1, "jb", 1.0, t1b, "ia");
+    CT(1.0, taub, "jiba", t1, "jb", 1.0, t1b, "ia");
+    // z2 onto the symmetry of t2, plus g; l~ -> l (the denominators are symmetric under a <-> b, so the division comes last)
+    PM(1.0, h->Lt, "ijab", 0.0, Sb, "ijab");
+    PM(0.5, t2b, "ijab", 1.0, Sb, "ijab");
+    PM(0.5, t2b, "jiba", 1.0, Sb, "ijab");
+    PM(2.0 / 3.0, Sb, "ijab", 0.0, Rb, "ijab");
+    PM(1.0 / 3.0, Sb, "ijba", 1.0, Rb, "ijab");
+    PM(0.5, t1b, "ia", 0.0, n1b, "ia");
+    PM(0.5, h->g1, "ia", 1.0, n1b, "ia");
+    if ((rc = cc_div(h, 0, n1b, dst))) return rc;
+    return cc_div(h, 1, Rb, dst + h->t2off);
+}
+
+// gamma (n x n) of the current (t, l) into gamma_dev: DESIGN.md K21, "Lambda"
+int lambda_rdm1(dmk_rccsd *h, double *gamma_dev) {
+    dmk_ctx *ctx = h->ctx;
+    const Engine &E = h->E;
+    const double *t1 = h->x, *t2 = h->x + h->t2off, *l1 = h->l, *l2 = h->l + h->t2off;
+    double *th = h->S, *doo = h->doo, *dvv = h->dvv, *dvo = h->dvo, *xt1 = h->xt1, *xt2 = h->xt2, *X = h->X1b;
+    int rc;
+    PM(2.0, t2, "ijab", 0.0, th, "ijab");
+    PM(-1.0, t2, "ijba", 1.0, th, "ijab");
+    CT(1.0, l2, "mnef", th, "inef", 0.0, xt1, "mi");
+    CT(1.0, th, "mnef", l2, "mnaf", 0.0, xt2, "ea");
+    CT(-1.0, l1, "ia", t1, "ja", 0.0, doo, "ij");
+    PM(-1.0, xt1, "ij", 1.0, doo, "ij");
+    CT(1.0, t1, "ia", l1, "ib", 0.0, dvv, "ab");
+    PM(1.0, xt2, "ab", 1.0, dvv, "ab");
+    PM(1.0, t1, "ia", 0.0, dvo, "ia");
+    CT(1.0, t1, "ie", l1, "me", 0.0, X, "im");
+    CT(-1.0, X, "im", t1, "ma", 1.0, dvo, "ia");
+    CT(1.0, th, "imae", l1, "me", 1.0, dvo, "ia");
+    CT(-1.0, xt1, "mi", t1, "ma", 1.0, dvo, "ia");
+    CT(-1.0, t1, "ie", xt2, "ae", 1.0, dvo, "ia");
+    FamScope fs(ctx, DMK_FAM_MISC);
+    const int n = h->o + h->v;
+    hipLaunchKernelGGL(cc_rdm1_kernel, dim3(grid_of((long long)n * n)), dim3(NT), 0, ctx->stream, h->o, h->v, doo, dvv, l1, dvo, gamma_dev);
+    DMK_CHECK_LAUNCH(ctx);
+    return DMK_OK;
+}
+
+#undef LADDER
 #undef CT
 #undef PM
+
+// The iteration of dmk_rccsd_run and dmk_rccsd_lambda_run: `update(from, to)` on the vector *x, DIIS over the ring with the steps
+// new - old as error vectors, ONE record read back per iteration.  energy == true: the T iteration (the energy of every new vector,
+// |dE| < tol_e part of the test); false: the test is |dx|_2 < tol_x alone.  e1 / e2: where the step is kept when there is no ring.
+struct Iterate {
+    double **x, **xnew, *ring_x, *ring_e, *e1, *e2;
+    bool energy;
+    const char *who;
+};
+
+template <class Update>
+int cc_iterate(dmk_rccsd *h, const Iterate &s, int max_iter, double tol_e, double tol_x, Update update, double *result) {
+    dmk_ctx *ctx = h->ctx;
+    int rc;
+    const int dim = h->diis;
+    const long long nx = h->nx, rs = h->ring_stride();
+    double B[DIIS_MAX][DIIS_MAX] = {{0.0}}, rec[16], e_old, e = 0.0, dE = 0.0, dt = 0.0;
+    if (s.energy) {
+        if ((rc = cc_energy(h, *s.x, h->rec))) return rc;
+        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        e = rec[0];
+    }
+    int it = 0, converged = 0, stored = 0;
+    while (it < max_iter) {
+        ++it;
+        const int slot = dim ? (stored % dim) : 0;
+        double *dst = dim ? s.ring_x + slot * rs : *s.xnew;
+        // the step new - old: a ring slot (the padding between the two parts is zero in every vector), or e1 / e2, free between updates
+        double *e1 = dim ? s.ring_e + slot * rs : s.e1, *e2 = dim ? e1 + h->t2off : s.e2;
+        if ((rc = update(*s.x, dst))) return rc;
+        if (s.energy && (rc = cc_energy(h, dst, h->rec))) return rc;
+        if ((rc = h->E.perm(1.0, dst, "ia", 0.0, e1, "ia"))) return rc;
+        if ((rc = h->E.perm(-1.0, *s.x, "ia", 1.0, e1, "ia"))) return rc;
+        if ((rc = h->E.perm(1.0, dst + h->t2off, "ijab", 0.0, e2, "ijab"))) return rc;
+        if ((rc = h->E.perm(-1.0, *s.x + h->t2off, "ijab", 1.0, e2, "ijab"))) return rc;
+        const int m = dim ? std::min(stored + 1, dim) : 1;
+        if (dim) {
+            for (int q = 0; q < m; ++q)
+                if ((rc = cc_dot(h, nx, e1, s.ring_e + q * rs, 1.0, 0, h->rec + 1 + q))) return rc;
+        } else {
+            if ((rc = cc_dot(h, (long long)h->o * h->v, e1, e1, 1.0, 0, h->rec + 1))) return rc;
+            if ((rc = cc_dot(h, nx - h->t2off, e2, e2, 1.0, 1, h->rec + 1))) return rc;
+        }
+        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, (size_t)(1 + m) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        e_old = e;
+        e = s.energy ? rec[0] : 0.0;
+        dE = e - e_old;
+        dt = std::sqrt(rec[1 + (dim ? slot : 0)]);
+        if (!std::isfinite(e) || !std::isfinite(dt)) return dmk_fail(ctx, DMK_ERR_NOCONV, "%s: non-finite energy or amplitudes in iteration %d", s.who, it);
+        if (std::fabs(dE) < tol_e && dt < tol_x) converged = 1;
+        if (!dim || converged) {
+            if (dim) DMK_HIP(ctx, hipMemcpyAsync(*s.x, dst, (size_t)nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            else std::swap(*s.x, *s.xnew);
+            if (converged) break;
+            continue;
+        }
+        for (int q = 0; q < m; ++q) B[slot][q] = B[q][slot] = rec[1 + q];
+        ++stored;
+        double Bm[DIIS_MAX * DIIS_MAX];
+        LinComb L{};
+        L.m = m;
+        for (int p = 0; p < m; ++p)
+            for (int q = 0; q < m; ++q) Bm[p * m + q] = B[p][q];
+        if (dmk_diis_coeffs(m, Bm, L.c) != DMK_OK) {          // no usable extrapolation: the newest vector
+            for (int q = 0; q < m; ++q) L.c[q] = q == slot ? 1.0 : 0.0;
+        }
+        {
+            FamScope fs(ctx, DMK_FAM_MISC);
+            hipLaunchKernelGGL(cc_lincomb_kernel, dim3(grid_of(nx)), dim3(NT), 0, ctx->stream, nx, L, s.ring_x, rs, *s.x);
+            DMK_CHECK_LAUNCH(ctx);
+        }
+    }
+    if (s.energy && dim && !converged && it > 0) {
+        // left unconverged with a ring: *x is the extrapolated vector, not the update whose energy `e` is.  The energy reported
+        // is the one of the amplitudes dmk_rccsd_get returns (dE stays the difference the convergence test saw)
+        if ((rc = cc_energy(h, *s.x, h->rec))) return rc;
+        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        e = rec[0];
+    }
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    result[0] = e; result[1] = converged; result[2] = it; result[3] = dt; result[4] = dE;
+    return DMK_OK;
+}
 
 }  // namespace
 
@@ -596,6 +951,7 @@ int dmk_rccsd_free(dmk_rccsd *h) {
 
 int dmk_rccsd_init(dmk_rccsd *h) {
     if (!h) return DMK_ERR_INVALID;
+    h->kept = false;
     const int rc = cc_init(h);
     if (rc) return rc;
     DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
@@ -606,6 +962,7 @@ int dmk_rccsd_set(dmk_rccsd *h, const double *t1, const double *t2) {
     if (!h) return DMK_ERR_INVALID;
     if (!t1 || !t2) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_set: NULL amplitudes");
     dmk_ctx *ctx = h->ctx;
+    h->kept = false;
     DMK_HIP(ctx, hipMemcpyAsync(h->x, t1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
     DMK_HIP(ctx, hipMemcpyAsync(h->x + h->t2off, t2, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -625,6 +982,7 @@ int dmk_rccsd_energy(dmk_rccsd *h, double *e_dev) {
 int dmk_rccsd_update(dmk_rccsd *h) {
     if (!h) return DMK_ERR_INVALID;
     if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_update: no amplitudes yet (init or set first)");
+    h->kept = false;
     const int rc = cc_update(h, h->x, h->xnew);
     if (rc) return rc;
     std::swap(h->x, h->xnew);
@@ -638,81 +996,128 @@ int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, do
     if (!result_host || max_iter < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_run: bad arguments");
     int rc;
     if (!h->have_amps && (rc = cc_init(h))) return rc;
-    const int dim = h->diis;
-    const long long nx = h->nx, rs = h->ring_stride();
-    double B[DIIS_MAX][DIIS_MAX] = {{0.0}}, rec[16], e_old, e = 0.0, dE = 0.0, dt = 0.0;
-    if ((rc = cc_energy(h, h->x, h->rec))) return rc;
-    DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+    h->kept = false;
+    // without a ring the step is kept in n1 / tau2, free between updates
+    const Iterate s{&h->x, &h->xnew, h->ring_x, h->ring_e, h->n1, h->tau2, true, "rccsd_run"};
+    return cc_iterate(h, s, max_iter, tol_e, tol_normt, [h](const double *from, double *to) { return cc_update(h, from, to); }, result_host);
+}
+
+int dmk_rccsd_lambda_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host) {
+    if (!bytes_host || nocc < 1 || nvir < 1 || nvir > 512 || nocc > 512 || diis_dim < 0 || diis_dim > DIIS_MAX) return DMK_ERR_INVALID;
+    dmk_rccsd h;
+    h.o = nocc; h.v = nvir; h.diis = diis_dim;
+    h.nx = pad32((long long)nocc * nvir) + (long long)nocc * nocc * nvir * nvir;
+    bytes_host[0] = (int64_t)h.lambda_carve(nullptr);
+    return DMK_OK;
+}
+
+int dmk_rccsd_lambda_init(dmk_rccsd *h) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_lambda_init: no amplitudes yet (run, init or set first)");
+    int rc;
+    if ((rc = lambda_alloc(h))) return rc;
+    DMK_HIP(ctx, hipMemcpyAsync(h->l, h->x, (size_t)h->nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
     DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    e = rec[0];
-    int it = 0, converged = 0, stored = 0;
-    while (it < max_iter) {
-        ++it;
-        const int slot = dim ? (stored % dim) : 0;
-        double *dst = dim ? h->ring_x + slot * rs : h->xnew;
-        // the step new - old: a ring slot (the padding between t1 and t2 is zero in every vector), or n1 / tau2, free between updates
-        double *e1 = dim ? h->ring_e + slot * rs : h->n1, *e2 = dim ? e1 + h->t2off : h->tau2;
-        if ((rc = cc_update(h, h->x, dst))) return rc;
-        if ((rc = cc_energy(h, dst, h->rec))) return rc;
-        if ((rc = h->E.perm(1.0, dst, "ia", 0.0, e1, "ia"))) return rc;
-        if ((rc = h->E.perm(-1.0, h->x, "ia", 1.0, e1, "ia"))) return rc;
-        if ((rc = h->E.perm(1.0, dst + h->t2off, "ijab", 0.0, e2, "ijab"))) return rc;
-        if ((rc = h->E.perm(-1.0, h->x + h->t2off, "ijab", 1.0, e2, "ijab"))) return rc;
-        const int m = dim ? std::min(stored + 1, dim) : 1;
-        if (dim) {
-            for (int q = 0; q < m; ++q)
-                if ((rc = cc_dot(h, nx, e1, h->ring_e + q * rs, 1.0, 0, h->rec + 1 + q))) return rc;
-        } else {
-            if ((rc = cc_dot(h, (long long)h->o * h->v, e1, e1, 1.0, 0, h->rec + 1))) return rc;
-            if ((rc = cc_dot(h, nx - h->t2off, e2, e2, 1.0, 1, h->rec + 1))) return rc;
-        }
-        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, (size_t)(1 + m) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        e_old = e;
-        e = rec[0];
-        dE = e - e_old;
-        dt = std::sqrt(rec[1 + (dim ? slot : 0)]);
-        if (!std::isfinite(e) || !std::isfinite(dt)) return dmk_fail(ctx, DMK_ERR_NOCONV, "rccsd_run: non-finite energy or amplitudes in iteration %d", it);
-        if (std::fabs(dE) < tol_e && dt < tol_normt) converged = 1;
-        if (!dim || converged) {
-            if (dim) DMK_HIP(ctx, hipMemcpyAsync(h->x, dst, (size_t)nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            else std::swap(h->x, h->xnew);
-            if (converged) break;
-            continue;
-        }
-        for (int q = 0; q < m; ++q) B[slot][q] = B[q][slot] = rec[1 + q];
-        ++stored;
-        double Bm[DIIS_MAX * DIIS_MAX];
-        LinComb L{};
-        L.m = m;
-        for (int p = 0; p < m; ++p)
-            for (int q = 0; q < m; ++q) Bm[p * m + q] = B[p][q];
-        if (dmk_diis_coeffs(m, Bm, L.c) != DMK_OK) {          // no usable extrapolation: the newest vector
-            for (int q = 0; q < m; ++q) L.c[q] = q == slot ? 1.0 : 0.0;
-        }
-        {
-            FamScope fs(ctx, DMK_FAM_MISC);
-            hipLaunchKernelGGL(cc_lincomb_kernel, dim3(grid_of(nx)), dim3(NT), 0, ctx->stream, nx, L, h->ring_x, rs, h->x);
-            DMK_CHECK_LAUNCH(ctx);
-        }
-    }
-    if (dim && !converged && it > 0) {
-        // left unconverged with a ring: h->x is the extrapolated vector, not the update whose energy `e` is.  The energy reported
-        // is the one of the amplitudes dmk_rccsd_get returns (dE stays the difference the convergence test saw)
-        if ((rc = cc_energy(h, h->x, h->rec))) return rc;
-        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        e = rec[0];
-    }
+    h->have_l = true;
+    return DMK_OK;
+}
+
+int dmk_rccsd_lambda_set(dmk_rccsd *h, const double *l1, const double *l2) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!l1 || !l2) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_lambda_set: NULL amplitudes");
+    int rc;
+    if ((rc = lambda_alloc(h))) return rc;
+    DMK_HIP(ctx, hipMemcpyAsync(h->l, l1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipMemcpyAsync(h->l + h->t2off, l2, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    result_host[0] = e; result_host[1] = converged; result_host[2] = it; result_host[3] = dt; result_host[4] = dE;
+    h->have_l = true;
+    return DMK_OK;
+}
+
+int dmk_rccsd_lambda_update(dmk_rccsd *h) {
+    if (!h) return DMK_ERR_INVALID;
+    if (!h->have_amps || !h->have_l)
+        return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_lambda_update: needs amplitudes and Lambda amplitudes (lambda_init or lambda_set first)");
+    int rc;
+    if ((rc = lambda_prepare(h))) return rc;
+    if ((rc = lambda_update(h, h->l, h->lnew))) return rc;
+    std::swap(h->l, h->lnew);
+    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
+    return DMK_OK;
+}
+
+int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *result_host) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!result_host || max_iter < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_lambda_run: bad arguments");
+    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_lambda_run: no amplitudes yet (run, init or set first)");
+    int rc;
+    if (!h->have_l && (rc = dmk_rccsd_lambda_init(h))) return rc;
+    if ((rc = lambda_prepare(h))) return rc;
+    // without a ring the step is kept in the adjoints of n1 / tau2, free between sweeps
+    const Iterate s{&h->l, &h->lnew, h->lring_x, h->lring_e, h->n1b, h->tau2, false, "rccsd_lambda_run"};
+    double res[5];
+    if ((rc = cc_iterate(h, s, max_iter, 1.0, tol_normt, [h](const double *from, double *to) { return lambda_update(h, from, to); }, res)))
+        return rc;
+    result_host[0] = res[1]; result_host[1] = res[2]; result_host[2] = res[3];
+    return DMK_OK;
+}
+
+int dmk_rccsd_rdm1(dmk_rccsd *h, double *gamma_dev) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!gamma_dev) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_rdm1: NULL result");
+    if (!h->have_amps || !h->have_l) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_rdm1: needs amplitudes and Lambda amplitudes");
+    const int rc = lambda_rdm1(h, gamma_dev);
+    if (rc) return rc;
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DMK_OK;
+}
+
+int dmk_rccsd_residual(dmk_rccsd *h, double *r1_dev, double *r2_dev) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!r1_dev || !r2_dev) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_residual: NULL result");
+    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_residual: no amplitudes yet (init or set first)");
+    const int rc = cc_residual(h);
+    if (rc) return rc;
+    DMK_HIP(ctx, hipMemcpyAsync(r1_dev, h->n1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipMemcpyAsync(r2_dev, h->R, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DMK_OK;
+}
+
+int dmk_rccsd_lagrangian(dmk_rccsd *h, const double *l1, const double *l2, double *out_dev) {
+    if (!h) return DMK_ERR_INVALID;
+    dmk_ctx *ctx = h->ctx;
+    if (!l1 || !l2 || !out_dev) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_lagrangian: NULL argument");
+    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_lagrangian: no amplitudes yet (init or set first)");
+    int rc;
+    if ((rc = cc_residual(h))) return rc;
+    // l~2 = 2 l2 - l2^T(ab) into S, free after cc_rod; the energy overwrites tau alone
+    if ((rc = h->E.perm(2.0, l2, "ijab", 0.0, h->S, "ijab"))) return rc;
+    if ((rc = h->E.perm(-1.0, l2, "ijba", 1.0, h->S, "ijab"))) return rc;
+    if ((rc = cc_energy(h, h->x, out_dev))) return rc;
+    if ((rc = cc_dot(h, (long long)h->o * h->v, l1, h->n1, 2.0, 1, out_dev))) return rc;
+    if ((rc = cc_dot(h, h->nx - h->t2off, h->S, h->R, 1.0, 1, out_dev))) return rc;
+    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DMK_OK;
 }
 
 int dmk_rccsd_get(dmk_rccsd *h, int what, double *out) {
     if (!h) return DMK_ERR_INVALID;
     dmk_ctx *ctx = h->ctx;
-    if (!out || what < DMK_RCCSD_T1 || what > DMK_RCCSD_EMP2) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_get: bad arguments");
+    if (!out || what < DMK_RCCSD_T1 || what > DMK_RCCSD_L2) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_get: bad arguments");
+    if (what == DMK_RCCSD_L1 || what == DMK_RCCSD_L2) {
+        if (!h->have_l) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_get: no Lambda amplitudes yet (lambda_init, lambda_set or lambda_run first)");
+        const double *ls = what == DMK_RCCSD_L1 ? h->l : h->l + h->t2off;
+        const size_t lc = what == DMK_RCCSD_L1 ? (size_t)h->o * h->v : (size_t)(h->nx - h->t2off);
+        DMK_HIP(ctx, hipMemcpyAsync(out, ls, lc * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return DMK_OK;
+    }
     if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_get: no amplitudes yet (init or set first)");
     const double *src = what == DMK_RCCSD_T1 ? h->x : what == DMK_RCCSD_T2 ? h->x + h->t2off : h->rec + 15;
     const size_t cnt = what == DMK_RCCSD_T1 ? (size_t)h->o * h->v : what == DMK_RCCSD_T2 ? (size_t)(h->nx - h->t2off) : 1;

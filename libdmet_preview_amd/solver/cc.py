@@ -6,9 +6,10 @@ Restricted (closed-shell) CCSD on the device, over the Hartree-Fock object of so
   run_ccsd  (e_corr, t1, t2) over a solver.scf.SCF whose HF() has run, shaped like mp.run_mp2
 
 The seven MO blocks come from dmk_ao2mo_s4 applied to the ERI block the DeviceHF already holds (the ERI is not uploaded again; the
-(vv|vv) block stays 4-fold packed and is never unpacked), the iteration is dmk_rccsd_run.  Not built, each refusing by name: the
-Lambda equations and the densities (and with them CCSD.run / run_dmet_ham, which return a density), UCCSD and GCCSD, (T), frozen
-orbitals, Brueckner and tailored CC, a level shift other than 0 and a damping other than 1.  The module imports without a GPU.
+(vv|vv) block stays 4-fold packed and is never unpacked), the iteration is dmk_rccsd_run.  Not in this module, each refusing by name:
+the Lambda equations and the densities (and with them CCSD.run / run_dmet_ham, which return a density) -- they are
+solver/cc_lambda.py (RCCSDLambda) and solver/cc_solver.py (CCSolver) --, UCCSD and GCCSD, (T), frozen orbitals, Brueckner and
+tailored CC, a level shift other than 0 and a damping other than 1.  The module imports without a GPU.
 """
 import ctypes as C
 
@@ -26,7 +27,9 @@ _BLOCKS = ("oooo", "ovoo", "ovov", "oovv", "ovvo", "ovvv", "vvvv")
 
 
 def _not_built(what):
-    raise NotImplementedError("%s is not built (solver.cc has the restricted T equations and the correlation energy only)" % what)
+    raise NotImplementedError("%s is not built (solver.cc has the restricted T equations and the correlation energy only; the Lambda "
+                              "equations, the one-particle density and run / run_dmet_ham are solver.cc_lambda.RCCSDLambda and "
+                              "solver.cc_solver.CCSolver)" % what)
 
 
 def plan_bytes(nocc, nvir, diis_space):

@@ -1,0 +1,193 @@
+"""
+The second half of restricted CCSD on the device ("Lambda"), over solver.cc.RCCSD: what a DMET impurity solver needs
+besides the correlation energy.
+
+  RCCSDLambda.solve_lambda   the Lambda amplitudes l1, l2 (PySCF's RCCSD l1 / l2) by dmk_rccsd_lambda_run: the reverse sweep of the
+                             amplitude equations, DIIS as for t
+  RCCSDLambda.make_rdm1      the CCSD one-particle density, MO basis ([occupied | virtual] of the object's orbitals) or AO
+  RCCSDLambda.expval         <H'> = H0' + E_HF' + E_corr(t; f', g') + <l~, r(t; f', g')> of ANOTHER Hamiltonian over the same
+                             orbitals in the CCSD state (t, l): linear in H', equal to tr h' gamma + 1/2 Gamma . g' without forming
+                             the two-particle density, and to E_HF + E_corr for H' = H.  It replaces the reference's exp_val_rccsd.
+
+solver.cc.RCCSD keeps refusing these (its tests pin that); solver.cc_solver.CCSolver is the reference-shaped front.  make_rdm2 stays
+unbuilt.  The module imports without a GPU.
+"""
+import ctypes as C
+
+import numpy as np
+
+from libdmet_preview_amd._lib import lib, c_vp, c_dbl, c_i64
+from libdmet_preview_amd.solver import cc, scf
+from libdmet_preview_amd.system import integral
+from libdmet_preview_amd.utils import logger as log
+
+_L1, _L2 = 3, 4
+
+
+def lambda_plan_bytes(nocc, nvir, diis_space):
+    """Bytes of the Lambda allocation of a dmk_rccsd handle: dmk_rccsd_lambda_plan, host arithmetic."""
+    out = (c_i64 * 1)()
+    rc = lib.dmk_rccsd_lambda_plan(int(nocc), int(nvir), int(diis_space), out)
+    if rc != 0:
+        raise ValueError("dmk_rccsd_lambda_plan refuses (nocc, nvir, diis_space) = (%d, %d, %d)" % (nocc, nvir, diis_space))
+    return int(out[0])
+
+
+class RCCSDLambda(cc.RCCSD):
+    def __init__(self, mf, frozen=None, mo_coeff=None, mo_occ=None):
+        cc.RCCSD.__init__(self, mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+        self.l1 = self.l2 = None
+        self.converged_lambda, self.cycles_lambda = False, 0
+
+    # ---- memory ------------------------------------------------------------------------------------------------------------------
+    def memory_plan(self):
+        """cc.RCCSD.memory_plan plus "lambda": the bytes of the handle's second allocation."""
+        plan = cc.RCCSD.memory_plan(self)
+        o = self._nocc[0]
+        plan["lambda"] = lambda_plan_bytes(o, self._scf._n - o, self.diis_space)
+        return plan
+
+    def _check_memory(self):
+        plan = self.memory_plan()
+        need = plan["integrals"] + max(plan["transform"], plan["handle"] + plan["workspace"] + plan["lambda"])
+        if self.max_memory is None:
+            have, what = self._scf._ctx.mem_info()[0], "free on the device"
+        else:
+            have, what = int(float(self.max_memory) * (1 << 20)), "allowed by max_memory"
+        if need > have:
+            raise MemoryError("RCCSD with Lambda, nocc = %d, nvir = %d, diis_space = %d plans %d bytes of device memory (integral blocks "
+                              "%d, handle %d, Lambda state %d, contraction workspace %d, transform workspace %d); %d bytes are %s"
+                              % (self._nocc[0], self._scf._n - self._nocc[0], self.diis_space, need, plan["integrals"], plan["handle"],
+                                 plan["lambda"], plan["workspace"], plan["transform"], have, what))
+
+    # ---- Lambda ------------------------------------------------------------------------------------------------------------------
+    def _need_t(self, t1=None, t2=None):
+        if (t1 is None) != (t2 is None):
+            raise ValueError("amplitudes: both t1 and t2, or neither")
+        if t1 is not None:
+            self._set(t1, t2)
+            self.t1, self.t2 = np.asarray(t1, dtype=np.float64), np.asarray(t2, dtype=np.float64)
+        elif self.t1 is None:
+            self.kernel()
+
+    def _set_l(self, l1, l2):
+        ctx = self._scf._ctx
+        s1, s2 = self._shapes()
+        l1, l2 = np.asarray(l1, dtype=np.float64), np.asarray(l2, dtype=np.float64)
+        if l1.shape != s1 or l2.shape != s2:
+            raise ValueError("Lambda amplitudes of shapes %s, %s; expected %s, %s" % (l1.shape, l2.shape, s1, s2))
+        d1, d2 = ctx.to_device(l1), ctx.to_device(l2)
+        ctx.check(lib.dmk_rccsd_lambda_set(self._handle(), d1.ptr, d2.ptr))
+
+    def _get_l(self):
+        ctx = self._scf._ctx
+        out = []
+        for what, shape in zip((_L1, _L2), self._shapes()):
+            d = ctx.empty(shape, np.float64)
+            ctx.check(lib.dmk_rccsd_get(self._handle(), what, d.ptr))
+            out.append(d.get())
+        return out
+
+    def update_lambda(self, l1, l2, t1=None, t2=None):
+        """ONE application of the Lambda equations at the amplitudes t (default: the current ones): -> (l1new, l2new)."""
+        self._need_t(t1, t2)
+        self._set_l(l1, l2)
+        self._scf._ctx.check(lib.dmk_rccsd_lambda_update(self._handle()))
+        return tuple(self._get_l())
+
+    def solve_lambda(self, t1=None, t2=None, l1=None, l2=None, approx_l=False):
+        """-> (l1, l2) on the host.  Starts from (l1, l2) when both are given, else from l = t; approx_l=True stops there (the
+        lowest order).  Tolerance conv_tol_normt on |dl|_2, at most max_cycle iterations: what the reference's run passes."""
+        if (l1 is None) != (l2 is None):
+            raise ValueError("a restart needs both l1 and l2")
+        self._need_t(t1, t2)
+        ctx, h = self._scf._ctx, self._handle()
+        if l1 is not None:
+            self._set_l(l1, l2)
+        else:
+            ctx.check(lib.dmk_rccsd_lambda_init(h))
+        if approx_l:
+            self.converged_lambda, self.cycles_lambda = True, 0
+        else:
+            res = (c_dbl * 3)()
+            ctx.check(lib.dmk_rccsd_lambda_run(h, int(self.max_cycle), float(self.conv_tol_normt), res))
+            self.converged_lambda, self.cycles_lambda = bool(res[0]), int(res[1])
+            log.debug(0, "RCCSD Lambda: %d iterations (|dl| = %.2e)%s", self.cycles_lambda, res[2],
+                      "" if self.converged_lambda else ", NOT converged")
+        self.l1, self.l2 = self._get_l()
+        return self.l1, self.l2
+
+    # ---- densities ---------------------------------------------------------------------------------------------------------------
+    def _mo(self):
+        return self._c[0][:, self._order[0]]
+
+    def make_rdm1(self, t1=None, t2=None, l1=None, l2=None, ao_repr=False):
+        """The spin-summed CCSD one-particle density (n, n), symmetric, trace = the number of electrons: in the MO basis
+        ([occupied | virtual] columns of the object's orbitals), or C gamma C^T with ao_repr=True.  Solves Lambda first if needed."""
+        self._need_t(t1, t2)
+        if l1 is not None or l2 is not None:
+            self._set_l(l1, l2)
+            self.l1, self.l2 = self._get_l()
+        elif self.l1 is None:
+            self.solve_lambda()
+        ctx, n = self._scf._ctx, self._scf._n
+        d = ctx.empty((n, n), np.float64)
+        ctx.check(lib.dmk_rccsd_rdm1(self._handle(), d.ptr))
+        gam = d.get()
+        if ao_repr:
+            c = self._mo()
+            gam = c @ gam @ c.T
+        return gam
+
+    def make_rdm2(self, *args, **kwargs):
+        cc._not_built("The CCSD two-particle density (make_rdm2); the energy of another Hamiltonian is expval(H0, h1, eri)")
+
+    def residual(self):
+        """(r1, r2) = R_od - d t of the current amplitudes: zero at convergence."""
+        ctx = self._scf._ctx
+        s1, s2 = self._shapes()
+        d1, d2 = ctx.empty(s1, np.float64), ctx.empty(s2, np.float64)
+        ctx.check(lib.dmk_rccsd_residual(self._handle(), d1.ptr, d2.ptr))
+        return d1.get(), d2.get()
+
+    # ---- another Hamiltonian -----------------------------------------------------------------------------------------------------
+    def expval(self, H0, h1, eri):
+        """<H'> of H' = (H0, h1 (n, n), eri: one block in any format system.integral.get_eri_format knows) in the CCSD state of this
+        object, at this object's orbitals.  A probe handle over the seven MO blocks of H' (no DIIS ring) evaluates
+        E_corr(t) + <l~, r(t)>; the probe and its blocks are released before the call returns."""
+        self._need_t()
+        if self.l1 is None:
+            self.solve_lambda()
+        mf = self._scf
+        ctx, n, o = mf._ctx, mf._n, self._nocc[0]
+        v = n - o
+        h1 = np.asarray(h1, dtype=np.float64).reshape(n, n)
+        eri = np.asarray(eri, dtype=np.float64)
+        fmt, spin_dim = integral.get_eri_format(eri, n)
+        if spin_dim:
+            if spin_dim != 1:
+                raise NotImplementedError("expval: a spin-dependent ERI (%d blocks) is not built: unrestricted CCSD is not" % spin_dim)
+            eri = eri[0]
+        d_blk = scf._block_to_dev_s4(ctx, eri, fmt, n)
+        dm = np.asarray(mf.make_rdm1(self.mo_coeff, self.mo_occ), dtype=np.float64)
+        d_dm = ctx.to_device(dm)
+        vj, vk = scf.fock_dev(ctx, n, d_blk, d_dm, d_dm)
+        veff = vj.get() - 0.5 * vk.get()
+        cs = self._mo()
+        e_hf = float(np.sum(dm * (h1 + 0.5 * veff)))
+        d_c, d_f = ctx.to_device(cs), ctx.to_device(cs.T @ (h1 + veff) @ cs)
+        rng = {"o": (d_c, 0, o), "v": (d_c, o, v)}
+        blocks = [scf.ao2mo_block_dev(ctx, n, d_blk, [rng[x] for x in name], compact=(name == "vvvv")) for name in cc._BLOCKS]
+        d_t = [ctx.to_device(a) for a in (self.t1, self.t2, self.l1, self.l2)]
+        d_e = ctx.empty((1,), np.float64)
+        probe = c_vp()
+        ctx.check(lib.dmk_rccsd_create(ctx.h, o, v, d_f.ptr, *([b.ptr for b in blocks] + [v * (v + 1) // 2, 0, C.byref(probe)])))
+        try:
+            ctx.check(lib.dmk_rccsd_set(probe, d_t[0].ptr, d_t[1].ptr))
+            ctx.check(lib.dmk_rccsd_lagrangian(probe, d_t[2].ptr, d_t[3].ptr, d_e.ptr))
+            e = float(d_e.get()[0])
+        finally:
+            lib.dmk_rccsd_free(probe)
+            for a in blocks + d_t + [d_blk, d_dm, d_c, d_f, d_e, vj, vk]:
+                a.free()
+        return float(H0) + e_hf + e

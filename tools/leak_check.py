@@ -108,4 +108,28 @@ def fit(it):
 worst = max(worst, measure("slater.FitVcorEmb (T = 0, fused objective)", fit, rounds=25))
 worst = max(worst, measure("slater.FitVcorEmb finite T + drho_dparam", lambda it: slater.FitVcorEmb(tgt, Lf, basis, Hubbard.VcorLocal(False, False, 4), 12.0,
                                                                                                    return_drho_dparam=True), rounds=25))
+
+# CCSD with Lambda over one device Hartree-Fock (12 orbitals, 8 electrons, a factored ERI): solve_lambda + make_rdm1 + expval, repeated
+from libdmet_preview_amd.solver import scf as dscf, cc_lambda
+rng = np.random.default_rng(21)
+nq, npq = 12, 78
+lev = np.linspace(-1.0, 1.0, nq) + np.where(np.arange(nq) >= 4, 1.5, 0.0)
+q, _ = np.linalg.qr(rng.standard_normal((nq, nq)))
+h1q = (q * lev) @ q.T
+Aq = rng.standard_normal((8, npq))
+eriq = (0.05 / nq) * (Aq.T @ Aq)
+hfq = dscf.SCF(newton_ah=False)
+hfq.set_system(8, 0, False, True)
+hfq.set_integral(nq, 0.0, {"cd": h1q[None]}, {"ccdd": eriq[None]})
+hfq.HF(tol=1e-10, MaxIter=100)
+
+
+def cclambda(it):
+    obj = cc_lambda.RCCSDLambda(hfq.mf)
+    obj.kernel()
+    obj.solve_lambda()
+    obj.make_rdm1()
+    obj.expval(0.0, h1q, eriq)
+    obj.close()
+worst = max(worst, measure("RCCSDLambda: T, solve_lambda, make_rdm1, expval", cclambda, rounds=25))
 print("leak check %s: worst %.2f MB" % ("ok" if worst <= 1.5 else "FOUND A LOSS", worst))
