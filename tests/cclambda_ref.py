@@ -14,6 +14,10 @@ for h = 1e-30.
     rdm1_by_derivative(so, t, l)     dL/df_pq over symmetric unit perturbations of the Fock matrix, plus 2 on the occupied diagonal
     rdm1_explicit(t1, t2, l1, l2)    the closed-shell formulas of the density (the ones the device evaluates), plain numpy
     expval_ref(...)                  H0' + E_HF' + L(t, l; f', g') of another Hamiltonian over the same orbitals
+    lambda_step_reverse / rdm1_reverse / grad_t_reverse   the same derivatives in REVERSE MODE: one backward pass of float64 CPU torch
+                                     autograd through the same update (ccsd_ref.torch_namespace) gives a whole gradient at any shape
+    lambda_run_ref / diis_coeffs_ref the iteration of dmk_rccsd_lambda_run (ring, DIIS weights as the header documents them) over the
+                                     reference sweep: how many sweeps a ring needs; run_loop_start / coupled_system: its test system
     fci_two_electron(sysm)           (E, X): the singlet ground vector of the n^2 problem; gamma_AO = 2 X X^T, <H'> = X^T H' X
     two_electron_matrix(sysm)        the n^2 x n^2 Hamiltonian of fci_two_electron
 """
@@ -42,14 +46,12 @@ def to_so_c(t1, t2):
     return T1, T2
 
 
-def energy_c(so, T1, T2):
-    """ccsd_ref.energy without the cast to float."""
-    return ES("ia,ia", so.fov, T1) + 0.25 * ES("ijab,ijab", so.oovv, T2) + 0.5 * ES("ijab,ia,jb", so.oovv, T1, T1)
+energy_c = CR.energy_of          # ccsd_ref.energy without the cast to float
 
 
-def residual(so, T1, T2):
+def residual(so, T1, T2, xp=CR.NP):
     """r = d (update(T) - T): the projected residual, zero at convergence."""
-    N1, N2 = CR.update(so, T1, T2)
+    N1, N2 = CR.update(so, T1, T2, xp)
     d1 = so.eo[:, None] - so.ev[None, :]
     d2 = d1[:, None, :, None] + d1[None, :, None, :]
     return d1 * (N1 - T1), d2 * (N2 - T2)
@@ -173,6 +175,132 @@ def rdm1_explicit(t1, t2, l1, l2):
     gam[o:, :o] = gam[:o, o:].T
     gam[o:, o:] = dvv + dvv.T
     return gam
+
+
+# ---- reverse mode ----------------------------------------------------------------------------------------------------------------
+_SO_ARRAYS = ("foo", "fov", "fvv", "eo", "ev", "oooo", "ooov", "oovv", "ovov", "ovvv", "vvvv")
+
+
+def _torch_so(so, f_mo=None):
+    """(torch, namespace, copy of `so` over float64 CPU tensors).  f_mo: a tensor that replaces the Fock matrix as with_fock does,
+    every Fock block derived from it inside the graph."""
+    import torch
+    s2 = copy.copy(so)
+    for name in _SO_ARRAYS:
+        setattr(s2, name, torch.from_numpy(np.ascontiguousarray(getattr(so, name), dtype=np.float64)))
+    if f_mo is not None:
+        o = so.o
+        two = lambda a: torch.kron(torch.eye(2, dtype=torch.float64), a)
+        s2.foo, s2.fov, s2.fvv = two(f_mo[:o, :o]), two(f_mo[:o, o:]), two(f_mo[o:, o:])
+        s2.eo, s2.ev = torch.diag(s2.foo), torch.diag(s2.fvv)
+        s2.f_mo = f_mo
+    return torch, CR.torch_namespace(), s2
+
+
+def _lagrangian_t(torch, xp, st, T1, T2, l1, l2):
+    """The spin-orbital L = E(T) + sum Lam1 r1 + 1/4 sum Lam2 r2 with Lam = to_so(l) as a 0-d tensor, and the denominators."""
+    Lam1, Lam2 = (torch.from_numpy(x) for x in CR.to_so(np.asarray(l1, dtype=np.float64), np.asarray(l2, dtype=np.float64)))
+    r1, r2 = residual(st, T1, T2, xp)
+    d1 = st.eo[:, None] - st.ev[None, :]
+    d2 = d1[:, None, :, None] + d1[None, :, None, :]
+    return CR.energy_of(st, T1, T2, xp) + torch.sum(Lam1 * r1) + 0.25 * torch.sum(Lam2 * r2), Lam1, Lam2, d1, d2
+
+
+def _grad_t(so, t1, t2, l1, l2):
+    """dL/dT over the FULL spin-orbital tensors (every element an independent leaf), the doubles part antisymmetrised onto the
+    unique amplitudes:  -> (L, G1, G2a, Lam1, Lam2, d1, d2) as numpy."""
+    torch, xp, st = _torch_so(so)
+    T1, T2 = (torch.from_numpy(x).requires_grad_(True) for x in CR.to_so(np.asarray(t1, dtype=np.float64), np.asarray(t2, dtype=np.float64)))
+    L, Lam1, Lam2, d1, d2 = _lagrangian_t(torch, xp, st, T1, T2, l1, l2)
+    L.backward()
+    G1, G2 = T1.grad.numpy(), T2.grad.numpy()
+    G2a = G2 - G2.transpose(1, 0, 2, 3) - G2.transpose(0, 1, 3, 2) + G2.transpose(1, 0, 3, 2)
+    return float(L.detach()), G1, G2a, Lam1.numpy(), Lam2.numpy(), d1.numpy(), d2.numpy()
+
+
+def lambda_step_reverse(so, t1, t2, l1, l2):
+    """ONE sweep of the Lambda equations on restricted amplitudes, (l1new, l2new) = from_so(Lam + (dL/dT) / d): the Jacobi step on
+    the stationarity condition dL/dT = 0 with the Fock-diagonal denominators (d Lam_new = g + (J + diag d)^T Lam in the notation of
+    lambda_by_jacobian, since dL/dx = g + J^T Lam)."""
+    _, G1, G2a, Lam1, Lam2, d1, d2 = _grad_t(so, t1, t2, l1, l2)
+    return CR.from_so(Lam1 + G1 / d1, Lam2 + G2a / d2)
+
+
+def grad_t_reverse(so, t1, t2, l1, l2):
+    """(L, dL/dT1 (O, V), dL/dT2 over the unique amplitudes spread antisymmetrically (O, O, V, V)) in spin orbitals: zero at the
+    solution of the Lambda equations."""
+    return _grad_t(so, t1, t2, l1, l2)[:3]
+
+
+def rdm1_reverse(so, t1, t2, l1, l2):
+    """gamma (n, n) = sym(dL/df) + 2 on the occupied diagonal for ANY (t, l): the Fock matrix is the leaf, its blocks and the
+    denominators derived from it as with_fock does."""
+    import torch
+    f = torch.from_numpy(np.array(so.f_mo, dtype=np.float64)).requires_grad_(True)
+    torch, xp, st = _torch_so(so, f)
+    T1, T2 = (torch.from_numpy(x) for x in CR.to_so(np.asarray(t1, dtype=np.float64), np.asarray(t2, dtype=np.float64)))
+    _lagrangian_t(torch, xp, st, T1, T2, l1, l2)[0].backward()
+    G = f.grad.numpy()
+    gam = 0.5 * (G + G.T)
+    gam[:so.o, :so.o] += 2.0 * np.eye(so.o)
+    return gam
+
+
+def diis_coeffs_ref(B):
+    """The DIIS weights as include/libdmetk.h documents them for dmk_diis_coeffs, in numpy: the Gram matrix scaled to a unit largest
+    diagonal, bordered with ones, pseudo-inverted on (0, ..., 0, 1) with the directions of |w| <= 1e-13 dropped, normalised."""
+    m = B.shape[0]
+    A = np.zeros((m + 1, m + 1))
+    A[:m, :m] = 0.5 * (B + B.T) / np.abs(np.diag(B)).max()
+    A[m, :m] = A[:m, m] = 1.0
+    w, V = np.linalg.eigh(A)
+    keep = np.abs(w) > 1e-13
+    c = (V[:m, keep] * (V[m, keep] / w[keep])).sum(axis=1)
+    return c / c.sum()
+
+
+def lambda_run_ref(so, t1, t2, l1, l2, ring, tol, max_iter=200):
+    """The iteration of dmk_rccsd_lambda_run over the REFERENCE sweep (lambda_step_reverse): a ring of `ring` (sweep, step) pairs,
+    the newest overwriting the oldest, the next l their DIIS combination; ring = 0: plain sweeping.  Converged when the 2-norm of a
+    step is below tol; the l kept is then that sweep's.  -> (l1, l2, sweeps, |dl|), sweeps = -1 when max_iter did not suffice."""
+    o, v = t1.shape
+    split = lambda x: (x[:o * v].reshape(o, v), x[o * v:].reshape(o, o, v, v))
+    x = np.concatenate([np.ravel(l1), np.ravel(l2)])
+    X, E, dl = [], [], np.inf
+    for it in range(1, max_iter + 1):
+        new = np.concatenate([np.ravel(a) for a in lambda_step_reverse(so, t1, t2, *split(x))])
+        step = new - x
+        dl = float(np.sqrt(np.sum(step ** 2)))
+        if dl < tol or not ring:
+            x = new
+            if dl < tol:
+                return split(x) + (it, dl)
+            continue
+        if len(X) < ring:
+            X.append(new)
+            E.append(step)
+        else:
+            X[(it - 1) % ring], E[(it - 1) % ring] = new, step
+        x = diis_coeffs_ref(np.array(E) @ np.array(E).T) @ np.array(X)
+    return split(x) + (-1, dl)
+
+
+def run_loop_start(o, v):
+    """The l the ring tests of tests/test_gpu_cclambda_shapes.py start from: random, symmetric, of scale 0.1 like every other l of
+    that file.  (From l = t the run-loop system is 2.5e-4 from its solution and a ring of 12 converges in 9 sweeps, before it is
+    full; tests/test_host_cclambda.py pins both counts over the reference sweep.)"""
+    return CR.random_amplitudes(np.random.default_rng(21), o, v)
+
+
+def coupled_system(o, v, scale):
+    """(system, canonical host orbitals) of ccsd_ref.uneven_system with the coupling `lam` multiplied by `scale` BEFORE the numpy
+    SCF: the system of the run-loop tests of tests/test_gpu_cclambda_shapes.py at (2, 3), scale 2.0 (l differs from t by 1e-4)."""
+    from tests import scf_ref as R
+    sysm = R.System(o + v, 500 + 37 * o + v, [o])
+    sysm.lam *= scale
+    ref = R.scf(sysm.h1[None], sysm.veff_rhf, [o], True)
+    assert ref["converged"], (o, v, scale)
+    return sysm, ref["mo_coeff"]
 
 
 def expval_ref(sysm2, H0, C, o, t1, t2, l1, l2):

@@ -10,6 +10,8 @@ t_ij^ab = t_ji^ba) maps to spin-orbital amplitudes as   aa = t - t^T(ab),   ab =
     spin_orbital(sysm, C, nocc)   -> SO: the Fock blocks and the <pq||rs> blocks at the orbitals C (columns, occupied first)
     update(so, T1, T2)            one application of the amplitude equations (Jacobi step with the Fock diagonal)
     energy(so, T1, T2)            f_ia t_ia + 1/4 <ij||ab> t_ijab + 1/2 <ij||ab> t_ia t_jb
+    NP / torch_namespace()        update and energy_of are stated ONCE, over an array namespace (einsum, diag, axis permutation): numpy
+                                  by default, torch tensors for the reverse-mode derivatives of tests/cclambda_ref.py
     solve(so, tol)                DIIS-free iteration from the MP2 guess until the amplitudes move by less than tol
     to_so / from_so               the maps between restricted and spin-orbital amplitudes
     r_update / r_energy / r_solve the same through the maps, on restricted amplitudes
@@ -24,6 +26,25 @@ import numpy as np
 from tests import mp2_ref as M
 
 ES = lambda *a: np.einsum(*a, optimize=True)
+
+
+class NP(object):
+    """The array namespace of the equations below for numpy arrays (real or complex)."""
+    es = staticmethod(ES)
+    diag = staticmethod(np.diag)
+    tr = staticmethod(lambda x, *axes: x.transpose(*axes))
+
+
+def torch_namespace():
+    """The same three operations for torch tensors (imported here: the module imports without torch), so that autograd can go
+    through update / energy_of: tests/cclambda_ref.py, the reverse-mode references."""
+    import torch
+
+    class TORCH(object):
+        es = staticmethod(torch.einsum)
+        diag = staticmethod(torch.diag)
+        tr = staticmethod(lambda x, *axes: x.permute(*axes))
+    return TORCH
 
 
 class SO(object):
@@ -74,21 +95,23 @@ def _denoms(so):
     return d1, d1[:, None, :, None] + d1[None, :, None, :]
 
 
-def update(so, T1, T2):
-    """One step of Stanton et al. eqs. 1-13; T1 (O, V), T2 (O, O, V, V) over spin orbitals."""
+def update(so, T1, T2, xp=NP):
+    """One step of Stanton et al. eqs. 1-13; T1 (O, V), T2 (O, O, V, V) over spin orbitals.  xp: the array namespace of `so` and the
+    amplitudes (NP, or torch_namespace() for tensors)."""
+    ES, diag, tr = xp.es, xp.diag, xp.tr
     oooo, ooov, oovv, ovov, ovvv, vvvv = so.oooo, so.ooov, so.oovv, so.ovov, so.ovvv, so.vvvv
     fov = so.fov
-    foo_od, fvv_od = so.foo - np.diag(so.eo), so.fvv - np.diag(so.ev)
+    foo_od, fvv_od = so.foo - diag(so.eo), so.fvv - diag(so.ev)
     tt = ES("ia,jb->ijab", T1, T1)
-    tau_t = T2 + 0.5 * (tt - tt.transpose(0, 1, 3, 2))
-    tau = T2 + tt - tt.transpose(0, 1, 3, 2)
+    tau_t = T2 + 0.5 * (tt - tr(tt, 0, 1, 3, 2))
+    tau = T2 + tt - tr(tt, 0, 1, 3, 2)
     # <am||ef> = -<ma||ef>;  <mb||ej> = -<mb||je>;  <mn||ej> = -<mn||je>
     Fae = fvv_od - 0.5 * ES("me,ma->ae", fov, T1) + ES("mf,mafe->ae", T1, ovvv) - 0.5 * ES("mnaf,mnef->ae", tau_t, oovv)
     Fmi = foo_od + 0.5 * ES("ie,me->mi", T1, fov) + ES("ne,mnie->mi", T1, ooov) + 0.5 * ES("inef,mnef->mi", tau_t, oovv)
     Fme = fov + ES("nf,mnef->me", T1, oovv)
     Wmnij = oooo + ES("je,mnie->mnij", T1, ooov) - ES("ie,mnje->mnij", T1, ooov) + 0.25 * ES("ijef,mnef->mnij", tau, oovv)
     Wabef = vvvv + ES("mb,maef->abef", T1, ovvv) - ES("ma,mbef->abef", T1, ovvv) + 0.25 * ES("mnab,mnef->abef", tau, oovv)
-    Wmbej = -ovov.transpose(0, 1, 3, 2) + ES("jf,mbef->mbej", T1, ovvv) + ES("nb,mnje->mbej", T1, ooov) \
+    Wmbej = -tr(ovov, 0, 1, 3, 2) + ES("jf,mbef->mbej", T1, ovvv) + ES("nb,mnje->mbej", T1, ooov) \
         - ES("jnfb,mnef->mbej", 0.5 * T2 + ES("jf,nb->jnfb", T1, T1), oovv)
     # T1
     r1 = fov + ES("ie,ae->ia", T1, Fae) - ES("ma,mi->ia", T1, Fmi) + ES("imae,me->ia", T2, Fme) - ES("nf,naif->ia", T1, ovov) \
@@ -96,23 +119,29 @@ def update(so, T1, T2):
     # T2
     Fbe = Fae - 0.5 * ES("mb,me->be", T1, Fme)
     x = ES("ijae,be->ijab", T2, Fbe)
-    r2 = oovv + x - x.transpose(0, 1, 3, 2)
+    r2 = oovv + x - tr(x, 0, 1, 3, 2)
     Fmj = Fmi + 0.5 * ES("je,me->mj", T1, Fme)
     x = ES("imab,mj->ijab", T2, Fmj)
-    r2 = r2 - (x - x.transpose(1, 0, 2, 3))
+    r2 = r2 - (x - tr(x, 1, 0, 2, 3))
     r2 = r2 + 0.5 * ES("mnab,mnij->ijab", tau, Wmnij) + 0.5 * ES("ijef,abef->ijab", tau, Wabef)
     x = ES("imae,mbej->ijab", T2, Wmbej) + ES("ie,ma,mbje->ijab", T1, T1, ovov)          # - t t <mb||ej> = + t t <mb||je>
-    r2 = r2 + x - x.transpose(1, 0, 2, 3) - x.transpose(0, 1, 3, 2) + x.transpose(1, 0, 3, 2)
+    r2 = r2 + x - tr(x, 1, 0, 2, 3) - tr(x, 0, 1, 3, 2) + tr(x, 1, 0, 3, 2)
     x = -ES("ie,jeab->ijab", T1, ovvv)                                                    # <ab||ej> = -<je||ab>
-    r2 = r2 + x - x.transpose(1, 0, 2, 3)
+    r2 = r2 + x - tr(x, 1, 0, 2, 3)
     x = ES("ma,ijmb->ijab", T1, ooov)                                                     # <mb||ij> = <ij||mb>
-    r2 = r2 - (x - x.transpose(0, 1, 3, 2))
+    r2 = r2 - (x - tr(x, 0, 1, 3, 2))
     d1, d2 = _denoms(so)
     return r1 / d1, r2 / d2
 
 
+def energy_of(so, T1, T2, xp=NP):
+    """The correlation energy as a 0-d array of the namespace (complex amplitudes and tensors keep their type)."""
+    ES = xp.es
+    return ES("ia,ia", so.fov, T1) + 0.25 * ES("ijab,ijab", so.oovv, T2) + 0.5 * ES("ijab,ia,jb", so.oovv, T1, T1)
+
+
 def energy(so, T1, T2):
-    return float(ES("ia,ia", so.fov, T1) + 0.25 * ES("ijab,ijab", so.oovv, T2) + 0.5 * ES("ijab,ia,jb", so.oovv, T1, T1))
+    return float(energy_of(so, T1, T2))
 
 
 def mp2_guess(so):

@@ -34,7 +34,7 @@ from tests import ccsd_ref as CR
 pytestmark = pytest.mark.gpu
 
 DMK_OK, DMK_ERR_INVALID, DMK_ERR_STATE = 0, -1, -5          # include/libdmetk.h
-T1, T2, EMP2 = 0, 1, 2
+T1, T2, EMP2, L1, L2 = 0, 1, 2, 3, 4
 TOL = 1e-10
 PAD = 3
 SHAPES = [(1, 1), (2, 1), (1, 2), (5, 1), (1, 40), (40, 2), (33, 3), (3, 33), (2, 40)]
@@ -53,7 +53,8 @@ def _bits(a):
 
 
 class Handle(object):
-    """One dmk_rccsd over host blocks uploaded here (the handle borrows them: they live as long as this object)."""
+    """One dmk_rccsd over host blocks uploaded here (the handle borrows them: they live as long as this object).  The Lambda entries
+    are used by tests/test_gpu_cclambda_shapes.py."""
 
     def __init__(self, ctx, o, v, fock, blocks, diis=0):
         from libdmet_preview_amd._lib import lib, c_vp
@@ -76,7 +77,7 @@ class Handle(object):
 
     def get(self, what):
         o, v = self.o, self.v
-        d = self.ctx.empty(((o, v), (o, o, v, v), (1,))[what], np.float64)
+        d = self.ctx.empty(((o, v), (o, o, v, v), (1,), (o, v), (o, o, v, v))[what], np.float64)
         self.ctx.check(self.lib.dmk_rccsd_get(self.h, what, d.ptr))
         return d.get()
 
@@ -97,6 +98,44 @@ class Handle(object):
         res = (c_dbl * 5)(*([np.nan] * 5))
         self.ctx.check(self.lib.dmk_rccsd_run(self.h, int(max_iter), tol_e, tol_normt, res))
         return tuple(float(x) for x in res)
+
+    # ---- Lambda (tests/test_gpu_cclambda_shapes.py) ------------------------------------------------------------------------------
+    def lambda_init(self):
+        self.ctx.check(self.lib.dmk_rccsd_lambda_init(self.h))
+
+    def lambda_set(self, l1, l2):
+        d1, d2 = self.ctx.to_device(l1), self.ctx.to_device(l2)
+        self.ctx.check(self.lib.dmk_rccsd_lambda_set(self.h, d1.ptr, d2.ptr))
+
+    def lambda_update(self):
+        self.ctx.check(self.lib.dmk_rccsd_lambda_update(self.h))
+
+    def lambda_run(self, max_iter, tol_normt=TOL_NORMT):
+        """-> (converged, iterations, |dl|)"""
+        from libdmet_preview_amd._lib import c_dbl
+        res = (c_dbl * 3)(*([np.nan] * 3))
+        self.ctx.check(self.lib.dmk_rccsd_lambda_run(self.h, int(max_iter), tol_normt, res))
+        return tuple(float(x) for x in res)
+
+    def lams(self):
+        return self.get(L1), self.get(L2)
+
+    def rdm1(self):
+        n = self.o + self.v
+        d = self.ctx.empty((n, n), np.float64)
+        self.ctx.check(self.lib.dmk_rccsd_rdm1(self.h, d.ptr))
+        return d.get()
+
+    def residual(self):
+        o, v = self.o, self.v
+        d1, d2 = self.ctx.empty((o, v), np.float64), self.ctx.empty((o, o, v, v), np.float64)
+        self.ctx.check(self.lib.dmk_rccsd_residual(self.h, d1.ptr, d2.ptr))
+        return d1.get(), d2.get()
+
+    def lagrangian(self, l1, l2):
+        d1, d2, d = self.ctx.to_device(l1), self.ctx.to_device(l2), self.ctx.empty((1,), np.float64)
+        self.ctx.check(self.lib.dmk_rccsd_lagrangian(self.h, d1.ptr, d2.ptr, d.ptr))
+        return float(d.get()[0])
 
 
 def _host(o, v, rotated):
