@@ -787,6 +787,20 @@ int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *r
 int dmk_rccsd_rdm1(dmk_rccsd *h, double *gamma_dev);
 int dmk_rccsd_residual(dmk_rccsd *h, double *r1_dev, double *r2_dev);
 int dmk_rccsd_lagrangian(dmk_rccsd *h, const double *l1, const double *l2, double *out_dev);
+/* The perturbative triples (T) of the handle's CURRENT t1, t2 (csrc/ccsd_t.hip): the arithmetic of PySCF's closed-shell
+ * ccsd_t, Fock-DIAGONAL denominators and the f_ov term kept -- the usual (T) at canonical orbitals, PySCF's number (not an
+ * orbital-invariant one) at rotated ones.  Only the unique triples a >= b >= c are visited; W of a batch of triples lives in a
+ * workspace allocated by the call and freed before it returns, sized for as many triples in flight as the byte budget holds.  The
+ * (vv|vv) block is not read.  No atomics: one partial sum per unique triple, then one fixed-order sum, so the result is bit-identical
+ * between calls and independent of the budget.
+ *   dmk_rccsd_t_plan  (HOST, no context) bytes_host[2]: the fixed bytes of the call's workspace and the bytes per triple in flight;
+ *                     DMK_ERR_INVALID for nocc, nvir outside [1, 512]
+ *   dmk_rccsd_t       max_bytes: the budget of that workspace (<= 0: three quarters of what is free on the device);
+ *                     DMK_ERR_NOMEM BEFORE any allocation when fixed + one triple exceed it.  result_host[2]: E_(T), batches used.
+ *                     The handle's amplitudes, its Lambda state and its kept intermediates are left untouched.  E_(T) is exactly 0
+ *                     in exact arithmetic for nocc = 1 or nvir = 1.  Returns after the stream drained. */
+int dmk_rccsd_t_plan(int nocc, int nvir, int64_t *bytes_host /*[2]*/);
+int dmk_rccsd_t(dmk_rccsd *h, int64_t max_bytes, double *result_host /*[2]*/);
 
 /* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
  * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the

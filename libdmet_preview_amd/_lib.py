@@ -168,6 +168,8 @@ PROTOTYPES = {
     "dmk_rccsd_rdm1": (c_int, [c_vp, c_vp]),
     "dmk_rccsd_residual": (c_int, [c_vp, c_vp, c_vp]),
     "dmk_rccsd_lagrangian": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "dmk_rccsd_t_plan": (c_int, [c_int, c_int, P(c_i64)]),
+    "dmk_rccsd_t": (c_int, [c_vp, c_i64, P(c_dbl)]),
     "dmk_dmet_h2_scaled":(c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
     "dmk_rho_glob": (c_int, [c_vp, _int3, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "dmk_sym_norm_bound": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),

@@ -23,6 +23,7 @@
 //                    of R), the one-particle density (cc_rdm1_kernel assembles it), the residual without a division (cc_resid_kernel)
 //                    and the Lagrangian E_corr + <l~, r> of a probe handle; their state is a third allocation, made on first use.
 #include "devres.h"
+#include "ccsd_view.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -877,6 +878,18 @@ int cc_iterate(dmk_rccsd *h, const Iterate &s, int max_iter, double tol_e, doubl
 }
 
 }  // namespace
+
+// ---- what csrc/ccsd_t.hip (K22) reads of a handle (ccsd_view.h) -------------------------------------------------------------------
+int dmk_rccsd_view(dmk_rccsd *h, RccsdView *out) {
+    *out = RccsdView{h->ctx, h->o, h->v, h->have_amps, h->ovoo, h->ovov, h->ovvv, h->fov, h->eo, h->ev, h->x, h->x + h->t2off};
+    return DMK_OK;
+}
+
+int dmk_cc_perm(dmk_ctx *ctx, int o, int v, double alpha, const double *in, const char *si, double beta, double *out, const char *so) {
+    Engine E;
+    E.ctx = ctx; E.o = o; E.v = v;
+    return E.perm(alpha, in, si, beta, out, so);
+}
 
 extern "C" {
 

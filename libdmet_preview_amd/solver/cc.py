@@ -8,8 +8,10 @@ Restricted (closed-shell) CCSD on the device, over the Hartree-Fock object of so
 The seven MO blocks come from dmk_ao2mo_s4 applied to the ERI block the DeviceHF already holds (the ERI is not uploaded again; the
 (vv|vv) block stays 4-fold packed and is never unpacked), the iteration is dmk_rccsd_run.  Not in this module, each refusing by name:
 the Lambda equations and the densities (and with them CCSD.run / run_dmet_ham, which return a density) -- they are
-solver/cc_lambda.py (RCCSDLambda) and solver/cc_solver.py (CCSolver) --, UCCSD and GCCSD, (T), frozen orbitals, Brueckner and
-tailored CC, a level shift other than 0 and a damping other than 1.  The module imports without a GPU.
+solver/cc_lambda.py (RCCSDLambda) and solver/cc_solver.py (CCSolver) --, the perturbative triples (T) -- the energy is
+solver/ccsd_t.py (kernel), reached through RCCSDLambda.ccsd_t and CCSolver.ccsd_t; the run option ccsdt=True also needs the (T) Lambda
+equations and the (T) densities, which are not built --, UCCSD and GCCSD, frozen orbitals, Brueckner and tailored CC, a level shift
+other than 0 and a damping other than 1.  The module imports without a GPU.
 """
 import ctypes as C
 
@@ -79,7 +81,7 @@ class RCCSD(PostHFBase):
         _not_built("The CCSD two-particle density (make_rdm2, it needs the Lambda equations)")
 
     def ccsd_t(self, *args, **kwargs):
-        _not_built("The perturbative triples (T) (ccsd_t)")
+        _not_built("The perturbative triples (T) (ccsd_t; the energy is solver.ccsd_t.kernel, RCCSDLambda.ccsd_t and CCSolver.ccsd_t)")
 
     # ---- life time ---------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -228,7 +230,8 @@ def GCCSD(*args, **kwargs):
 
 
 _RUN_OPTIONS = ("conv_tol", "conv_tol_normt", "max_cycle", "diis_space", "level_shift", "iterative_damping", "max_memory")
-_UNBUILT_RUN_OPTIONS = {"ccsdt": "The perturbative triples (T) (ccsdt)", "ccsdt_energy": "The perturbative triples (T) (ccsdt_energy)",
+_T_RUN = "The (T) Lambda equations and the (T) densities (%s; the (T) energy alone is solver.ccsd_t.kernel)"
+_UNBUILT_RUN_OPTIONS = {"ccsdt": _T_RUN % "ccsdt", "ccsdt_energy": _T_RUN % "ccsdt_energy",
                         "bcc": "Brueckner CC (bcc)", "tcc": "Tailored CC (tcc)", "calc_rdm2": "The CCSD two-particle density (calc_rdm2)",
                         "approx_l": "The Lambda equations (approx_l)", "restart": "Restart files (restart)"}
 

@@ -8,6 +8,7 @@ besides the correlation energy.
   RCCSDLambda.expval         <H'> = H0' + E_HF' + E_corr(t; f', g') + <l~, r(t; f', g')> of ANOTHER Hamiltonian over the same
                              orbitals in the CCSD state (t, l): linear in H', equal to tr h' gamma + 1/2 Gamma . g' without forming
                              the two-particle density, and to E_HF + E_corr for H' = H.  It replaces the reference's exp_val_rccsd.
+  RCCSDLambda.ccsd_t         the perturbative triples E_(T) of the amplitudes (solver/ccsd_t.py), kept in e_t
 
 solver.cc.RCCSD keeps refusing these (its tests pin that); solver.cc_solver.CCSolver is the reference-shaped front.  make_rdm2 stays
 unbuilt.  The module imports without a GPU.
@@ -17,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from libdmet_preview_amd._lib import lib, c_vp, c_dbl, c_i64
-from libdmet_preview_amd.solver import cc, scf
+from libdmet_preview_amd.solver import cc, ccsd_t, scf
 from libdmet_preview_amd.system import integral
 from libdmet_preview_amd.utils import logger as log
 
@@ -38,6 +39,7 @@ class RCCSDLambda(cc.RCCSD):
         cc.RCCSD.__init__(self, mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
         self.l1 = self.l2 = None
         self.converged_lambda, self.cycles_lambda = False, 0
+        self.e_t = None
 
     # ---- memory ------------------------------------------------------------------------------------------------------------------
     def memory_plan(self):
@@ -116,6 +118,14 @@ class RCCSDLambda(cc.RCCSD):
                       "" if self.converged_lambda else ", NOT converged")
         self.l1, self.l2 = self._get_l()
         return self.l1, self.l2
+
+    # ---- (T) -------------------------------------------------------------------------------------------------------------------
+    def ccsd_t(self, t1=None, t2=None):
+        """E_(T) of the current amplitudes (or of t1, t2): solver.ccsd_t.kernel; PySCF's closed-shell number, Fock-diagonal
+        denominators.  Kept in e_t."""
+        self._need_t(t1, t2)
+        self.e_t = ccsd_t.kernel(self)
+        return self.e_t
 
     # ---- densities ---------------------------------------------------------------------------------------------------------------
     def _mo(self):

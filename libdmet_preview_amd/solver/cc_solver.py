@@ -6,9 +6,11 @@ solver/scf_solver.py.
   run            :618-1153   HF, T, solve_lambda, make_rdm1 -> (onepdm, E)
   run_dmet_ham   :1169-1211  the energy of the CCSD state on a scaled DMET Hamiltonian: RCCSDLambda.expval in place of exp_val_rccsd
   make_rdm1      the density of the last run
+  ccsd_t         :1073-1076  E_(T) of the last run's amplitudes (solver/ccsd_t.py): E_CCSD(T) = E + ccsd_t()
 
-Unrestricted and generalised references, (T), Brueckner / tailored / linear CC, frozen orbitals, the two-particle density, HDF5 output
-and MPI are not built: each raises NotImplementedError by name.  A restart (restart=True) starts T and Lambda from the amplitudes of
+Unrestricted and generalised references, the ccsdt=True path of run / run_dmet_ham (it needs the (T) Lambda equations and the (T)
+densities, _get_ccsdt_drv), Brueckner / tailored / linear CC, frozen orbitals, the two-particle density, HDF5 output and MPI are not
+built: each raises NotImplementedError by name.  A restart (restart=True) starts T and Lambda from the amplitudes of
 the previous run, held in memory only.  The module imports without a GPU; the device context is created by the first call that computes.
 """
 import numpy as np
@@ -65,7 +67,11 @@ class CCSolver(object):
             _refuse("the two-particle density (calc_rdm2)")
         if Mu is not None:
             _refuse("a chemical potential (Mu) in restricted CCSD")
-        for name in ("ccsdt", "ccsdt_energy", "bcc", "ccd", "dump_tl", "fcc_name_save", "remove_h2", "mo_energy_custom", "mo_occ_custom",
+        for name in ("ccsdt", "ccsdt_energy"):
+            if kwargs.get(name, None) not in (None, False):
+                _refuse("%s=%r (the (T) Lambda equations and the (T) densities; the (T) energy alone is ccsd_t() after run())"
+                        % (name, kwargs[name]))
+        for name in ("bcc", "ccd", "dump_tl", "fcc_name_save", "remove_h2", "mo_energy_custom", "mo_occ_custom",
                      "mo_coeff_custom"):
             if kwargs.get(name, None) not in (None, False):
                 _refuse("%s=%r" % (name, kwargs[name]))
@@ -115,7 +121,7 @@ class CCSolver(object):
         if use_calculated_twopdm:
             _refuse("use_calculated_twopdm (the two-particle density)")
         if kwargs.get("ccsdt", False):
-            _refuse("ccsdt")
+            _refuse("ccsdt (the (T) densities)")
         if self.cisolver is None:
             raise RuntimeError("CCSolver.run_dmet_ham: run() first")
         eri = np.asarray(Ham.H2["ccdd"])
@@ -125,6 +131,12 @@ class CCSolver(object):
 
     def make_rdm1(self, Ham=None):
         return self.onepdm
+
+    def ccsd_t(self):
+        """E_(T) of the amplitudes of the last run (PySCF's closed-shell ccsd_t on the device): E_CCSD(T) = E + ccsd_t()."""
+        if self.cisolver is None or not self.optimized:
+            raise RuntimeError("CCSolver.ccsd_t: run() first")
+        return self.cisolver.ccsd_t()
 
     def make_rdm2(self, *args, **kwargs):
         _refuse("the two-particle density (make_rdm2)")

@@ -132,4 +132,16 @@ def cclambda(it):
     obj.expval(0.0, h1q, eriq)
     obj.close()
 worst = max(worst, measure("RCCSDLambda: T, solve_lambda, make_rdm1, expval", cclambda, rounds=25))
+
+# (T) over one solved object: the scoped workspace of dmk_rccsd_t, the default budget and one that forces many batches
+from libdmet_preview_amd.solver import ccsd_t
+objq = cc_lambda.RCCSDLambda(hfq.mf)
+objq.kernel()
+
+
+def triples(it):
+    ccsd_t.kernel(objq)
+    ccsd_t.kernel(objq, max_memory=0.25)
+worst = max(worst, measure("solver.ccsd_t.kernel: (T) in one batch and in many", triples, rounds=25))
+objq.close()
 print("leak check %s: worst %.2f MB" % ("ok" if worst <= 1.5 else "FOUND A LOSS", worst))
