@@ -802,6 +802,50 @@ int dmk_rccsd_lagrangian(dmk_rccsd *h, const double *l1, const double *l2, doubl
 int dmk_rccsd_t_plan(int nocc, int nvir, int64_t *bytes_host /*[2]*/);
 int dmk_rccsd_t(dmk_rccsd *h, int64_t max_bytes, double *result_host /*[2]*/);
 
+/* ---- full configuration interaction of a small impurity (csrc/fci.hip; solver/fci.py of the reference, which
+ * goes through PySCF's direct_spin1 / direct_uhf).  norb <= 32 orbitals, na / nb electrons.  Strings are bit masks ordered by integer
+ * value; the vector is c[Ia][Ib], row-major, Na x Nb with Nb fastest, |Ia Ib> = prod_{p in Ia} a+_p,alpha prod_{q in Ib} a+_q,beta |0>
+ * with the orbitals ascending inside each product.  All determinant counts and offsets are 64-bit.
+ *     H = H0 + sum_s hs_pq Es_pq + 1/2 sum_s g^ss_pqrs (Es_pq Es_rs - d_qr Es_ps) + g^ab_pqrs Ea_pq Eb_rs
+ * spin = 1: h1 (n, n) and eri_aa (n, n, n, n) serve both spins (eri_ab, eri_bb ignored); spin = 2: h1 (2, n, n) and the blocks
+ * aa, ab = (p_a q_a | r_b s_b), bb.  All DEVICE arrays, read at create (nothing is borrowed).
+ *   dmk_fci_plan    (HOST, no context) bytes_host[3]: the fixed bytes of a handle (vector, diagonal, one work vector, 2 max_space
+ *                   Davidson vectors, link tables, integrals, Gram matrix), the bytes per alpha row in flight, the determinant count;
+ *                   DMK_ERR_INVALID for norb outside [1, 32], na / nb outside [0, norb], spin outside 1 | 2, max_space outside [2, 16]
+ *   dmk_fci_create  max_bytes: the budget of the handle (<= 0: three quarters of what is free on the device).  DMK_ERR_NOMEM BEFORE
+ *                   any allocation when fixed + one row exceed it; otherwise as many alpha rows in flight as fit (at most all).
+ *                   Builds the link tables on the host, computes the diagonal (fci_hdiag_kernel) and sets the vector to the unit
+ *                   vector on the lowest-diagonal determinant (lowest index among equals).
+ *   dmk_fci_set / _get   the current vector (DMK_FCI_C) is set from / copied to a device array of Ndet doubles; DMK_FCI_HDIAG is
+ *                   read-only.  The vector is used as given (dmk_fci_run normalises its start).
+ *   dmk_fci_info    info_host[4]: Na, Nb, alpha rows in flight, slabs per product
+ *   dmk_fci_sigma   sigma = (H - H0) c for device vectors that do not overlap.  Slabs of alpha rows: D = E c gathered through the
+ *                   link tables, one dmk_dgemm_batched product with the integral supermatrix, sigma gathered back; every sigma
+ *                   element is owned by one thread, fixed order of additions, no atomics.
+ *   dmk_fci_run     Davidson for the lowest root from the current vector; preconditioner 1 / |H_II - theta|; max_space <= that of create;
+ *                   collapses to the Ritz vector when the space is full.  Converged when |dE| < tol_e and |r|_2 < tol_r (dE of the
+ *                   first iteration is 0: an exact start converges at once).  result_host[5]: E + H0, converged (0 | 1), iterations
+ *                   (= products H c), |r|_2, dE.  max_iter = 0 does nothing and reports E = NaN, converged = 0.  The Ritz vector
+ *                   becomes the current vector.  Fixed-order reductions: a second run gives the same bits.
+ *   dmk_fci_rdm1    out (2, n, n): g^s_pq = <p+_s q_s> of the current vector (taken as normalised), alpha then beta, for both
+ *                   values of spin
+ *   dmk_fci_rdm2    dm2[p,q,r,s] = <p+ r+ s q>; spin = 1: the spin-summed (n, n, n, n); spin = 2: (3, n, n, n, n), blocks
+ *                   aa, ab, bb with ab = <p+_a r+_b s_b q_a>.  One Gram product over the determinants, accumulated slab by slab.
+ * Every call returns after the stream drained. */
+typedef struct dmk_fci dmk_fci;
+enum { DMK_FCI_C = 0, DMK_FCI_HDIAG = 1 };
+int dmk_fci_plan(int norb, int na, int nb, int spin, int max_space, int64_t *bytes_host /*[3]*/);
+int dmk_fci_create(dmk_ctx *ctx, int norb, int na, int nb, int spin, const double *h1, const double *eri_aa, const double *eri_ab,
+                   const double *eri_bb, double h0, int max_space, int64_t max_bytes, dmk_fci **out);
+int dmk_fci_free(dmk_fci *h);
+int dmk_fci_set(dmk_fci *h, const double *c_dev);
+int dmk_fci_get(dmk_fci *h, int what, double *out_dev);
+int dmk_fci_info(dmk_fci *h, int64_t *info_host /*[4]*/);
+int dmk_fci_sigma(dmk_fci *h, const double *c_dev, double *sigma_dev);
+int dmk_fci_run(dmk_fci *h, int max_iter, double tol_e, double tol_r, int max_space, double *result_host /*[5]*/);
+int dmk_fci_rdm1(dmk_fci *h, double *out_dev);
+int dmk_fci_rdm2(dmk_fci *h, double *out_dev);
+
 /* ---- behind the solver (routine/slater.py:1716-2119, routine/slater_helper.py:158-309) ---------
  * Copy of one spin block of an embedding ERI, every element (ij|kl) weighted by (m_i + m_j + m_k + m_l) / 4 with m the
  * indicator of the nimp impurity indices imp_idx_host (host int32, inside [0, n), no repeats; nimp = 0 is legal):

@@ -170,6 +170,16 @@ PROTOTYPES = {
     "dmk_rccsd_lagrangian": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "dmk_rccsd_t_plan": (c_int, [c_int, c_int, P(c_i64)]),
     "dmk_rccsd_t": (c_int, [c_vp, c_i64, P(c_dbl)]),
+    "dmk_fci_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_i64)]),
+    "dmk_fci_create": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_dbl, c_int, c_i64, P(c_vp)]),
+    "dmk_fci_free": (c_int, [c_vp]),
+    "dmk_fci_set": (c_int, [c_vp, c_vp]),
+    "dmk_fci_get": (c_int, [c_vp, c_int, c_vp]),
+    "dmk_fci_info": (c_int, [c_vp, P(c_i64)]),
+    "dmk_fci_sigma": (c_int, [c_vp, c_vp, c_vp]),
+    "dmk_fci_run": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_int, P(c_dbl)]),
+    "dmk_fci_rdm1": (c_int, [c_vp, c_vp]),
+    "dmk_fci_rdm2": (c_int, [c_vp, c_vp]),
     "dmk_dmet_h2_scaled":(c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_i64]),
     "dmk_rho_glob": (c_int, [c_vp, _int3, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "dmk_sym_norm_bound": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),

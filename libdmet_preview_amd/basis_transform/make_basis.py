@@ -6,6 +6,7 @@ every product running through the batched complex MFMA GEMM of libdmetk:
   transform_h1_to_lo     make_basis.py:524-558
   transform_rdm1_to_lo   make_basis.py:590-618
   transform_rdm1_to_ao   make_basis.py:620-644
+  transform_rdm1_to_ao_mol, transform_rdm2_to_ao_mol   make_basis.py:812-917 (no k-points, impurity-sized: numpy on the host)
 """
 import numpy as np
 
@@ -120,3 +121,46 @@ def transform_rdm1_to_ao(dm_lo_lo, C_ao_lo):
     (D, Cf), spin, keep = _spin_stacks(dm_lo_lo, C_ao_lo)
     return _result(_unflatten(_triple("N", Cf, D, "C", Cf), spin, keep), dm_lo_lo, C_ao_lo)
 
+
+
+# ---- molecular (no k-points) densities of an impurity solver: a few dozen orbitals, numpy on the host -----------------------------
+
+def _mol_spin(C_ao_mo, nspin):
+    """C with a leading spin axis of nspin (one set of orbitals is repeated)"""
+    C = np.asarray(C_ao_mo)
+    if C.ndim == 2:
+        C = C[np.newaxis]
+    if C.shape[0] not in (1, nspin):
+        raise ValueError("orbitals of %d spin channels for a density of %d" % (C.shape[0], nspin))
+    return C if C.shape[0] == nspin else np.asarray([C[0]] * nspin)
+
+
+def transform_rdm1_to_ao_mol(dm_mo_mo, C_ao_mo):
+    r"""\gamma^{AO} = C \gamma^{MO} C^{\dagger} without k-points (make_basis.py:812-834).  The spin axis comes from the orbitals; a
+    density without one is shared by their spin channels, orbitals without one serve every spin channel of the density."""
+    dm, C = np.asarray(dm_mo_mo), np.asarray(C_ao_mo)
+    if dm.ndim == 2 and C.ndim == 2:
+        return C @ dm @ C.conj().T
+    nspin = max(dm.shape[0] if dm.ndim == 3 else 1, C.shape[0] if C.ndim == 3 else 1)
+    C = _mol_spin(C, nspin)
+    dm = _mol_spin(dm, nspin)
+    return np.asarray([C[s] @ dm[s] @ C[s].conj().T for s in range(nspin)])
+
+
+def transform_rdm2_to_ao_mol(rdm2_mo, C_ao_mo):
+    r"""\Gamma^{AO}_{pqrs} = \sum C_{pi} C^*_{qj} C_{rk} C^*_{sl} \Gamma^{MO}_{ijkl} without k-points (make_basis.py:866-917): one
+    block (4-d, or a spin axis of 1) with one set of orbitals, or the blocks aa, ab, bb (spin axis of 3) with the orbitals of the
+    first pair of indices from the first and of the second pair from the second spin of the block."""
+    g, C = np.asarray(rdm2_mo), np.asarray(C_ao_mo)
+    one = lambda x, Ca, Cb: np.einsum("pi,qj,rk,sl,ijkl->pqrs", Ca, Ca.conj(), Cb, Cb.conj(), x, optimize=True)
+    if g.ndim == 4:
+        if C.ndim != 2:
+            raise ValueError("a two-particle density without a spin axis needs one set of orbitals")
+        return one(g, C, C)
+    if g.shape[0] == 1:
+        C = _mol_spin(C, 1) if C.ndim == 2 or C.shape[0] == 1 else C
+        return one(g[0], C[0], C[0])[np.newaxis]
+    if g.shape[0] != 3:
+        raise ValueError("a two-particle density with a spin axis of %d (1, or 3: aa, ab, bb)" % g.shape[0])
+    C = _mol_spin(C, 2)
+    return np.asarray([one(g[0], C[0], C[0]), one(g[1], C[0], C[1]), one(g[2], C[1], C[1])])

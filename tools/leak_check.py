@@ -144,4 +144,22 @@ def triples(it):
     ccsd_t.kernel(objq, max_memory=0.25)
 worst = max(worst, measure("solver.ccsd_t.kernel: (T) in one batch and in many", triples, rounds=25))
 objq.close()
+
+# FCI over the same Hamiltonian at 8 orbitals (4, 4): the handle, its slab workspace, Davidson and both densities, one slab and many
+from libdmet_preview_amd.solver import fci as dfci
+gq = np.zeros((8, 8), dtype=np.int64)
+gq[np.tril_indices(8)] = np.arange(36)
+gq = gq + np.tril(gq, -1).T
+eri8 = (0.05 / 8) * np.einsum("Pa,Pb->ab", Aq[:, :36], Aq[:, :36])[gq.reshape(-1)][:, gq.reshape(-1)].reshape(8, 8, 8, 8)
+
+
+def fci_round(it):
+    for mem in (None, 2.0):
+        ci = dfci.DeviceFCI(ctx)
+        ci.max_memory = mem
+        ci.kernel(h1q[:8, :8], eri8, 8, (4, 4))
+        ci.make_rdm1()
+        ci.make_rdm2()
+        ci.close()
+worst = max(worst, measure("solver.fci.DeviceFCI: kernel, make_rdm1, make_rdm2", fci_round, rounds=25))
 print("leak check %s: worst %.2f MB" % ("ok" if worst <= 1.5 else "FOUND A LOSS", worst))
