@@ -686,7 +686,10 @@ int dmk_fci_run(dmk_fci *h, int max_iter, double tol_e, double tol_r, int max_sp
         }
         if ((rc = fci_dots(h, t, t, 0, 1, d))) return rc;
         nrm = std::sqrt(d[0]);
-        if (!(nrm > 1e-14)) break;          // nothing new to add: the space is exhausted (Ndet reached, or an exact start)
+        // nothing new to add: the space is exhausted (Ndet or a symmetry sector reached, or an exact start).  The Ritz pair cannot
+        // improve, and dE is still the last real step (the residual vanished on the step that completed the space): the residual
+        // alone decides.  The correction is r over an energy difference, so the absolute 1e-14 does not depend on the scale of H.
+        if (!(nrm > 1e-14)) { conv = rnorm < tol_r; break; }
         const double s = 1.0 / nrm;
         if ((rc = fci_comb(h, s, t, 0, h->V, vs, d))) return rc;
     }

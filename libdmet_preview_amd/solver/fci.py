@@ -15,8 +15,9 @@ FCI of csrc/fci.hip, laid out like solver/cc_solver.py.
                  run_dmet_ham   :206-259   the energy of a scaled Hamiltonian from onepdm_mo / twopdm_mo (numpy on the host: n is small)
 
 ghf, bcs, Mu, mo_*_custom, a pspace_size other than the default, FCI_AO and MPI are not built: each raises NotImplementedError by
-name.  Convergence: |dE| < conv_tol and |r|_2 < conv_tol_residual (default sqrt(conv_tol), PySCF's rule).  The module imports without
-a GPU; the device context is created by the first call that computes.
+name.  Convergence: |dE| < conv_tol and |r|_2 < conv_tol_residual (default sqrt(conv_tol), PySCF's rule); where the Davidson basis
+exhausts the space (a handful of determinants) the residual alone decides.  The module imports without a GPU; the device context is
+created by the first call that computes.
 """
 import ctypes as C
 

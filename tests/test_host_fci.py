@@ -161,3 +161,67 @@ def test_molecular_density_transforms():
     assert np.abs(mb.transform_rdm2_to_ao_mol(g2[:1], C[0])[0] - mb.transform_rdm2_to_ao_mol(g2[0], C[0])).max() == 0.0
     with pytest.raises(ValueError):
         mb.transform_rdm2_to_ao_mol(g2[:2], C)
+
+
+# ---- the references of tests/test_gpu_fci_edges.py ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("unrestricted", [False, True])
+def test_solvable_hamiltonian_against_dense(unrestricted):
+    """the occupation-pattern spectrum against eigvalsh of the operator-built H; the product of minors is the ground vector"""
+    S = F.solvable(5, 2, 3, unrestricted)
+    sp = F.Space(5, 2, 3)
+    H = sp.dense(S.h1, S.eri)
+    assert np.abs(np.linalg.eigvalsh(H) - S.spectrum()).max() <= 1e-12
+    c = S.ground_vector()
+    assert abs(np.linalg.norm(c) - 1.0) <= 1e-13 and np.linalg.norm(H @ c - S.e0 * c) <= 1e-12
+    assert np.abs(sp.rdm1(c) - S.ground_rdm1()).max() <= 1e-13
+    assert (not unrestricted and np.array_equal(S.h1[0], S.h1[1])) or (unrestricted and np.abs(S.h1[0] - S.h1[1]).max() > 1e-3)
+
+
+@pytest.mark.parametrize("na,nb,unrestricted", [(3, 2, False), (2, 4, True), (6, 1, True)])
+def test_solvable_matrix_form_product(na, nb, unrestricted):
+    S = F.solvable(6, na, nb, unrestricted)
+    sp = F.Space(6, na, nb)
+    x = np.random.default_rng(na).standard_normal(sp.ndet)
+    ref = sp.matvec(S.h1, S.eri, x)
+    assert np.abs(S.matvec(x) - ref).max() <= 1e-12 * np.abs(sp.matvec(S.h1, S.eri, x, True)).max()
+    c = S.ground_vector()
+    assert np.linalg.norm(S.matvec(c) - S.e0 * c) <= 1e-12
+
+
+@pytest.mark.parametrize("unrestricted", [False, True])
+def test_solvable_case_of_the_gpu_test(unrestricted):
+    """(11, 4, 5), 152460 determinants: what the device test relies on -- a gap, a start that overlaps, an eigenvector in closed form"""
+    S = F.solvable(11, 4, 5, unrestricted)
+    sp = F.Space(11, 4, 5)
+    c = S.ground_vector()
+    assert sp.ndet == 152460 and S.gap >= 1e-2
+    assert abs(c[int(np.argmin(sp.hdiag(S.h1, S.eri)))]) >= 1e-3
+    assert abs(np.linalg.norm(c) - 1.0) <= 1e-13 and np.linalg.norm(S.matvec(c) - S.e0 * c) <= 1e-11
+    res = F.davidson(S.matvec, sp.hdiag(S.h1, S.eri))
+    assert res["converged"] == 1 and abs(res["e"] - S.e0) <= 1e-10 and res["iterations"] <= 100
+
+
+@pytest.mark.parametrize("scale", [1.0, 1e3])
+@pytest.mark.parametrize("name", sorted(F.TINY_CASES))
+def test_restated_davidson_on_tiny_spaces(name, scale):
+    """the restatement of the device loop where the basis exhausts the space: converged, and the conditions of the device test"""
+    sp, h1, eri, h0, w, v = F.tiny_case(name, scale)
+    assert sp.ndet <= 12 and (sp.ndet == 1 or w[1] - w[0] >= 1e-2 * scale)
+    H, hd = sp.dense(h1, eri), sp.hdiag(h1, eri)
+    assert abs(v[int(np.argmin(hd)), 0]) >= 1e-3
+    for ms in (12, 2):
+        res = F.davidson(H, hd, max_space=ms, tol_e=1e-12 * scale, tol_r=1e-10 * scale)
+        assert res["converged"] == 1 and res["r"] < 1e-10 * scale and abs(res["e"] - w[0]) <= 1e-10 * scale
+        assert ms == 2 or res["iterations"] <= sp.ndet + 1
+
+
+@pytest.mark.parametrize("name", sorted(F.COLLAPSE_COUNTS))
+def test_restated_davidson_counts(name):
+    """the iteration counts the device tests take their max_iter from (twice these); rounding may move one by a step or two"""
+    sp, h1, eri, h0, e0, gap, c0 = F.solver_case(name)
+    H, hd = sp.dense(h1, eri), sp.hdiag(h1, eri)
+    for ms, want in F.COLLAPSE_COUNTS[name].items():
+        res = F.davidson(H, hd, max_space=ms, max_iter=400)
+        assert res["converged"] == 1 and abs(res["e"] - e0) <= 1e-10
+        assert abs(res["iterations"] - want) <= 2, (ms, res["iterations"], want)
+    assert F.davidson(H, hd, max_iter=5)["converged"] == 0 and F.davidson(H, hd, max_iter=0)["iterations"] == 0
