@@ -720,6 +720,12 @@ int dmk_mp2_uhf(dmk_ctx *ctx, int nocc_a, int nvir_a, int nocc_b, int nvir_b, co
  * DMK_ERR_INVALID before any launch).  All offsets 64-bit.  The launch is enqueued on the context's stream. */
 int dmk_cc_ladder_s4(dmk_ctx *ctx, int64_t m, int nvir, const double *vvvv_s4, int64_t ld, const double *tau, double alpha, double beta,
                      double *out);
+/* The same on the mixed-spin block, the same kernel with two extents:
+ *     out[r][a][B] = beta out[r][a][B] + alpha sum_{c,D} tau[r][c][D] (ac|BD)       a, c < nvir_a; B, D < nvir_b; tau, out: m x nvir_a x nvir_b
+ * vvVV_s4: rows pair(a,c) over nvir_a, columns pair(max(B,D), min(B,D)) over nvir_b, pitch ld >= npair(nvir_b).  m >= 1, both extents
+ * in [1, 512] (others: DMK_ERR_INVALID before any launch).  Bit-reproducible. */
+int dmk_cc_ladder_s4_ab(dmk_ctx *ctx, int64_t m, int nvir_a, int nvir_b, const double *vvVV_s4, int64_t ld, const double *tau, double alpha,
+                        double beta, double *out);
 /* Closed-shell CCSD amplitudes and correlation energy with a general (non-canonical) Fock matrix; the equations are stated in
  * DESIGN.md K21.  fock_mo (n x n, n = nocc + nvir, [occupied | virtual] order) is copied at create; the integral blocks are
  * BORROWED and must outlive the handle: oooo, ovoo, ovov, oovv, ovvo, ovvv unpacked as dmk_ao2mo_s4 writes them ((pq|rs) at
@@ -801,6 +807,42 @@ int dmk_rccsd_lagrangian(dmk_rccsd *h, const double *l1, const double *l2, doubl
  *                     in exact arithmetic for nocc = 1 or nvir = 1.  Returns after the stream drained. */
 int dmk_rccsd_t_plan(int nocc, int nvir, int64_t *bytes_host /*[2]*/);
 int dmk_rccsd_t(dmk_rccsd *h, int64_t max_bytes, double *result_host /*[2]*/);
+
+/* ---- unrestricted CCSD (csrc/uccsd.hip; solver/cc.py:227, :912 and solver/uccsd_ite.py of the reference) ------
+ * The T1 / T2 amplitude equations with general (non-canonical) Fock matrices and the correlation energy over TWO sets of orbitals.
+ * Amplitudes in PySCF's unrestricted layout, stored in full: t1a (oa, va), t1b (ob, vb), t2aa (oa, oa, va, va), t2ab (oa, ob, va,
+ * vb), t2bb (ob, ob, vb, vb); t2aa / t2bb antisymmetric in ij and in ab.
+ * dmk_uccsd_ints: BORROWED device pointers that must outlive the handle.  fock_a / fock_b: the MO Fock matrices, (oa + va)^2 and
+ * (ob + vb)^2, [occupied | virtual], copied at create.  The blocks are (pq|rs) row-major in the order of the letters of their names,
+ * lower case alpha, upper case beta; vvvv, VVVV, vvVV are packed on both sides (dmk_cc_ladder_s4 / _ab), each with its own pitch.
+ * The blocks with a beta bra and an alpha ket (OVoo, OOvv, OVvv) are the transposes of (oo|OV), (vv|OO), (vv|OV).
+ *   dmk_uccsd_plan    (HOST, no context) bytes_host[2]: the handle's allocation and its contraction workspace;
+ *                     DMK_ERR_INVALID unless every extent is in [1, 512] and diis_dim in [0, 12]
+ *   dmk_uccsd_init    the MP2 guess; DMK_UCCSD_EMP2 of dmk_uccsd_get is then its doubles energy
+ *   dmk_uccsd_set / _energy / _update / _run / _get / _free    as their dmk_rccsd_* namesakes; |dt| of result_host[3] is the 2-norm
+ *                     over the five arrays as stored.  DMK_ERR_STATE before init / set. */
+/* out (cols x rows) = in (rows x cols)^T on the device, through 32 x 32 tiles in LDS: how the blocks with a beta bra are made from
+ * their alpha-beta twins.  Enqueued on the context's stream. */
+int dmk_transpose_f64(dmk_ctx *ctx, int64_t rows, int64_t cols, const double *in, double *out);
+typedef struct dmk_uccsd dmk_uccsd;
+typedef struct dmk_uccsd_ints {
+    const double *fock_a, *fock_b;
+    const double *oooo, *ovoo, *ovov, *oovv, *ovvv, *vvvv;
+    const double *OOOO, *OVOO, *OVOV, *OOVV, *OVVV, *VVVV;
+    const double *ooOO, *ovOO, *ovOV, *ooVV, *ovVV, *vvVV;
+    const double *OVoo, *OOvv, *OVvv;
+    int64_t ld_vvvv, ld_VVVV, ld_vvVV;
+} dmk_uccsd_ints;
+enum { DMK_UCCSD_T1A = 0, DMK_UCCSD_T1B = 1, DMK_UCCSD_T2AA = 2, DMK_UCCSD_T2AB = 3, DMK_UCCSD_T2BB = 4, DMK_UCCSD_EMP2 = 5 };
+int dmk_uccsd_plan(int nocc_a, int nvir_a, int nocc_b, int nvir_b, int diis_dim, int64_t *bytes_host /*[2]*/);
+int dmk_uccsd_create(dmk_ctx *ctx, int nocc_a, int nvir_a, int nocc_b, int nvir_b, const dmk_uccsd_ints *ints, int diis_dim, dmk_uccsd **out);
+int dmk_uccsd_init(dmk_uccsd *h);
+int dmk_uccsd_set(dmk_uccsd *h, const double *t1a, const double *t1b, const double *t2aa, const double *t2ab, const double *t2bb);
+int dmk_uccsd_energy(dmk_uccsd *h, double *e_dev);
+int dmk_uccsd_update(dmk_uccsd *h);
+int dmk_uccsd_run(dmk_uccsd *h, int max_iter, double tol_e, double tol_normt, double *result_host /*[5]*/);
+int dmk_uccsd_get(dmk_uccsd *h, int what, double *out);
+int dmk_uccsd_free(dmk_uccsd *h);
 
 /* ---- full configuration interaction of a small impurity (csrc/fci.hip; solver/fci.py of the reference, which
  * goes through PySCF's direct_spin1 / direct_uhf).  norb <= 32 orbitals, na / nb electrons.  Strings are bit masks ordered by integer

@@ -151,6 +151,7 @@ PROTOTYPES = {
     "dmk_mp2_uhf": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                             c_vp, c_vp, c_vp]),
     "dmk_cc_ladder_s4": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_dbl, c_dbl, c_vp]),
+    "dmk_cc_ladder_s4_ab": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_dbl, c_dbl, c_vp]),
     "dmk_rccsd_plan": (c_int, [c_int, c_int, c_int, P(c_i64)]),
     "dmk_rccsd_create": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, P(c_vp)]),
     "dmk_rccsd_init": (c_int, [c_vp]),
@@ -170,6 +171,16 @@ PROTOTYPES = {
     "dmk_rccsd_lagrangian": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "dmk_rccsd_t_plan": (c_int, [c_int, c_int, P(c_i64)]),
     "dmk_rccsd_t": (c_int, [c_vp, c_i64, P(c_dbl)]),
+    "dmk_transpose_f64": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "dmk_uccsd_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_i64)]),
+    "dmk_uccsd_create": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, P(c_vp)]),
+    "dmk_uccsd_init": (c_int, [c_vp]),
+    "dmk_uccsd_set": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dmk_uccsd_energy": (c_int, [c_vp, c_vp]),
+    "dmk_uccsd_update": (c_int, [c_vp]),
+    "dmk_uccsd_run": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_vp]),
+    "dmk_uccsd_get": (c_int, [c_vp, c_int, c_vp]),
+    "dmk_uccsd_free": (c_int, [c_vp]),
     "dmk_fci_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_i64)]),
     "dmk_fci_create": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_dbl, c_int, c_i64, P(c_vp)]),
     "dmk_fci_free": (c_int, [c_vp]),

@@ -2,6 +2,9 @@
 // and the correlation energy, over the MO blocks that dmk_ao2mo_s4 writes.  Replaces cc.CCSD(mf).kernel() behind the reference's
 // CCSD.run (solver/cc.py:905-906, :1029) for a restricted Hamiltonian.  The equations are stated in DESIGN.md K21.
 //
+// The ladder kernel, the permute kernels, the element-wise helpers, the contraction engine and the DIIS iteration are in cc_engine.h,
+// which csrc/uccsd.hip (K24, unrestricted) includes as well; what they are:
+//
 // cc_ladder_kernel   THE HOT KERNEL, the particle-particle ladder out[r][a][b] (+)= sum_cd tau[r][c][d] (ac|bd), the only
 //                    O(o^2 v^4) term, on the 4-fold PACKED (vv|vv) block (rows pair(a,c), columns pair(b,d)); the v^4 tensor is never
 //                    unpacked to memory.  For fixed a (the batch) it is a GEMM  M = rows r, N = b, K = (c, d)  whose B operand
@@ -24,200 +27,9 @@
 //                    and the Lagrangian E_corr + <l~, r> of a probe handle; their state is a third allocation, made on first use.
 #include "devres.h"
 #include "ccsd_view.h"
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
+#include "cc_engine.h"
 
 namespace {
-
-constexpr int NT = 256, BM = 64, BN = 64, BK = 16, LDT = 81;
-constexpr int DOT_GRID = 1024, DIIS_MAX = 12;
-
-long long pair_of(long long k) { return k * (k + 1) / 2; }
-
-struct Ladder {
-    long long m; int v;
-    const double *W; long long ld;
-    const double *tau; double alpha, beta; double *out;
-};
-
-__global__ __launch_bounds__(NT) void cc_ladder_kernel(Ladder g) {
-    __shared__ double As[2][BK][LDT], Bs[2][BK][LDT];
-    const int v = g.v;
-    const long long vv = (long long)v * v;
-    const int tilesN = (v + BN - 1) / BN;
-    const long long tilesM = (g.m + BM - 1) / BM;
-    long long bid = blockIdx.x;
-    const int tn = (int)(bid % tilesN); bid /= tilesN;
-    const long long tm = bid % tilesM;
-    const int a = (int)(bid / tilesM);
-    const long long m0 = tm * BM;
-    const int n0 = tn * BN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int x = lane & 15, q = lane >> 4;
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int c64 = tid & 63, k4 = tid >> 6;          // lanes along b: k = k4 + 4 j
-    const int kg = tid & 15, mg = tid >> 4;           // lanes along k: row / column mg + 16 j
-    const int nd = (v + BK - 1) / BK;                 // chunks of d per c
-    const int nk = v * nd;
-
-    double ra[4], rb[4];
-    auto along_b = [&](int d0) { return d0 >= n0 + BN / 2; };
-    auto load = [&](int t) {
-        const int c = t / nd, d0 = (t - c * nd) * BK;
-        const int hi = a > c ? a : c, lo = a > c ? c : a;
-        const double *row = g.W + ((long long)hi * (hi + 1) / 2 + lo) * g.ld;
-        const double *ta = g.tau + (long long)c * v + d0 + kg;
-        const bool ab = along_b(d0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long long m = m0 + mg + 16 * j;
-            ra[j] = (m < g.m && d0 + kg < v) ? ta[m * vv] : 0.0;
-            const int d = ab ? d0 + k4 + 4 * j : d0 + kg;
-            const int b = ab ? n0 + c64 : n0 + mg + 16 * j;
-            const int h = b > d ? b : d, l = b > d ? d : b;
-            rb[j] = (b < v && d < v) ? row[(long long)h * (h + 1) / 2 + l] : 0.0;
-        }
-    };
-    auto stage = [&](int buf, int t) {
-        const int c = t / nd, d0 = (t - c * nd) * BK;
-        const bool ab = along_b(d0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            As[buf][kg][mg + 16 * j] = ra[j];
-            if (ab) Bs[buf][k4 + 4 * j][c64] = rb[j];
-            else Bs[buf][kg][mg + 16 * j] = rb[j];
-        }
-    };
-
-    d4_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
-    load(0);
-    stage(0, 0);
-    __syncthreads();
-#pragma unroll 1
-    for (int t = 0; t < nk; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < nk) load(t + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK / 4; ++kk) {
-            double fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                fa[i] = As[buf][4 * kk + q][wm + 16 * i + x];
-                fb[i] = Bs[buf][4 * kk + q][wn + 16 * i + x];
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-        if (t + 1 < nk) stage(buf ^ 1, t + 1);      // the other stage was last read before the previous barrier
-        __syncthreads();
-    }
-    // D layout: row = (lane >> 4) + 4 r, column = lane & 15
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long long m = m0 + wm + 16 * i + q + 4 * r;
-                const int b = n0 + wn + 16 * j + x;
-                if (m >= g.m || b >= v) continue;
-                double *p = g.out + m * vv + (long long)a * v + b;
-                const double s = g.alpha * acc[i][j][r];
-                *p = g.beta != 0.0 ? s + g.beta * *p : s;
-            }
-}
-
-int ladder_launch(dmk_ctx *ctx, const Ladder &g) {
-    const long long tilesM = (g.m + BM - 1) / BM, tilesN = (g.v + BN - 1) / BN;
-    const long long blocks = tilesM * tilesN * g.v;
-    if (blocks > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4: a launch of %lld workgroups", blocks);
-    FamScope fs(ctx, DMK_FAM_DGEMM);
-    fs.mfma_flops(2.0 * BM * BN * BK * (double)g.v * ((g.v + BK - 1) / BK) * (double)blocks);
-    hipLaunchKernelGGL(cc_ladder_kernel, dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, g);
-    DMK_CHECK_LAUNCH(ctx);
-    return DMK_OK;
-}
-
-// ---- permute-and-combine -------------------------------------------------------------------------------------------------------
-// Source axes 0..3 (row-major, axis 3 fastest) of extents d[], each with the stride os[] it has in the destination.
-struct PermLin { long long d[4], os[4]; };
-
-__global__ __launch_bounds__(NT) void cc_perm_lin_kernel(long long total, PermLin p, double alpha, const double *__restrict__ in, double beta,
-                                                         double *__restrict__ out) {
-    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
-        long long r = e;
-        const long long i3 = r % p.d[3]; r /= p.d[3];
-        const long long i2 = r % p.d[2]; r /= p.d[2];
-        const long long i1 = r % p.d[1], i0 = r / p.d[1];
-        double *q = out + i0 * p.os[0] + i1 * p.os[1] + i2 * p.os[2] + i3 * p.os[3];
-        const double s = alpha * in[e];
-        *q = beta != 0.0 ? s + beta * *q : s;
-    }
-}
-
-// plane (x: fastest axis of the source, y: fastest axis of the destination), the other two axes r, s are the batch
-struct PermTile { long long dx, dy, dr, ds, isy, isr, iss, osx, osr, oss; };
-
-__global__ __launch_bounds__(NT) void cc_perm_tile_kernel(PermTile p, double alpha, const double *__restrict__ in, double beta,
-                                                          double *__restrict__ out) {
-    __shared__ double tile[32][33];
-    const long long tcx = (p.dx + 31) / 32, tcy = (p.dy + 31) / 32;
-    long long bid = blockIdx.x;
-    const long long x0 = (bid % tcx) * 32; bid /= tcx;
-    const long long y0 = (bid % tcy) * 32; bid /= tcy;
-    const long long s = bid % p.ds, r = bid / p.ds;
-    in += r * p.isr + s * p.iss;
-    out += r * p.osr + s * p.oss;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const long long y = y0 + ty + 8 * k, xx = x0 + tx;
-        if (y < p.dy && xx < p.dx) tile[ty + 8 * k][tx] = in[y * p.isy + xx];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const long long xx = x0 + ty + 8 * k, y = y0 + tx;
-        if (y < p.dy && xx < p.dx) {
-            double *q = out + xx * p.osx + y;
-            const double w = alpha * tile[tx][ty + 8 * k];
-            *q = beta != 0.0 ? w + beta * *q : w;
-        }
-    }
-}
-
-// ---- elementwise ---------------------------------------------------------------------------------------------------------------
-// out[i][j][a][b] = c2 t2[i][j][a][b] + c1 t1[i][a] t1[j][b]
-__global__ __launch_bounds__(NT) void cc_tau_kernel(int o, int v, double c2, double c1, const double *__restrict__ t1,
-                                                    const double *__restrict__ t2, double *__restrict__ out) {
-    const long long vv = (long long)v * v, total = (long long)o * o * vv;
-    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
-        const long long ij = e / vv, ab = e % vv;
-        const int i = (int)(ij / o), j = (int)(ij % o), a = (int)(ab / v), b = (int)(ab % v);
-        out[e] = c2 * t2[e] + c1 * t1[(long long)i * v + a] * t1[(long long)j * v + b];
-    }
-}
-
-// out = in / D: D_ia = e_i - e_a (two == 0, in (o, v)) or D_ijab = e_i + e_j - e_a - e_b (in (o, o, v, v))
-__global__ __launch_bounds__(NT) void cc_div_kernel(int o, int v, int two, const double *__restrict__ in, const double *__restrict__ eo,
-                                                    const double *__restrict__ ev, double *__restrict__ out) {
-    const long long vv = two ? (long long)v * v : v, total = (two ? (long long)o * o : o) * vv;
-    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < total; e += (long long)gridDim.x * NT) {
-        const long long ij = e / vv, ab = e % vv;
-        double d;
-        if (two) d = (eo[ij / o] + eo[ij % o]) - (ev[ab / v] + ev[ab % v]);
-        else d = eo[ij] - ev[ab];
-        out[e] = in[e] / d;
-    }
-}
 
 // out = in - D t with the D of cc_div_kernel: the projected residual R_od - d t, nothing divided (in and out may be the same array)
 __global__ __launch_bounds__(NT) void cc_resid_kernel(int o, int v, int two, const double *in, const double *__restrict__ t,
@@ -249,151 +61,6 @@ __global__ __launch_bounds__(NT) void cc_rdm1_kernel(int o, int v, const double 
         gamma[e] = x;
     }
 }
-
-// the Fock matrix (n x n) cut into f_oo and f_vv without their diagonals, f_ov, and the diagonals
-__global__ __launch_bounds__(NT) void cc_fock_split_kernel(int o, int v, const double *__restrict__ f, double *__restrict__ foo,
-                                                           double *__restrict__ fvv, double *__restrict__ fov, double *__restrict__ eo,
-                                                           double *__restrict__ ev) {
-    const int n = o + v;
-    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < (long long)n * n; e += (long long)gridDim.x * NT) {
-        const int p = (int)(e / n), q = (int)(e % n);
-        const double x = f[e];
-        if (p < o && q < o) { foo[(long long)p * o + q] = p == q ? 0.0 : x; if (p == q) eo[p] = x; }
-        else if (p >= o && q >= o) { fvv[(long long)(p - o) * v + q - o] = p == q ? 0.0 : x; if (p == q) ev[p - o] = x; }
-        else if (p < o) fov[(long long)p * v + q - o] = x;
-    }
-}
-
-// partial[block] = sum x y over a fixed grid; then *out = (acc ? *out : 0) + scale sum partial, one workgroup, fixed order
-__global__ __launch_bounds__(NT) void cc_dot_kernel(long long n, const double *__restrict__ x, const double *__restrict__ y,
-                                                    double *__restrict__ partial) {
-    __shared__ double red[NT];
-    double s = 0.0;
-    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < n; e += (long long)gridDim.x * NT) s = fma(x[e], y[e], s);
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = NT / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(NT) void cc_sum_kernel(int count, const double *__restrict__ partial, double scale, int acc, double *__restrict__ out) {
-    __shared__ double red[NT];
-    double s = 0.0;
-    for (int t = threadIdx.x; t < count; t += NT) s += partial[t];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = NT / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = (acc ? *out : 0.0) + scale * red[0];
-}
-
-// out = sum_q c[q] x_q, x_q = base + q stride
-struct LinComb { int m; double c[DIIS_MAX]; };
-__global__ __launch_bounds__(NT) void cc_lincomb_kernel(long long n, LinComb L, const double *__restrict__ base, long long stride,
-                                                        double *__restrict__ out) {
-    for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < n; e += (long long)gridDim.x * NT) {
-        double s = 0.0;
-        for (int q = 0; q < L.m; ++q) s = fma(L.c[q], base[q * stride + e], s);
-        out[e] = s;
-    }
-}
-
-int grid_of(long long n) { return std::max(1, dmk_grid1d(n, 4096)); }
-
-// ---- the contraction engine ------------------------------------------------------------------------------------------------------
-// Index letters: i j k l occupied, a b c d virtual.  Tensors are row-major in the order of their letters.
-struct Engine {
-    dmk_ctx *ctx = nullptr;
-    int o = 0, v = 0;
-    double *PA = nullptr, *PB = nullptr, *PC = nullptr;      // scratch of `big` doubles each
-
-    long long dim(char c) const { return c >= 'i' ? o : v; }
-    long long count(const std::string &s) const { long long n = 1; for (char c : s) n *= dim(c); return n; }
-
-    // out (order so) = alpha in (order si) + beta out
-    int perm(double alpha, const double *in, const char *si, double beta, double *out, const char *so) const {
-        const int nd = (int)std::strlen(si), off = 4 - nd;
-        if (nd < 1 || nd > 4 || (int)std::strlen(so) != nd) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: permute '%s' -> '%s'", si, so);
-        long long d[4] = {1, 1, 1, 1}, is[4] = {0, 0, 0, 0}, os[4] = {0, 0, 0, 0}, ost[4];
-        for (int k = 0; k < nd; ++k) d[off + k] = dim(si[k]);
-        is[3] = 1;
-        for (int k = 2; k >= 0; --k) is[k] = is[k + 1] * d[k + 1];
-        long long run = 1;
-        for (int q = nd - 1; q >= 0; --q) { ost[q] = run; run *= dim(so[q]); }
-        for (int k = 0; k < nd; ++k) {
-            const char *w = std::strchr(so, si[k]);
-            if (!w) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: permute '%s' -> '%s'", si, so);
-            os[off + k] = ost[w - so];
-        }
-        const long long total = d[0] * d[1] * d[2] * d[3];
-        FamScope fs(ctx, DMK_FAM_MISC);
-        if (os[3] == 1) {
-            PermLin p;
-            for (int k = 0; k < 4; ++k) { p.d[k] = d[k]; p.os[k] = os[k]; }
-            hipLaunchKernelGGL(cc_perm_lin_kernel, dim3(grid_of(total)), dim3(NT), 0, ctx->stream, total, p, alpha, in, beta, out);
-        } else {
-            int y = -1, rs[2], nrs = 0;
-            for (int k = 0; k < 3; ++k) { if (os[k] == 1 && d[k] > 1 && y < 0) y = k; }
-            if (y < 0) for (int k = 0; k < 3; ++k) if (os[k] == 1 && y < 0) y = k;
-            if (y < 0) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: permute '%s' -> '%s' has no unit stride", si, so);
-            for (int k = 0; k < 3; ++k) if (k != y) rs[nrs++] = k;
-            PermTile p{d[3], d[y], d[rs[0]], d[rs[1]], is[y], is[rs[0]], is[rs[1]], os[3], os[rs[0]], os[rs[1]]};
-            const long long blocks = ((p.dx + 31) / 32) * ((p.dy + 31) / 32) * p.dr * p.ds;
-            if (blocks > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: a permute of %lld tiles", blocks);
-            hipLaunchKernelGGL(cc_perm_tile_kernel, dim3((unsigned)blocks), dim3(NT), 0, ctx->stream, p, alpha, in, beta, out);
-        }
-        DMK_CHECK_LAUNCH(ctx);
-        return DMK_OK;
-    }
-
-    // C = alpha op(A) op(B) + beta C with M cut so that no launch exceeds the grid's second dimension
-    int gemm(int opA, int opB, long long M, long long N, long long K, double alpha, const double *A, const double *B, double beta,
-             double *C) const {
-        if (N > 0x7fffffffLL || K > 0x7fffffffLL) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd: a product of %lld x %lld x %lld", M, N, K);
-        const long long lda = opA ? M : K, ldb = opB ? K : N, chunk = 32LL * 65535;
-        for (long long m0 = 0; m0 < M; m0 += chunk) {
-            const int mc = (int)std::min(chunk, M - m0);
-            const int rc = dmk_dgemm_batched(ctx, opA, opB, mc, (int)N, (int)K, 1, alpha, A + (opA ? m0 : m0 * lda), lda, 0, B, ldb, 0, beta,
-                                             C + m0 * N, N, 0);
-            if (rc) return rc;
-        }
-        return DMK_OK;
-    }
-
-    // C[sc] = alpha sum_(letters shared by sa and sb) A[sa] B[sb] + beta C[sc]
-    int contract(double alpha, const double *A, const char *sa, const double *B, const char *sb, double beta, double *C,
-                 const char *sc) const {
-        std::string FA, K, FB;
-        for (const char *p = sa; *p; ++p) (std::strchr(sb, *p) ? K : FA) += *p;
-        for (const char *p = sb; *p; ++p) if (!std::strchr(sa, *p)) FB += *p;
-        int opA = 0, opB = 0, rc;
-        if (FA + K == sa) opA = 0;
-        else if (K + FA == sa) opA = 1;
-        else { if ((rc = perm(1.0, A, sa, 0.0, PA, (FA + K).c_str()))) return rc; A = PA; }
-        if (K + FB == sb) opB = 0;
-        else if (FB + K == sb) opB = 1;
-        else { if ((rc = perm(1.0, B, sb, 0.0, PB, (K + FB).c_str()))) return rc; B = PB; }
-        const long long M = count(FA), N = count(FB), Kd = count(K);
-        const std::string prod = FA + FB;
-        if (prod == sc) return gemm(opA, opB, M, N, Kd, alpha, A, B, beta, C);
-        if ((rc = gemm(opA, opB, M, N, Kd, alpha, A, B, 0.0, PC))) return rc;
-        return perm(1.0, PC, prod.c_str(), beta, C, sc);
-    }
-};
-
-long long pad32(long long k) { return (k + 31) / 32 * 32; }
-long long big_of(long long o, long long v) { return std::max(std::max(o * o * o * o, o * o * o * v), std::max(o * o * v * v, o * v * v * v)); }
-
-struct Carver {
-    char *p;
-    explicit Carver(void *base) : p(static_cast<char *>(base)) {}
-    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += dmk_align256((size_t)std::max<long long>(count, 1) * 8); return q; }
-};
 
 }  // namespace
 
@@ -471,20 +138,14 @@ void plan_bytes(int o, int v, int diis, int64_t *bytes) {
 }
 
 int cc_dot(dmk_rccsd *h, long long n, const double *x, const double *y, double scale, int acc, double *out) {
-    dmk_ctx *ctx = h->ctx;
-    FamScope fs(ctx, DMK_FAM_MISC);
-    const int grid = (int)std::min<long long>(DOT_GRID, (n + NT - 1) / NT);
-    hipLaunchKernelGGL(cc_dot_kernel, dim3(grid), dim3(NT), 0, ctx->stream, n, x, y, h->part);
-    hipLaunchKernelGGL(cc_sum_kernel, dim3(1), dim3(NT), 0, ctx->stream, grid, h->part, scale, acc, out);
-    DMK_CHECK_LAUNCH(ctx);
-    return DMK_OK;
+    return cc_dot(h->ctx, h->part, n, x, y, scale, acc, out);
 }
 
 int cc_tau(dmk_rccsd *h, double c2, double c1, const double *amp, double *out) {
     dmk_ctx *ctx = h->ctx;
     FamScope fs(ctx, DMK_FAM_MISC);
-    hipLaunchKernelGGL(cc_tau_kernel, dim3(grid_of((long long)h->o * h->o * h->v * h->v)), dim3(NT), 0, ctx->stream, h->o, h->v, c2, c1, amp,
-                       amp + h->t2off, out);
+    hipLaunchKernelGGL(cc_tau_kernel, dim3(grid_of((long long)h->o * h->o * h->v * h->v)), dim3(NT), 0, ctx->stream, h->o, h->o, h->v, h->v, c2, c1, amp,
+                       amp, amp + h->t2off, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -493,7 +154,8 @@ int cc_div(dmk_rccsd *h, int two, const double *in, double *out) {
     dmk_ctx *ctx = h->ctx;
     FamScope fs(ctx, DMK_FAM_MISC);
     const long long n = two ? (long long)h->o * h->o * h->v * h->v : (long long)h->o * h->v;
-    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(n)), dim3(NT), 0, ctx->stream, h->o, h->v, two, in, h->eo, h->ev, out);
+    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(n)), dim3(NT), 0, ctx->stream,
+                       Denoms{h->o, h->o, h->v, h->v, h->eo, h->eo, h->ev, h->ev}, two, in, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -551,7 +213,7 @@ int cc_rod(dmk_rccsd *h, const double *src) {
     CT(1.0, ovoo, "lcki", t1, "jc", 1.0, Woooo, "klij"); CT(1.0, ovoo, "kclj", t1, "ic", 1.0, Woooo, "klij");
     CT(1.0, ovov, "kcld", tau, "ijcd", 1.0, Woooo, "klij");
     CT(1.0, Woooo, "klij", tau, "klab", 1.0, R, "ijab");                                  // hole-hole ladder
-    Ladder lad{(long long)h->o * h->o, h->v, h->vvvv, h->ld_vvvv, tau, 1.0, 1.0, R};         // particle-particle ladder
+    Ladder lad{(long long)h->o * h->o, h->v, h->v, h->vvvv, h->ld_vvvv, tau, 1.0, 1.0, R};         // particle-particle ladder
     if ((rc = ladder_launch(h->ctx, lad))) return rc;
     CT(1.0, ovvv, "kcbd", tau, "ijcd", 0.0, Y, "ijkb"); CT(-1.0, t1, "ka", Y, "ijkb", 1.0, S, "ijab");
     CT(1.0, Lvv, "ac", t2, "ijcb", 1.0, S, "ijab");
@@ -641,7 +303,7 @@ int lambda_prepare(dmk_rccsd *h) {
     return DMK_OK;
 }
 
-#define LADDER(in, b, dst) do { if ((rc = ladder_launch(h->ctx, Ladder{(long long)h->o * h->o, h->v, h->vvvv, h->ld_vvvv, in, 1.0, b, dst}))) return rc; } while (0)
+#define LADDER(in, b, dst) do { if ((rc = ladder_launch(h->ctx, Ladder{(long long)h->o * h->o, h->v, h->v, h->vvvv, h->ld_vvvv, in, 1.0, b, dst}))) return rc; } while (0)
 
 // one application of the Lambda equations to the vector `src` = (l1, l2), the new (l1, l2) into `dst`: the weights
 // l~1 = 2 l1, l~2 = 2 l2 - l2^T(ab) go BACKWARDS through cc_rod (every CT(alpha, A, B -> C) gives Ab += alpha Cb . B and
@@ -791,92 +453,6 @@ int lambda_rdm1(dmk_rccsd *h, double *gamma_dev) {
 #undef CT
 #undef PM
 
-// The iteration of dmk_rccsd_run and dmk_rccsd_lambda_run: `update(from, to)` on the vector *x, DIIS over the ring with the steps
-// new - old as error vectors, ONE record read back per iteration.  energy == true: the T iteration (the energy of every new vector,
-// |dE| < tol_e part of the test); false: the test is |dx|_2 < tol_x alone.  e1 / e2: where the step is kept when there is no ring.
-struct Iterate {
-    double **x, **xnew, *ring_x, *ring_e, *e1, *e2;
-    bool energy;
-    const char *who;
-};
-
-template <class Update>
-int cc_iterate(dmk_rccsd *h, const Iterate &s, int max_iter, double tol_e, double tol_x, Update update, double *result) {
-    dmk_ctx *ctx = h->ctx;
-    int rc;
-    const int dim = h->diis;
-    const long long nx = h->nx, rs = h->ring_stride();
-    double B[DIIS_MAX][DIIS_MAX] = {{0.0}}, rec[16], e_old, e = 0.0, dE = 0.0, dt = 0.0;
-    if (s.energy) {
-        if ((rc = cc_energy(h, *s.x, h->rec))) return rc;
-        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        e = rec[0];
-    }
-    int it = 0, converged = 0, stored = 0;
-    while (it < max_iter) {
-        ++it;
-        const int slot = dim ? (stored % dim) : 0;
-        double *dst = dim ? s.ring_x + slot * rs : *s.xnew;
-        // the step new - old: a ring slot (the padding between the two parts is zero in every vector), or e1 / e2, free between updates
-        double *e1 = dim ? s.ring_e + slot * rs : s.e1, *e2 = dim ? e1 + h->t2off : s.e2;
-        if ((rc = update(*s.x, dst))) return rc;
-        if (s.energy && (rc = cc_energy(h, dst, h->rec))) return rc;
-        if ((rc = h->E.perm(1.0, dst, "ia", 0.0, e1, "ia"))) return rc;
-        if ((rc = h->E.perm(-1.0, *s.x, "ia", 1.0, e1, "ia"))) return rc;
-        if ((rc = h->E.perm(1.0, dst + h->t2off, "ijab", 0.0, e2, "ijab"))) return rc;
-        if ((rc = h->E.perm(-1.0, *s.x + h->t2off, "ijab", 1.0, e2, "ijab"))) return rc;
-        const int m = dim ? std::min(stored + 1, dim) : 1;
-        if (dim) {
-            for (int q = 0; q < m; ++q)
-                if ((rc = cc_dot(h, nx, e1, s.ring_e + q * rs, 1.0, 0, h->rec + 1 + q))) return rc;
-        } else {
-            if ((rc = cc_dot(h, (long long)h->o * h->v, e1, e1, 1.0, 0, h->rec + 1))) return rc;
-            if ((rc = cc_dot(h, nx - h->t2off, e2, e2, 1.0, 1, h->rec + 1))) return rc;
-        }
-        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, (size_t)(1 + m) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        e_old = e;
-        e = s.energy ? rec[0] : 0.0;
-        dE = e - e_old;
-        dt = std::sqrt(rec[1 + (dim ? slot : 0)]);
-        if (!std::isfinite(e) || !std::isfinite(dt)) return dmk_fail(ctx, DMK_ERR_NOCONV, "%s: non-finite energy or amplitudes in iteration %d", s.who, it);
-        if (std::fabs(dE) < tol_e && dt < tol_x) converged = 1;
-        if (!dim || converged) {
-            if (dim) DMK_HIP(ctx, hipMemcpyAsync(*s.x, dst, (size_t)nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            else std::swap(*s.x, *s.xnew);
-            if (converged) break;
-            continue;
-        }
-        for (int q = 0; q < m; ++q) B[slot][q] = B[q][slot] = rec[1 + q];
-        ++stored;
-        double Bm[DIIS_MAX * DIIS_MAX];
-        LinComb L{};
-        L.m = m;
-        for (int p = 0; p < m; ++p)
-            for (int q = 0; q < m; ++q) Bm[p * m + q] = B[p][q];
-        if (dmk_diis_coeffs(m, Bm, L.c) != DMK_OK) {          // no usable extrapolation: the newest vector
-            for (int q = 0; q < m; ++q) L.c[q] = q == slot ? 1.0 : 0.0;
-        }
-        {
-            FamScope fs(ctx, DMK_FAM_MISC);
-            hipLaunchKernelGGL(cc_lincomb_kernel, dim3(grid_of(nx)), dim3(NT), 0, ctx->stream, nx, L, s.ring_x, rs, *s.x);
-            DMK_CHECK_LAUNCH(ctx);
-        }
-    }
-    if (s.energy && dim && !converged && it > 0) {
-        // left unconverged with a ring: *x is the extrapolated vector, not the update whose energy `e` is.  The energy reported
-        // is the one of the amplitudes dmk_rccsd_get returns (dE stays the difference the convergence test saw)
-        if ((rc = cc_energy(h, *s.x, h->rec))) return rc;
-        DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        e = rec[0];
-    }
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    result[0] = e; result[1] = converged; result[2] = it; result[3] = dt; result[4] = dE;
-    return DMK_OK;
-}
-
 }  // namespace
 
 // ---- what csrc/ccsd_t.hip (K22) reads of a handle (ccsd_view.h) -------------------------------------------------------------------
@@ -887,7 +463,7 @@ int dmk_rccsd_view(dmk_rccsd *h, RccsdView *out) {
 
 int dmk_cc_perm(dmk_ctx *ctx, int o, int v, double alpha, const double *in, const char *si, double beta, double *out, const char *so) {
     Engine E;
-    E.ctx = ctx; E.o = o; E.v = v;
+    E.ctx = ctx; E.extents(o, v, o, v);
     return E.perm(alpha, in, si, beta, out, so);
 }
 
@@ -899,7 +475,17 @@ int dmk_cc_ladder_s4(dmk_ctx *ctx, int64_t m, int nvir, const double *vvvv_s4, i
     if (m < 1 || nvir < 1 || nvir > 512 || !vvvv_s4 || !tau || !out)
         return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4: bad arguments (m >= 1, 1 <= nvir <= 512; block, tau and out)");
     if (ld < pair_of(nvir)) return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4: row pitch %lld below npair = %lld", (long long)ld, pair_of(nvir));
-    return ladder_launch(ctx, Ladder{(long long)m, nvir, vvvv_s4, (long long)ld, tau, alpha, beta, out});
+    return ladder_launch(ctx, Ladder{(long long)m, nvir, nvir, vvvv_s4, (long long)ld, tau, alpha, beta, out});
+}
+
+int dmk_cc_ladder_s4_ab(dmk_ctx *ctx, int64_t m, int nvir_a, int nvir_b, const double *vvVV_s4, int64_t ld, const double *tau, double alpha,
+                        double beta, double *out) {
+    if (!ctx) return DMK_ERR_INVALID;
+    if (m < 1 || nvir_a < 1 || nvir_a > 512 || nvir_b < 1 || nvir_b > 512 || !vvVV_s4 || !tau || !out)
+        return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4_ab: bad arguments (m >= 1, 1 <= nvir_a, nvir_b <= 512; block, tau and out)");
+    if (ld < pair_of(nvir_b))
+        return dmk_fail(ctx, DMK_ERR_INVALID, "cc_ladder_s4_ab: row pitch %lld below npair_b = %lld", (long long)ld, pair_of(nvir_b));
+    return ladder_launch(ctx, Ladder{(long long)m, nvir_a, nvir_b, vvVV_s4, (long long)ld, tau, alpha, beta, out});
 }
 
 int dmk_rccsd_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host) {
@@ -931,7 +517,7 @@ int dmk_rccsd_create(dmk_ctx *ctx, int nocc, int nvir, const double *fock_mo, co
     }
     h->carve(h->mem.get<void>());
     const size_t third = (size_t)bytes[1] / 3;
-    h->E.ctx = ctx; h->E.o = nocc; h->E.v = nvir;
+    h->E.ctx = ctx; h->E.extents(nocc, nvir, nocc, nvir);
     h->E.PA = h->ws.get<double>();
     h->E.PB = reinterpret_cast<double *>(h->ws.get<char>() + third);
     h->E.PC = reinterpret_cast<double *>(h->ws.get<char>() + 2 * third);
@@ -1011,8 +597,9 @@ int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, do
     if (!h->have_amps && (rc = cc_init(h))) return rc;
     h->kept = false;
     // without a ring the step is kept in n1 / tau2, free between updates
-    const Iterate s{&h->x, &h->xnew, h->ring_x, h->ring_e, h->n1, h->tau2, true, "rccsd_run"};
-    return cc_iterate(h, s, max_iter, tol_e, tol_normt, [h](const double *from, double *to) { return cc_update(h, from, to); }, result_host);
+    const Iterate s{&h->x, &h->xnew, h->ring_x, h->ring_e, 2, {0, h->t2off}, {(long long)h->o * h->v, h->nx - h->t2off}, {h->n1, h->tau2}, true, "rccsd_run"};
+    return cc_iterate(h, s, max_iter, tol_e, tol_normt, [h](const double *from, double *to) { return cc_update(h, from, to); },
+                      [h](const double *amp, double *e_dev) { return cc_energy(h, amp, e_dev); }, result_host);
 }
 
 int dmk_rccsd_lambda_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host) {
@@ -1070,9 +657,11 @@ int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *r
     if (!h->have_l && (rc = dmk_rccsd_lambda_init(h))) return rc;
     if ((rc = lambda_prepare(h))) return rc;
     // without a ring the step is kept in the adjoints of n1 / tau2, free between sweeps
-    const Iterate s{&h->l, &h->lnew, h->lring_x, h->lring_e, h->n1b, h->tau2, false, "rccsd_lambda_run"};
+    const Iterate s{&h->l, &h->lnew, h->lring_x, h->lring_e, 2, {0, h->t2off}, {(long long)h->o * h->v, h->nx - h->t2off}, {h->n1b, h->tau2}, false,
+                    "rccsd_lambda_run"};
     double res[5];
-    if ((rc = cc_iterate(h, s, max_iter, 1.0, tol_normt, [h](const double *from, double *to) { return lambda_update(h, from, to); }, res)))
+    if ((rc = cc_iterate(h, s, max_iter, 1.0, tol_normt, [h](const double *from, double *to) { return lambda_update(h, from, to); },
+                         [](const double *, double *) { return (int)DMK_OK; }, res)))
         return rc;
     result_host[0] = res[1]; result_host[1] = res[2]; result_host[2] = res[3];
     return DMK_OK;

@@ -10,7 +10,7 @@ The seven MO blocks come from dmk_ao2mo_s4 applied to the ERI block the DeviceHF
 the Lambda equations and the densities (and with them CCSD.run / run_dmet_ham, which return a density) -- they are
 solver/cc_lambda.py (RCCSDLambda) and solver/cc_solver.py (CCSolver) --, the perturbative triples (T) -- the energy is
 solver/ccsd_t.py (kernel), reached through RCCSDLambda.ccsd_t and CCSolver.ccsd_t; the run option ccsdt=True also needs the (T) Lambda
-equations and the (T) densities, which are not built --, UCCSD and GCCSD, frozen orbitals, Brueckner and tailored CC, a level shift
+equations and the (T) densities, which are not built --, UCCSD (it is solver/uccsd.py, which run_ccsd dispatches to) and GCCSD, frozen orbitals, Brueckner and tailored CC, a level shift
 other than 0 and a damping other than 1.  The module imports without a GPU.
 """
 import ctypes as C
@@ -222,7 +222,7 @@ CCSD = RCCSD
 
 
 def UCCSD(*args, **kwargs):
-    _not_built("Unrestricted CCSD (UCCSD)")
+    _not_built("Unrestricted CCSD (UCCSD) in this module: it is solver.uccsd.UCCSD, which run_ccsd uses for an unrestricted solver; here it")
 
 
 def GCCSD(*args, **kwargs):
@@ -238,7 +238,8 @@ _UNBUILT_RUN_OPTIONS = {"ccsdt": _T_RUN % "ccsdt", "ccsdt_energy": _T_RUN % "ccs
 
 def run_ccsd(scfsolver, t1=None, t2=None, mo_coeff=None, mo_occ=None, frozen=None, **opts):
     """The T part of the reference's CCSD.run (solver/cc.py:618-1153) over a solver.scf.SCF whose HF() has run: -> (e_corr, t1, t2).
-    The solver's `.cc` holds the RCCSD object afterwards.  Options: conv_tol, conv_tol_normt, max_cycle, diis_space, max_memory
+    The solver's `.cc` holds the RCCSD object afterwards; over an unrestricted solver it is a solver.uccsd.UCCSD and
+    t1 = (t1a, t1b), t2 = (t2aa, t2ab, t2bb).  Options: conv_tol, conv_tol_normt, max_cycle, diis_space, max_memory
     (level_shift and iterative_damping only at their neutral values)."""
     for key, val in opts.items():
         if key in _UNBUILT_RUN_OPTIONS:
@@ -250,10 +251,13 @@ def run_ccsd(scfsolver, t1=None, t2=None, mo_coeff=None, mo_occ=None, frozen=Non
         log.warn("running HF first with default settings")
         scfsolver.HF()
     log.check(scfsolver.mf.converged, "Hartree-Fock calculation has not converged")
-    if not scfsolver.spinRestricted:
-        _not_built("Unrestricted CCSD (UCCSD)")
-    log.result("Restricted CCSD on the device")
-    cc = RCCSD(scfsolver.mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+    if scfsolver.spinRestricted:
+        log.result("Restricted CCSD on the device")
+        cc = RCCSD(scfsolver.mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
+    else:
+        from libdmet_preview_amd.solver.uccsd import UCCSD as DeviceUCCSD
+        log.result("Unrestricted CCSD on the device")
+        cc = DeviceUCCSD(scfsolver.mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
     for key in _RUN_OPTIONS:
         if key in opts:
             setattr(cc, key, opts[key])

@@ -145,6 +145,25 @@ def triples(it):
 worst = max(worst, measure("solver.ccsd_t.kernel: (T) in one batch and in many", triples, rounds=25))
 objq.close()
 
+# UCCSD over an unrestricted device Hartree-Fock on the same orbitals (4 alpha, 4 beta, three different ERI blocks): the transforms with
+# the transposed beta-alpha twins, the dmk_uccsd handle and its workspace, with a ring and without
+Bq = rng.standard_normal((8, npq))
+eri3 = (0.05 / nq) * np.asarray([Aq.T @ Aq, Bq.T @ Bq, Aq.T @ Bq])
+hfu = dscf.SCF(newton_ah=False)
+hfu.set_system(8, 0, False, False)
+hfu.set_integral(nq, 0.0, {"cd": np.asarray([h1q, h1q])}, {"ccdd": eri3})
+hfu.HF(tol=1e-10, MaxIter=100)
+from libdmet_preview_amd.solver import uccsd as duccsd
+
+
+def uccsd_round(it):
+    for diis in (8, 0):
+        obj = duccsd.UCCSD(hfu.mf)
+        obj.diis_space = diis
+        obj.kernel()
+        obj.close()
+worst = max(worst, measure("solver.uccsd.UCCSD: ao2mo, create, run, free", uccsd_round, rounds=25))
+
 # FCI over the same Hamiltonian at 8 orbitals (4, 4): the handle, its slab workspace, Davidson and both densities, one slab and many
 from libdmet_preview_amd.solver import fci as dfci
 gq = np.zeros((8, 8), dtype=np.int64)
