@@ -282,11 +282,6 @@ bool widths_ok(int n, int n1, int n2, int n3, int n4) {
     return n >= 1 && n <= 512 && n1 >= 1 && n1 <= n && n2 >= 1 && n2 <= n && n3 >= 1 && n3 <= n && n4 >= 1 && n4 <= n;
 }
 
-struct StreamDrain {        // declared after the owners of device memory: the stream is drained before they let go
-    hipStream_t s;
-    ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -326,7 +321,7 @@ int dmk_ao2mo_s4(dmk_ctx *ctx, int n, const double *eri, int64_t ld, const doubl
         (void)hipGetLastError();
         return dmk_fail(ctx, DMK_ERR_NOMEM, "ao2mo_s4: no device memory for a workspace of %lld bytes", (long long)p.bytes);
     }
-    StreamDrain drain{ctx->stream};
+    StreamDrain drain{ctx->stream};          // declared after the owners of device memory: the stream is drained before they let go
     char *base = ws.get<char>();
     double *T = reinterpret_cast<double *>(base);
     double *bufA = reinterpret_cast<double *>(base + dmk_align256((size_t)p.t_doubles * 8));

@@ -1,11 +1,13 @@
 // What csrc/ccsd.hip (K21) and csrc/uccsd.hip (K24) share: ONE copy of the particle-particle ladder kernel, the permute kernels, the
-// element-wise helpers, the contraction engine over index letters and the DIIS iteration.  Everything is in an unnamed namespace: each
-// of the two files compiles its own instance.
+// element-wise helpers, the contraction engine over index letters, what a handle is made of (Parts: the layout of an amplitude vector;
+// Ring: a vector with its DIIS ring; Core: what dmk_rccsd and dmk_uccsd derive from, with the moves their entry points share) and the
+// DIIS iteration over them.  Everything is in an unnamed namespace: each of the two files compiles its own instance.
 #pragma once
 #include "devres.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 namespace {
@@ -360,7 +362,6 @@ long long big_pair(long long o, long long v, long long O, long long V) {
 long long big_of(long long o, long long v, long long O, long long V) {
     return std::max(std::max(big_pair(o, v, o, v), big_pair(O, V, O, V)), big_pair(o, v, O, V));
 }
-long long big_of(long long o, long long v) { return big_of(o, v, o, v); }
 
 // *out = (acc ? *out : 0) + scale sum x y; part: 2048 doubles of the caller
 int cc_dot(dmk_ctx *ctx, double *part, long long n, const double *x, const double *y, double scale, int acc, double *out) {
@@ -372,36 +373,153 @@ int cc_dot(dmk_ctx *ctx, double *part, long long n, const double *x, const doubl
     return DMK_OK;
 }
 
-struct Carver {
-    char *p;
-    explicit Carver(void *base) : p(static_cast<char *>(base)) {}
-    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += dmk_align256((size_t)std::max<long long>(count, 1) * 8); return q; }
+// ---- what the handles of ccsd.hip and uccsd.hip are made of ---------------------------------------------------------------------------
+// The layout of an amplitude vector: np parts of cnt[] doubles at off[], every offset a multiple of 32 doubles, nx doubles in all.  The
+// padding behind a part is zero in every vector; the last part is padded as well only where pad_last says so.
+constexpr int PARTS_MAX = 5;
+struct Parts {
+    int np = 0;
+    long long off[PARTS_MAX] = {0}, cnt[PARTS_MAX] = {0}, nx = 0;
+    Parts() = default;
+    Parts(std::initializer_list<long long> counts, bool pad_last) {
+        for (long long c : counts) { off[np] = pad32(nx); cnt[np] = c; nx = off[np++] + c; }
+        if (pad_last) nx = pad32(nx);
+    }
 };
 
-// The iteration of dmk_rccsd_run, dmk_rccsd_lambda_run and dmk_uccsd_run over a handle H (members ctx, diis, nx, rec, part, E and
-// ring_stride()): `update(from, to)` on the vector *x, DIIS over the ring with the steps new - old as error vectors, ONE record read
-// back per iteration.  The vector is np parts at off[] of cnt[] doubles (the padding between them is zero in every vector).
-// energy(vec, e_dev): the T iteration (the energy of every new vector, |dE| < tol_e part of the test); energy_on == false: the test
+// A vector under iteration: the current one, the one an update writes, and the DIIS ring of `diis` vectors and `diis` steps
+struct Ring {
+    double *x = nullptr, *xnew = nullptr, *ring_x = nullptr, *ring_e = nullptr;
+    long long nx = 0;
+    void carve(Carver &c, long long n, int diis) {
+        nx = n;
+        x = c.take(nx); xnew = c.take(nx);
+        ring_x = reinterpret_cast<double *>(c.p);
+        for (int q = 0; q < diis; ++q) c.take(nx);
+        ring_e = reinterpret_cast<double *>(c.p);
+        for (int q = 0; q < diis; ++q) c.take(nx);
+    }
+    long long ring_stride() const { return (long long)(dmk_align256((size_t)nx * 8) / 8); }
+};
+
+// What dmk_rccsd and dmk_uccsd derive from: the layout P of the vector, the T ring, the two allocations (mem: what the handle's
+// carve() lays out; ws: the three scratch thirds of the engine), the reduction scratch and the records (rec[15]: E(MP2) of init).
+struct Core {
+    dmk_ctx *ctx = nullptr;
+    int diis = 0;
+    Parts P;
+    DevMem mem, ws;
+    Engine E;
+    Ring T;
+    double *part = nullptr, *rec = nullptr;
+    bool have_amps = false;
+
+    Core(dmk_ctx *c, int o, int v, int O, int V, int diis_dim) : ctx(c), diis(diis_dim) { E.ctx = c; E.extents(o, v, O, V); }
+    // doubles of a tensor named by o v (alpha) and O V (beta) extents, "oOvV"
+    long long ext(const char *t) const {
+        long long n = 1;
+        for (; *t; ++t) n *= *t == 'o' ? E.o : *t == 'O' ? E.O : *t == 'v' ? E.v : E.V;
+        return n;
+    }
+    struct Slot { double **p; const char *t; };
+    template <size_t N> void take(Carver &c, const Slot (&tab)[N]) { for (const Slot &e : tab) *e.p = c.take(ext(e.t)); }
+    int64_t ws_bytes() const { return 3 * (int64_t)dmk_align256((size_t)big_of(E.o, E.v, E.O, E.V) * 8); }
+
+    // `body`, then the stream is waited for
+    template <class Body> int synced(Body body) {
+        const int rc = body();
+        if (rc) return rc;
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return DMK_OK;
+    }
+    // np device arrays into the parts of the vector `dst`, waited for; *have: there are amplitudes now
+    int set(const double *const *src, double *dst, bool *have) {
+        for (int p = 0; p < P.np; ++p) DMK_HIP(ctx, hipMemcpyAsync(dst + P.off[p], src[p], (size_t)P.cnt[p] * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *have = true;
+        return DMK_OK;
+    }
+    // np device arrays src[] of the parts' sizes out to dst[], not waited for
+    int parts_out(const double *const *src, double *const *dst) {
+        for (int p = 0; p < P.np; ++p) DMK_HIP(ctx, hipMemcpyAsync(dst[p], src[p], (size_t)P.cnt[p] * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        return DMK_OK;
+    }
+    // part p of the vector `vec` (p == np: E(MP2)) out, waited for
+    int get(const double *vec, int p, double *out) {
+        const double *src = p < P.np ? vec + P.off[p] : rec + 15;
+        DMK_HIP(ctx, hipMemcpyAsync(out, src, (size_t)(p < P.np ? P.cnt[p] : 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return DMK_OK;
+    }
+    // one application of `update(from, to)` to the vector of ring r, waited for
+    template <class Update> int step(Ring &r, Update update) {
+        const int rc = update(r.x, r.xnew);
+        if (rc) return rc;
+        std::swap(r.x, r.xnew);
+        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return DMK_OK;
+    }
+};
+
+int cc_dot(Core *h, long long n, const double *x, const double *y, double scale, int acc, double *out) {
+    return cc_dot(h->ctx, h->part, n, x, y, scale, acc, out);
+}
+
+// The common course of dmk_rccsd_create and dmk_uccsd_create over a fresh handle h (extents, layout and integrals set): both
+// allocations, the carve, the scratch thirds, zeros, then `fill` (the Fock split and the arrays made from the integrals).  On failure
+// the handle is deleted, after the stream has been waited for once work may be queued on it.
+template <class H, class Fill> int cc_create(H *h, const char *who, Fill fill, H **out) {
+    dmk_ctx *ctx = h->ctx;
+    const int64_t bytes[2] = {(int64_t)h->carve(nullptr), h->ws_bytes()};
+    if (h->mem.alloc(ctx, (size_t)bytes[0]) != hipSuccess || h->ws.alloc(ctx, (size_t)bytes[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        delete h;
+        return dmk_fail(ctx, DMK_ERR_NOMEM, "%s: no device memory for %lld + %lld bytes", who, (long long)bytes[0], (long long)bytes[1]);
+    }
+    h->carve(h->mem.template get<void>());
+    const size_t third = (size_t)bytes[1] / 3;
+    h->E.PA = h->ws.template get<double>();
+    h->E.PB = reinterpret_cast<double *>(h->ws.template get<char>() + third);
+    h->E.PC = reinterpret_cast<double *>(h->ws.template get<char>() + 2 * third);
+    auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); delete h; return code; };
+    if (hipMemsetAsync(h->mem.template get<void>(), 0, (size_t)bytes[0], ctx->stream) != hipSuccess)
+        return fail(dmk_fail(ctx, DMK_ERR_HIP, "%s: memset failed", who));
+    const int rc = fill();
+    if (rc) return fail(rc);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "%s: the stream failed", who));
+    *out = h;
+    return DMK_OK;
+}
+
+template <class H> int cc_free(H *h) {
+    if (!h) return DMK_OK;
+    (void)hipStreamSynchronize(h->ctx->stream);      // work that reads the handle's memory may still be queued
+    delete h;
+    return DMK_OK;
+}
+
+// The iteration of dmk_rccsd_run, dmk_rccsd_lambda_run and dmk_uccsd_run over a handle: `update(from, to)` on the vector of `ring`,
+// DIIS over the ring with the steps new - old as error vectors, ONE record read back per iteration.
+// energy(vec, e_dev): the T iteration (the energy of every new vector, |dE| < tol_e part of the test); energy == false: the test
 // is |dx|_2 < tol_x alone.  step[]: where the step of each part is kept when there is no ring.
-constexpr int PARTS_MAX = 5;
 struct Iterate {
-    double **x, **xnew, *ring_x, *ring_e;
-    int np;
-    long long off[PARTS_MAX], cnt[PARTS_MAX];
+    Ring *ring;
     double *step[PARTS_MAX];
     bool energy;
     const char *who;
 };
 
-template <class H, class Update, class Energy>
-int cc_iterate(H *h, const Iterate &s, int max_iter, double tol_e, double tol_x, Update update, Energy energy, double *result) {
+template <class Update, class Energy>
+int cc_iterate(Core *h, const Iterate &s, int max_iter, double tol_e, double tol_x, Update update, Energy energy, double *result) {
     dmk_ctx *ctx = h->ctx;
+    Ring &r = *s.ring;
+    const Parts &P = h->P;
     int rc;
     const int dim = h->diis;
-    const long long nx = h->nx, rs = h->ring_stride();
+    const long long nx = P.nx, rs = r.ring_stride();
     double B[DIIS_MAX][DIIS_MAX] = {{0.0}}, rec[16], e_old, e = 0.0, dE = 0.0, dt = 0.0;
     if (s.energy) {
-        if ((rc = energy(*s.x, h->rec))) return rc;
+        if ((rc = energy(r.x, h->rec))) return rc;
         DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
         DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         e = rec[0];
@@ -410,23 +528,23 @@ int cc_iterate(H *h, const Iterate &s, int max_iter, double tol_e, double tol_x,
     while (it < max_iter) {
         ++it;
         const int slot = dim ? (stored % dim) : 0;
-        double *dst = dim ? s.ring_x + slot * rs : *s.xnew;
-        double *ering = dim ? s.ring_e + slot * rs : nullptr;
-        if ((rc = update(*s.x, dst))) return rc;
+        double *dst = dim ? r.ring_x + slot * rs : r.xnew;
+        double *ering = dim ? r.ring_e + slot * rs : nullptr;
+        if ((rc = update(r.x, dst))) return rc;
         if (s.energy && (rc = energy(dst, h->rec))) return rc;
         // the step new - old: a ring slot, or step[], free between updates
-        for (int p = 0; p < s.np; ++p) {
-            double *ep = dim ? ering + s.off[p] : s.step[p];
-            if ((rc = h->E.axpby(s.cnt[p], 1.0, dst + s.off[p], 0.0, ep))) return rc;
-            if ((rc = h->E.axpby(s.cnt[p], -1.0, *s.x + s.off[p], 1.0, ep))) return rc;
+        for (int p = 0; p < P.np; ++p) {
+            double *ep = dim ? ering + P.off[p] : s.step[p];
+            if ((rc = h->E.axpby(P.cnt[p], 1.0, dst + P.off[p], 0.0, ep))) return rc;
+            if ((rc = h->E.axpby(P.cnt[p], -1.0, r.x + P.off[p], 1.0, ep))) return rc;
         }
         const int m = dim ? std::min(stored + 1, dim) : 1;
         if (dim) {
             for (int q = 0; q < m; ++q)
-                if ((rc = cc_dot(ctx, h->part, nx, ering, s.ring_e + q * rs, 1.0, 0, h->rec + 1 + q))) return rc;
+                if ((rc = cc_dot(h, nx, ering, r.ring_e + q * rs, 1.0, 0, h->rec + 1 + q))) return rc;
         } else {
-            for (int p = 0; p < s.np; ++p)
-                if ((rc = cc_dot(ctx, h->part, s.cnt[p], s.step[p], s.step[p], 1.0, p > 0, h->rec + 1))) return rc;
+            for (int p = 0; p < P.np; ++p)
+                if ((rc = cc_dot(h, P.cnt[p], s.step[p], s.step[p], 1.0, p > 0, h->rec + 1))) return rc;
         }
         DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, (size_t)(1 + m) * 8, hipMemcpyDeviceToHost, ctx->stream));
         DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -437,8 +555,8 @@ int cc_iterate(H *h, const Iterate &s, int max_iter, double tol_e, double tol_x,
         if (!std::isfinite(e) || !std::isfinite(dt)) return dmk_fail(ctx, DMK_ERR_NOCONV, "%s: non-finite energy or amplitudes in iteration %d", s.who, it);
         if (std::fabs(dE) < tol_e && dt < tol_x) converged = 1;
         if (!dim || converged) {
-            if (dim) DMK_HIP(ctx, hipMemcpyAsync(*s.x, dst, (size_t)nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            else std::swap(*s.x, *s.xnew);
+            if (dim) DMK_HIP(ctx, hipMemcpyAsync(r.x, dst, (size_t)nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            else std::swap(r.x, r.xnew);
             if (converged) break;
             continue;
         }
@@ -454,14 +572,14 @@ int cc_iterate(H *h, const Iterate &s, int max_iter, double tol_e, double tol_x,
         }
         {
             FamScope fs(ctx, DMK_FAM_MISC);
-            hipLaunchKernelGGL(cc_lincomb_kernel, dim3(grid_of(nx)), dim3(NT), 0, ctx->stream, nx, L, s.ring_x, rs, *s.x);
+            hipLaunchKernelGGL(cc_lincomb_kernel, dim3(grid_of(nx)), dim3(NT), 0, ctx->stream, nx, L, r.ring_x, rs, r.x);
             DMK_CHECK_LAUNCH(ctx);
         }
     }
     if (s.energy && dim && !converged && it > 0) {
         // left unconverged with a ring: *x is the extrapolated vector, not the update whose energy `e` is.  The energy reported
         // is the one of the amplitudes dmk_rccsd_get returns (dE stays the difference the convergence test saw)
-        if ((rc = energy(*s.x, h->rec))) return rc;
+        if ((rc = energy(r.x, h->rec))) return rc;
         DMK_HIP(ctx, hipMemcpyAsync(rec, h->rec, 8, hipMemcpyDeviceToHost, ctx->stream));
         DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         e = rec[0];

@@ -20,11 +20,14 @@
 // Contract           every other term: a two-operand contraction named by its index letters is  permute (only where the operand is
 //                    not already [free, summed] or [summed, free])  ->  dmk_dgemm_batched  ->  permute-accumulate (only where the
 //                    product's index order differs from the destination's).  No host loops over elements, no host round trips.
-// dmk_rccsd          the handle: amplitudes, intermediates, DIIS ring (one allocation) and the contraction workspace (another).
+// dmk_rccsd          the handle, a Core of cc_engine.h: the (t1 | t2) vector with its DIIS ring and the intermediates (one allocation)
+//                    and the contraction workspace (another).  The layout (Parts) and the ring (Ring) are the types the Lambda
+//                    iteration and uccsd.hip use as well.
 // Lambda             ("Lambda") the Lambda equations as the REVERSE SWEEP of the amplitude equations (lambda_update: the
 //                    adjoint of every line of cc_rod in the reverse order, the (vv|vv) term being cc_ladder_kernel itself on the adjoint
 //                    of R), the one-particle density (cc_rdm1_kernel assembles it), the residual without a division (cc_resid_kernel)
-//                    and the Lagrangian E_corr + <l~, r> of a probe handle; their state is a third allocation, made on first use.
+//                    and the Lagrangian E_corr + <l~, r> of a probe handle; their state (a second Ring and the kept intermediates) is a
+//                    third allocation, made on first use.
 #include "devres.h"
 #include "ccsd_view.h"
 #include "cc_engine.h"
@@ -64,88 +67,61 @@ __global__ __launch_bounds__(NT) void cc_rdm1_kernel(int o, int v, const double 
 
 }  // namespace
 
-struct dmk_rccsd {
-    dmk_ctx *ctx = nullptr;
-    int o = 0, v = 0, diis = 0;
-    long long nx = 0, t2off = 0;
+struct dmk_rccsd : Core {
+    int o, v;
     const double *oooo = nullptr, *ovoo = nullptr, *ovov = nullptr, *oovv = nullptr, *ovvo = nullptr, *ovvv = nullptr, *vvvv = nullptr;
     long long ld_vvvv = 0;
-    DevMem mem, ws;
-    Engine E;
-    double *x = nullptr, *xnew = nullptr, *ring_x = nullptr, *ring_e = nullptr;
     double *Lovov, *Lt, *tau, *tau2, *R, *S, *Wvoov, *Wvovo, *Woooo, *Y, *Q;
-    double *foo, *Foo, *Loo, *X1, *X2, *fvv, *Fvv, *Lvv, *fov, *Fov, *n1, *eo, *ev, *part, *rec;
-    bool have_amps = false;
+    double *foo, *Foo, *Loo, *X1, *X2, *fvv, *Fvv, *Lvv, *fov, *Fov, *n1, *eo, *ev;
 
+    // the vector: t1 | t2, t1 padded with zeros to a multiple of 32 doubles, t2 not
+    dmk_rccsd(dmk_ctx *c, int nocc, int nvir, int diis_dim) : Core(c, nocc, nvir, nocc, nvir, diis_dim), o(nocc), v(nvir) {
+        P = Parts({ext("ov"), ext("oovv")}, false);
+    }
     // what the carve lays out; with a null base: the bytes
     size_t carve(void *base) {
         Carver c(base);
-        const long long oo = (long long)o * o, vv = (long long)v * v, ov = (long long)o * v, t2n = oo * vv;
-        x = c.take(nx); xnew = c.take(nx);
-        ring_x = reinterpret_cast<double *>(c.p);
-        for (int q = 0; q < diis; ++q) c.take(nx);
-        ring_e = reinterpret_cast<double *>(c.p);
-        for (int q = 0; q < diis; ++q) c.take(nx);
-        Lovov = c.take(t2n); Lt = c.take(t2n); tau = c.take(t2n); tau2 = c.take(t2n); R = c.take(t2n); S = c.take(t2n);
-        Wvoov = c.take(t2n); Wvovo = c.take(t2n);
-        Woooo = c.take(oo * oo); Y = c.take(oo * ov); Q = c.take(oo * ov);
-        foo = c.take(oo); Foo = c.take(oo); Loo = c.take(oo); X1 = c.take(oo); X2 = c.take(oo);
-        fvv = c.take(vv); Fvv = c.take(vv); Lvv = c.take(vv);
-        fov = c.take(ov); Fov = c.take(ov); n1 = c.take(ov);
-        eo = c.take(o); ev = c.take(v);
+        T.carve(c, P.nx, diis);
+        const Slot tab[] = {
+            {&Lovov, "oovv"}, {&Lt, "oovv"}, {&tau, "oovv"}, {&tau2, "oovv"}, {&R, "oovv"}, {&S, "oovv"}, {&Wvoov, "oovv"}, {&Wvovo, "oovv"},
+            {&Woooo, "oooo"}, {&Y, "ooov"}, {&Q, "ooov"}, {&foo, "oo"}, {&Foo, "oo"}, {&Loo, "oo"}, {&X1, "oo"}, {&X2, "oo"},
+            {&fvv, "vv"}, {&Fvv, "vv"}, {&Lvv, "vv"}, {&fov, "ov"}, {&Fov, "ov"}, {&n1, "ov"}, {&eo, "o"}, {&ev, "v"}};
+        take(c, tab);
         part = c.take(2048); rec = c.take(16);
         return (size_t)(c.p - static_cast<char *>(base));
     }
-    long long ring_stride() const { return (long long)(dmk_align256((size_t)nx * 8) / 8); }
 
     // ---- Lambda ("Lambda"): a second allocation, made by the first Lambda call ------------------------------------
-    // l / lnew and the ring as x / xnew above; k*: the T-only intermediates of cc_rod at the current t, kept across sweeps; *b: the
+    // L: the vector (l1 | l2) and its ring, as T; k*: the T-only intermediates of cc_rod at the current t, kept across sweeps; *b: the
     // adjoints that have no home in the first allocation (those of R, S, tau, tau2, Wvoov, Wvovo, Woooo live in the buffers of those
     // names, which hold nothing between two applications of cc_rod); g1 the t1 gradient of the energy; d* / xt*: density pieces.
     DevMem lmem;
-    double *l = nullptr, *lnew = nullptr, *lring_x = nullptr, *lring_e = nullptr;
+    Ring L;
     double *ktau, *ktau2, *kWvoov, *kWvovo, *kWoooo, *kFov, *kFoo, *kFvv, *kLoo, *kLvv, *kX1, *kX2;
     double *t2b, *Qb, *Yb, *t1b, *n1b, *Fovb, *Foob, *Loob, *X1b, *X2b, *Fvvb, *Lvvb, *g1;
     double *doo, *dvv, *dvo, *xt1, *xt2;
-    bool have_l = false, kept = false;          // kept: the k* arrays belong to the amplitudes in x
+    bool have_l = false, kept = false;          // kept: the k* arrays belong to the amplitudes in T.x
 
     size_t lambda_carve(void *base) {
         Carver c(base);
-        const long long oo = (long long)o * o, vv = (long long)v * v, ov = (long long)o * v, t2n = oo * vv;
-        l = c.take(nx); lnew = c.take(nx);
-        lring_x = reinterpret_cast<double *>(c.p);
-        for (int q = 0; q < diis; ++q) c.take(nx);
-        lring_e = reinterpret_cast<double *>(c.p);
-        for (int q = 0; q < diis; ++q) c.take(nx);
-        ktau = c.take(t2n); ktau2 = c.take(t2n); kWvoov = c.take(t2n); kWvovo = c.take(t2n); t2b = c.take(t2n);
-        kWoooo = c.take(oo * oo); Qb = c.take(oo * ov); Yb = c.take(oo * ov);
-        kFoo = c.take(oo); kLoo = c.take(oo); kX1 = c.take(oo); kX2 = c.take(oo);
-        Foob = c.take(oo); Loob = c.take(oo); X1b = c.take(oo); X2b = c.take(oo); doo = c.take(oo); xt1 = c.take(oo);
-        kFvv = c.take(vv); kLvv = c.take(vv); Fvvb = c.take(vv); Lvvb = c.take(vv); dvv = c.take(vv); xt2 = c.take(vv);
-        kFov = c.take(ov); Fovb = c.take(ov); t1b = c.take(ov); n1b = c.take(ov); g1 = c.take(ov); dvo = c.take(ov);
+        L.carve(c, P.nx, diis);
+        const Slot tab[] = {
+            {&ktau, "oovv"}, {&ktau2, "oovv"}, {&kWvoov, "oovv"}, {&kWvovo, "oovv"}, {&t2b, "oovv"}, {&kWoooo, "oooo"}, {&Qb, "ooov"}, {&Yb, "ooov"},
+            {&kFoo, "oo"}, {&kLoo, "oo"}, {&kX1, "oo"}, {&kX2, "oo"}, {&Foob, "oo"}, {&Loob, "oo"}, {&X1b, "oo"}, {&X2b, "oo"}, {&doo, "oo"}, {&xt1, "oo"},
+            {&kFvv, "vv"}, {&kLvv, "vv"}, {&Fvvb, "vv"}, {&Lvvb, "vv"}, {&dvv, "vv"}, {&xt2, "vv"},
+            {&kFov, "ov"}, {&Fovb, "ov"}, {&t1b, "ov"}, {&n1b, "ov"}, {&g1, "ov"}, {&dvo, "ov"}};
+        take(c, tab);
         return (size_t)(c.p - static_cast<char *>(base));
     }
 };
 
 namespace {
 
-void plan_bytes(int o, int v, int diis, int64_t *bytes) {
-    dmk_rccsd h;
-    h.o = o; h.v = v; h.diis = diis;
-    h.nx = pad32((long long)o * v) + (long long)o * o * v * v;
-    bytes[0] = (int64_t)h.carve(nullptr);
-    bytes[1] = 3 * (int64_t)dmk_align256((size_t)big_of(o, v) * 8);
-}
-
-int cc_dot(dmk_rccsd *h, long long n, const double *x, const double *y, double scale, int acc, double *out) {
-    return cc_dot(h->ctx, h->part, n, x, y, scale, acc, out);
-}
-
 int cc_tau(dmk_rccsd *h, double c2, double c1, const double *amp, double *out) {
     dmk_ctx *ctx = h->ctx;
     FamScope fs(ctx, DMK_FAM_MISC);
-    hipLaunchKernelGGL(cc_tau_kernel, dim3(grid_of((long long)h->o * h->o * h->v * h->v)), dim3(NT), 0, ctx->stream, h->o, h->o, h->v, h->v, c2, c1, amp,
-                       amp, amp + h->t2off, out);
+    hipLaunchKernelGGL(cc_tau_kernel, dim3(grid_of(h->P.cnt[1])), dim3(NT), 0, ctx->stream, h->o, h->o, h->v, h->v, c2, c1, amp,
+                       amp, amp + h->P.off[1], out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -153,8 +129,7 @@ int cc_tau(dmk_rccsd *h, double c2, double c1, const double *amp, double *out) {
 int cc_div(dmk_rccsd *h, int two, const double *in, double *out) {
     dmk_ctx *ctx = h->ctx;
     FamScope fs(ctx, DMK_FAM_MISC);
-    const long long n = two ? (long long)h->o * h->o * h->v * h->v : (long long)h->o * h->v;
-    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(n)), dim3(NT), 0, ctx->stream,
+    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(h->P.cnt[two])), dim3(NT), 0, ctx->stream,
                        Denoms{h->o, h->o, h->v, h->v, h->eo, h->eo, h->ev, h->ev}, two, in, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
@@ -164,8 +139,8 @@ int cc_div(dmk_rccsd *h, int two, const double *in, double *out) {
 int cc_energy(dmk_rccsd *h, const double *amp, double *e_dev) {
     int rc;
     if ((rc = cc_tau(h, 1.0, 1.0, amp, h->tau))) return rc;
-    if ((rc = cc_dot(h, (long long)h->o * h->v, h->fov, amp, 2.0, 0, e_dev))) return rc;
-    return cc_dot(h, (long long)h->o * h->o * h->v * h->v, h->Lt, h->tau, 1.0, 1, e_dev);
+    if ((rc = cc_dot(h, h->P.cnt[0], h->fov, amp, 2.0, 0, e_dev))) return rc;
+    return cc_dot(h, h->P.cnt[1], h->Lt, h->tau, 1.0, 1, e_dev);
 }
 
 #define CT(alpha, A, sa, B, sb, beta, C, sc) do { if ((rc = E.contract(alpha, A, sa, B, sb, beta, C, sc))) return rc; } while (0)
@@ -175,7 +150,7 @@ int cc_energy(dmk_rccsd *h, const double *amp, double *e_dev) {
 // of t2 into h->R.  Every intermediate named in the handle is left as the equations define it at `src`.
 int cc_rod(dmk_rccsd *h, const double *src) {
     const Engine &E = h->E;
-    const double *t1 = src, *t2 = src + h->t2off;
+    const double *t1 = src, *t2 = src + h->P.off[1];
     const double *oooo = h->oooo, *ovoo = h->ovoo, *ovov = h->ovov, *oovv = h->oovv, *ovvo = h->ovvo, *ovvv = h->ovvv;
     double *tau = h->tau, *tau2 = h->tau2, *R = h->R, *S = h->S, *Wvoov = h->Wvoov, *Wvovo = h->Wvovo, *Woooo = h->Woooo, *Y = h->Y, *Q = h->Q;
     double *Foo = h->Foo, *Loo = h->Loo, *X1 = h->X1, *X2 = h->X2, *Fvv = h->Fvv, *Lvv = h->Lvv, *Fov = h->Fov, *n1 = h->n1;
@@ -237,17 +212,17 @@ int cc_update(dmk_rccsd *h, const double *src, double *dst) {
     int rc;
     if ((rc = cc_rod(h, src))) return rc;
     if ((rc = cc_div(h, 0, h->n1, dst))) return rc;
-    return cc_div(h, 1, h->R, dst + h->t2off);
+    return cc_div(h, 1, h->R, dst + h->P.off[1]);
 }
 
 int cc_init(dmk_rccsd *h) {
     const Engine &E = h->E;
     int rc;
-    if ((rc = cc_div(h, 0, h->fov, h->x))) return rc;
+    if ((rc = cc_div(h, 0, h->fov, h->T.x))) return rc;
     PM(1.0, h->ovov, "iajb", 0.0, h->R, "ijab");
-    if ((rc = cc_div(h, 1, h->R, h->x + h->t2off))) return rc;
+    if ((rc = cc_div(h, 1, h->R, h->T.x + h->P.off[1]))) return rc;
     // E(MP2) = sum (2 (ia|jb) - (ib|ja)) t_ij^ab: the doubles alone, as PySCF's init_amps reports it
-    if ((rc = cc_dot(h, h->nx - h->t2off, h->Lt, h->x + h->t2off, 1.0, 0, h->rec + 15))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[1], h->Lt, h->T.x + h->P.off[1], 1.0, 0, h->rec + 15))) return rc;
     h->have_amps = true;
     return DMK_OK;
 }
@@ -256,8 +231,7 @@ int cc_init(dmk_rccsd *h) {
 int cc_resid(dmk_rccsd *h, int two, const double *in, const double *t, double *out) {
     dmk_ctx *ctx = h->ctx;
     FamScope fs(ctx, DMK_FAM_MISC);
-    const long long n = two ? (long long)h->o * h->o * h->v * h->v : (long long)h->o * h->v;
-    hipLaunchKernelGGL(cc_resid_kernel, dim3(grid_of(n)), dim3(NT), 0, ctx->stream, h->o, h->v, two, in, t, h->eo, h->ev, out);
+    hipLaunchKernelGGL(cc_resid_kernel, dim3(grid_of(h->P.cnt[two])), dim3(NT), 0, ctx->stream, h->o, h->v, two, in, t, h->eo, h->ev, out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -265,9 +239,9 @@ int cc_resid(dmk_rccsd *h, int two, const double *in, const double *t, double *o
 // r1 = R_od - d t1 into h->n1, r2 into h->R, of the current amplitudes
 int cc_residual(dmk_rccsd *h) {
     int rc;
-    if ((rc = cc_rod(h, h->x))) return rc;
-    if ((rc = cc_resid(h, 0, h->n1, h->x, h->n1))) return rc;
-    return cc_resid(h, 1, h->R, h->x + h->t2off, h->R);
+    if ((rc = cc_rod(h, h->T.x))) return rc;
+    if ((rc = cc_resid(h, 0, h->n1, h->T.x, h->n1))) return rc;
+    return cc_resid(h, 1, h->R, h->T.x + h->P.off[1], h->R);
 }
 
 int lambda_alloc(dmk_rccsd *h) {
@@ -290,7 +264,7 @@ int lambda_prepare(dmk_rccsd *h) {
     dmk_ctx *ctx = h->ctx;
     const Engine &E = h->E;
     int rc;
-    if ((rc = cc_rod(h, h->x))) return rc;
+    if ((rc = cc_rod(h, h->T.x))) return rc;
     const long long oo = (long long)h->o * h->o, vv = (long long)h->v * h->v, ov = (long long)h->o * h->v, t2n = oo * vv;
     const struct { double *dst; const double *src; long long n; } keep[] = {
         {h->ktau, h->tau, t2n}, {h->ktau2, h->tau2, t2n}, {h->kWvoov, h->Wvoov, t2n}, {h->kWvovo, h->Wvovo, t2n}, {h->kWoooo, h->Woooo, oo * oo},
@@ -298,7 +272,7 @@ int lambda_prepare(dmk_rccsd *h) {
         {h->kX1, h->X1, oo}, {h->kX2, h->X2, oo}};
     for (const auto &k : keep) DMK_HIP(ctx, hipMemcpyAsync(k.dst, k.src, (size_t)k.n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     PM(2.0, h->fov, "ia", 0.0, h->g1, "ia");
-    CT(2.0, h->Lovov, "iajb", h->x, "jb", 1.0, h->g1, "ia");
+    CT(2.0, h->Lovov, "iajb", h->T.x, "jb", 1.0, h->g1, "ia");
     h->kept = true;
     return DMK_OK;
 }
@@ -308,10 +282,10 @@ int lambda_prepare(dmk_rccsd *h) {
 // one application of the Lambda equations to the vector `src` = (l1, l2), the new (l1, l2) into `dst`: the weights
 // l~1 = 2 l1, l~2 = 2 l2 - l2^T(ab) go BACKWARDS through cc_rod (every CT(alpha, A, B -> C) gives Ab += alpha Cb . B and
 // Bb += alpha Cb . A for the operands that depend on t, in the reverse order; a buffer's adjoint starts with beta = 0 where it is
-// first written), then l~ = (z + g) / d and l from l~.  lambda_prepare must have run for the amplitudes in h->x.
+// first written), then l~ = (z + g) / d and l from l~.  lambda_prepare must have run for the amplitudes in h->T.x.
 int lambda_update(dmk_rccsd *h, const double *src, double *dst) {
     const Engine &E = h->E;
-    const double *t1 = h->x, *t2 = h->x + h->t2off, *l1 = src, *l2 = src + h->t2off;
+    const double *t1 = h->T.x, *t2 = h->T.x + h->P.off[1], *l1 = src, *l2 = src + h->P.off[1];
     const double *ovoo = h->ovoo, *ovov = h->ovov, *oovv = h->oovv, *ovvo = h->ovvo, *ovvv = h->ovvv;
     const double *fov = h->fov, *Lovov = h->Lovov;
     const double *ktau = h->ktau, *kWvoov = h->kWvoov, *kWvovo = h->kWvovo, *kWoooo = h->kWoooo, *kFov = h->kFov, *kFoo = h->kFoo,
@@ -418,14 +392,14 @@ int lambda_update(dmk_rccsd *h, const double *src, double *dst) {
     PM(0.5, t1b, "ia", 0.0, n1b, "ia");
     PM(0.5, h->g1, "ia", 1.0, n1b, "ia");
     if ((rc = cc_div(h, 0, n1b, dst))) return rc;
-    return cc_div(h, 1, Rb, dst + h->t2off);
+    return cc_div(h, 1, Rb, dst + h->P.off[1]);
 }
 
 // gamma (n x n) of the current (t, l) into gamma_dev: DESIGN.md K21, "Lambda"
 int lambda_rdm1(dmk_rccsd *h, double *gamma_dev) {
     dmk_ctx *ctx = h->ctx;
     const Engine &E = h->E;
-    const double *t1 = h->x, *t2 = h->x + h->t2off, *l1 = h->l, *l2 = h->l + h->t2off;
+    const double *t1 = h->T.x, *t2 = h->T.x + h->P.off[1], *l1 = h->L.x, *l2 = h->L.x + h->P.off[1];
     double *th = h->S, *doo = h->doo, *dvv = h->dvv, *dvo = h->dvo, *xt1 = h->xt1, *xt2 = h->xt2, *X = h->X1b;
     int rc;
     PM(2.0, t2, "ijab", 0.0, th, "ijab");
@@ -457,7 +431,7 @@ int lambda_rdm1(dmk_rccsd *h, double *gamma_dev) {
 
 // ---- what csrc/ccsd_t.hip (K22) reads of a handle (ccsd_view.h) -------------------------------------------------------------------
 int dmk_rccsd_view(dmk_rccsd *h, RccsdView *out) {
-    *out = RccsdView{h->ctx, h->o, h->v, h->have_amps, h->ovoo, h->ovov, h->ovvv, h->fov, h->eo, h->ev, h->x, h->x + h->t2off};
+    *out = RccsdView{h->ctx, h->o, h->v, h->have_amps, h->ovoo, h->ovov, h->ovvv, h->fov, h->eo, h->ev, h->T.x, h->T.x + h->P.off[1]};
     return DMK_OK;
 }
 
@@ -490,7 +464,9 @@ int dmk_cc_ladder_s4_ab(dmk_ctx *ctx, int64_t m, int nvir_a, int nvir_b, const d
 
 int dmk_rccsd_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host) {
     if (!bytes_host || nocc < 1 || nvir < 1 || nvir > 512 || nocc > 512 || diis_dim < 0 || diis_dim > DIIS_MAX) return DMK_ERR_INVALID;
-    plan_bytes(nocc, nvir, diis_dim, bytes_host);
+    dmk_rccsd h(nullptr, nocc, nvir, diis_dim);
+    bytes_host[0] = (int64_t)h.carve(nullptr);
+    bytes_host[1] = h.ws_bytes();
     return DMK_OK;
 }
 
@@ -503,90 +479,51 @@ int dmk_rccsd_create(dmk_ctx *ctx, int nocc, int nvir, const double *fock_mo, co
     if (diis_dim < 0 || diis_dim > DIIS_MAX) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_create: diis_dim %d outside [0, %d]", diis_dim, DIIS_MAX);
     if (ld_vvvv < pair_of(nvir)) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_create: pitch of the (vv|vv) block below npair");
     *out = nullptr;
-    dmk_rccsd *h = new dmk_rccsd;
-    h->ctx = ctx; h->o = nocc; h->v = nvir; h->diis = diis_dim;
-    h->t2off = pad32((long long)nocc * nvir);
-    h->nx = h->t2off + (long long)nocc * nocc * nvir * nvir;
+    dmk_rccsd *h = new dmk_rccsd(ctx, nocc, nvir, diis_dim);
     h->oooo = oooo; h->ovoo = ovoo; h->ovov = ovov; h->oovv = oovv; h->ovvo = ovvo; h->ovvv = ovvv; h->vvvv = vvvv_s4; h->ld_vvvv = ld_vvvv;
-    int64_t bytes[2];
-    plan_bytes(nocc, nvir, diis_dim, bytes);
-    if (h->mem.alloc(ctx, (size_t)bytes[0]) != hipSuccess || h->ws.alloc(ctx, (size_t)bytes[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        delete h;
-        return dmk_fail(ctx, DMK_ERR_NOMEM, "rccsd_create: no device memory for %lld + %lld bytes", (long long)bytes[0], (long long)bytes[1]);
-    }
-    h->carve(h->mem.get<void>());
-    const size_t third = (size_t)bytes[1] / 3;
-    h->E.ctx = ctx; h->E.extents(nocc, nvir, nocc, nvir);
-    h->E.PA = h->ws.get<double>();
-    h->E.PB = reinterpret_cast<double *>(h->ws.get<char>() + third);
-    h->E.PC = reinterpret_cast<double *>(h->ws.get<char>() + 2 * third);
-    int rc = DMK_OK;
-    auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); delete h; return code; };
-    if (hipMemsetAsync(h->mem.get<void>(), 0, (size_t)bytes[0], ctx->stream) != hipSuccess)
-        return fail(dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: memset failed"));
-    {
-        FamScope fs(ctx, DMK_FAM_MISC);
-        const int n = nocc + nvir;
-        hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)n * n)), dim3(NT), 0, ctx->stream, nocc, nvir, fock_mo, h->foo, h->fvv,
-                           h->fov, h->eo, h->ev);
-        if (hipGetLastError() != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: kernel launch failed"));
-    }
-    // L_kcld = 2 (kc|ld) - (kd|lc), and the same in (k, l, c, d) order for the energy
-    if ((rc = h->E.perm(2.0, ovov, "kcld", 0.0, h->Lovov, "kcld"))) return fail(rc);
-    if ((rc = h->E.perm(-1.0, ovov, "kdlc", 1.0, h->Lovov, "kcld"))) return fail(rc);
-    if ((rc = h->E.perm(1.0, h->Lovov, "iajb", 0.0, h->Lt, "ijab"))) return fail(rc);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: the stream failed"));
-    *out = h;
-    return DMK_OK;
+    return cc_create(h, "rccsd_create", [&]() -> int {
+        {
+            FamScope fs(ctx, DMK_FAM_MISC);
+            const int n = nocc + nvir;
+            hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)n * n)), dim3(NT), 0, ctx->stream, nocc, nvir, fock_mo, h->foo, h->fvv,
+                               h->fov, h->eo, h->ev);
+            if (hipGetLastError() != hipSuccess) return dmk_fail(ctx, DMK_ERR_HIP, "rccsd_create: kernel launch failed");
+        }
+        // L_kcld = 2 (kc|ld) - (kd|lc), and the same in (k, l, c, d) order for the energy
+        int rc;
+        if ((rc = h->E.perm(2.0, ovov, "kcld", 0.0, h->Lovov, "kcld"))) return rc;
+        if ((rc = h->E.perm(-1.0, ovov, "kdlc", 1.0, h->Lovov, "kcld"))) return rc;
+        return h->E.perm(1.0, h->Lovov, "iajb", 0.0, h->Lt, "ijab");
+    }, out);
 }
 
-int dmk_rccsd_free(dmk_rccsd *h) {
-    if (!h) return DMK_OK;
-    (void)hipStreamSynchronize(h->ctx->stream);      // work that reads the handle's memory may still be queued
-    delete h;
-    return DMK_OK;
-}
+int dmk_rccsd_free(dmk_rccsd *h) { return cc_free(h); }
 
 int dmk_rccsd_init(dmk_rccsd *h) {
     if (!h) return DMK_ERR_INVALID;
     h->kept = false;
-    const int rc = cc_init(h);
-    if (rc) return rc;
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->synced([h] { return cc_init(h); });
 }
 
 int dmk_rccsd_set(dmk_rccsd *h, const double *t1, const double *t2) {
     if (!h) return DMK_ERR_INVALID;
     if (!t1 || !t2) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_set: NULL amplitudes");
-    dmk_ctx *ctx = h->ctx;
     h->kept = false;
-    DMK_HIP(ctx, hipMemcpyAsync(h->x, t1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipMemcpyAsync(h->x + h->t2off, t2, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    h->have_amps = true;
-    return DMK_OK;
+    const double *src[2] = {t1, t2};
+    return h->set(src, h->T.x, &h->have_amps);
 }
 
 int dmk_rccsd_energy(dmk_rccsd *h, double *e_dev) {
     if (!h) return DMK_ERR_INVALID;
     if (!e_dev || !h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_energy: no amplitudes yet (init or set first), or a NULL result");
-    const int rc = cc_energy(h, h->x, e_dev);
-    if (rc) return rc;
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->synced([=] { return cc_energy(h, h->T.x, e_dev); });
 }
 
 int dmk_rccsd_update(dmk_rccsd *h) {
     if (!h) return DMK_ERR_INVALID;
     if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_update: no amplitudes yet (init or set first)");
     h->kept = false;
-    const int rc = cc_update(h, h->x, h->xnew);
-    if (rc) return rc;
-    std::swap(h->x, h->xnew);
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->step(h->T, [h](const double *from, double *to) { return cc_update(h, from, to); });
 }
 
 int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, double *result_host) {
@@ -597,16 +534,14 @@ int dmk_rccsd_run(dmk_rccsd *h, int max_iter, double tol_e, double tol_normt, do
     if (!h->have_amps && (rc = cc_init(h))) return rc;
     h->kept = false;
     // without a ring the step is kept in n1 / tau2, free between updates
-    const Iterate s{&h->x, &h->xnew, h->ring_x, h->ring_e, 2, {0, h->t2off}, {(long long)h->o * h->v, h->nx - h->t2off}, {h->n1, h->tau2}, true, "rccsd_run"};
+    const Iterate s{&h->T, {h->n1, h->tau2}, true, "rccsd_run"};
     return cc_iterate(h, s, max_iter, tol_e, tol_normt, [h](const double *from, double *to) { return cc_update(h, from, to); },
                       [h](const double *amp, double *e_dev) { return cc_energy(h, amp, e_dev); }, result_host);
 }
 
 int dmk_rccsd_lambda_plan(int nocc, int nvir, int diis_dim, int64_t *bytes_host) {
     if (!bytes_host || nocc < 1 || nvir < 1 || nvir > 512 || nocc > 512 || diis_dim < 0 || diis_dim > DIIS_MAX) return DMK_ERR_INVALID;
-    dmk_rccsd h;
-    h.o = nocc; h.v = nvir; h.diis = diis_dim;
-    h.nx = pad32((long long)nocc * nvir) + (long long)nocc * nocc * nvir * nvir;
+    dmk_rccsd h(nullptr, nocc, nvir, diis_dim);
     bytes_host[0] = (int64_t)h.lambda_carve(nullptr);
     return DMK_OK;
 }
@@ -617,7 +552,7 @@ int dmk_rccsd_lambda_init(dmk_rccsd *h) {
     if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_lambda_init: no amplitudes yet (run, init or set first)");
     int rc;
     if ((rc = lambda_alloc(h))) return rc;
-    DMK_HIP(ctx, hipMemcpyAsync(h->l, h->x, (size_t)h->nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    DMK_HIP(ctx, hipMemcpyAsync(h->L.x, h->T.x, (size_t)h->P.nx * 8, hipMemcpyDeviceToDevice, ctx->stream));
     DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     h->have_l = true;
     return DMK_OK;
@@ -625,15 +560,11 @@ int dmk_rccsd_lambda_init(dmk_rccsd *h) {
 
 int dmk_rccsd_lambda_set(dmk_rccsd *h, const double *l1, const double *l2) {
     if (!h) return DMK_ERR_INVALID;
-    dmk_ctx *ctx = h->ctx;
-    if (!l1 || !l2) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_lambda_set: NULL amplitudes");
+    if (!l1 || !l2) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_lambda_set: NULL amplitudes");
     int rc;
     if ((rc = lambda_alloc(h))) return rc;
-    DMK_HIP(ctx, hipMemcpyAsync(h->l, l1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipMemcpyAsync(h->l + h->t2off, l2, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    h->have_l = true;
-    return DMK_OK;
+    const double *src[2] = {l1, l2};
+    return h->set(src, h->L.x, &h->have_l);
 }
 
 int dmk_rccsd_lambda_update(dmk_rccsd *h) {
@@ -642,10 +573,7 @@ int dmk_rccsd_lambda_update(dmk_rccsd *h) {
         return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_lambda_update: needs amplitudes and Lambda amplitudes (lambda_init or lambda_set first)");
     int rc;
     if ((rc = lambda_prepare(h))) return rc;
-    if ((rc = lambda_update(h, h->l, h->lnew))) return rc;
-    std::swap(h->l, h->lnew);
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->step(h->L, [h](const double *from, double *to) { return lambda_update(h, from, to); });
 }
 
 int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *result_host) {
@@ -657,8 +585,7 @@ int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *r
     if (!h->have_l && (rc = dmk_rccsd_lambda_init(h))) return rc;
     if ((rc = lambda_prepare(h))) return rc;
     // without a ring the step is kept in the adjoints of n1 / tau2, free between sweeps
-    const Iterate s{&h->l, &h->lnew, h->lring_x, h->lring_e, 2, {0, h->t2off}, {(long long)h->o * h->v, h->nx - h->t2off}, {h->n1b, h->tau2}, false,
-                    "rccsd_lambda_run"};
+    const Iterate s{&h->L, {h->n1b, h->tau2}, false, "rccsd_lambda_run"};
     double res[5];
     if ((rc = cc_iterate(h, s, max_iter, 1.0, tol_normt, [h](const double *from, double *to) { return lambda_update(h, from, to); },
                          [](const double *, double *) { return (int)DMK_OK; }, res)))
@@ -669,43 +596,38 @@ int dmk_rccsd_lambda_run(dmk_rccsd *h, int max_iter, double tol_normt, double *r
 
 int dmk_rccsd_rdm1(dmk_rccsd *h, double *gamma_dev) {
     if (!h) return DMK_ERR_INVALID;
-    dmk_ctx *ctx = h->ctx;
-    if (!gamma_dev) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_rdm1: NULL result");
-    if (!h->have_amps || !h->have_l) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_rdm1: needs amplitudes and Lambda amplitudes");
-    const int rc = lambda_rdm1(h, gamma_dev);
-    if (rc) return rc;
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DMK_OK;
+    if (!gamma_dev) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_rdm1: NULL result");
+    if (!h->have_amps || !h->have_l) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_rdm1: needs amplitudes and Lambda amplitudes");
+    return h->synced([=] { return lambda_rdm1(h, gamma_dev); });
 }
 
 int dmk_rccsd_residual(dmk_rccsd *h, double *r1_dev, double *r2_dev) {
     if (!h) return DMK_ERR_INVALID;
-    dmk_ctx *ctx = h->ctx;
-    if (!r1_dev || !r2_dev) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_residual: NULL result");
-    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_residual: no amplitudes yet (init or set first)");
-    const int rc = cc_residual(h);
-    if (rc) return rc;
-    DMK_HIP(ctx, hipMemcpyAsync(r1_dev, h->n1, (size_t)h->o * h->v * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipMemcpyAsync(r2_dev, h->R, (size_t)(h->nx - h->t2off) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DMK_OK;
+    if (!r1_dev || !r2_dev) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_residual: NULL result");
+    if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_residual: no amplitudes yet (init or set first)");
+    return h->synced([=]() -> int {
+        const int rc = cc_residual(h);
+        if (rc) return rc;
+        const double *src[2] = {h->n1, h->R};
+        double *dst[2] = {r1_dev, r2_dev};
+        return h->parts_out(src, dst);
+    });
 }
 
 int dmk_rccsd_lagrangian(dmk_rccsd *h, const double *l1, const double *l2, double *out_dev) {
     if (!h) return DMK_ERR_INVALID;
-    dmk_ctx *ctx = h->ctx;
-    if (!l1 || !l2 || !out_dev) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_lagrangian: NULL argument");
-    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_lagrangian: no amplitudes yet (init or set first)");
-    int rc;
-    if ((rc = cc_residual(h))) return rc;
-    // l~2 = 2 l2 - l2^T(ab) into S, free after cc_rod; the energy overwrites tau alone
-    if ((rc = h->E.perm(2.0, l2, "ijab", 0.0, h->S, "ijab"))) return rc;
-    if ((rc = h->E.perm(-1.0, l2, "ijba", 1.0, h->S, "ijab"))) return rc;
-    if ((rc = cc_energy(h, h->x, out_dev))) return rc;
-    if ((rc = cc_dot(h, (long long)h->o * h->v, l1, h->n1, 2.0, 1, out_dev))) return rc;
-    if ((rc = cc_dot(h, h->nx - h->t2off, h->S, h->R, 1.0, 1, out_dev))) return rc;
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DMK_OK;
+    if (!l1 || !l2 || !out_dev) return dmk_fail(h->ctx, DMK_ERR_INVALID, "rccsd_lagrangian: NULL argument");
+    if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "rccsd_lagrangian: no amplitudes yet (init or set first)");
+    return h->synced([=]() -> int {
+        int rc;
+        if ((rc = cc_residual(h))) return rc;
+        // l~2 = 2 l2 - l2^T(ab) into S, free after cc_rod; the energy overwrites tau alone
+        if ((rc = h->E.perm(2.0, l2, "ijab", 0.0, h->S, "ijab"))) return rc;
+        if ((rc = h->E.perm(-1.0, l2, "ijba", 1.0, h->S, "ijab"))) return rc;
+        if ((rc = cc_energy(h, h->T.x, out_dev))) return rc;
+        if ((rc = cc_dot(h, h->P.cnt[0], l1, h->n1, 2.0, 1, out_dev))) return rc;
+        return cc_dot(h, h->P.cnt[1], h->S, h->R, 1.0, 1, out_dev);
+    });
 }
 
 int dmk_rccsd_get(dmk_rccsd *h, int what, double *out) {
@@ -714,18 +636,10 @@ int dmk_rccsd_get(dmk_rccsd *h, int what, double *out) {
     if (!out || what < DMK_RCCSD_T1 || what > DMK_RCCSD_L2) return dmk_fail(ctx, DMK_ERR_INVALID, "rccsd_get: bad arguments");
     if (what == DMK_RCCSD_L1 || what == DMK_RCCSD_L2) {
         if (!h->have_l) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_get: no Lambda amplitudes yet (lambda_init, lambda_set or lambda_run first)");
-        const double *ls = what == DMK_RCCSD_L1 ? h->l : h->l + h->t2off;
-        const size_t lc = what == DMK_RCCSD_L1 ? (size_t)h->o * h->v : (size_t)(h->nx - h->t2off);
-        DMK_HIP(ctx, hipMemcpyAsync(out, ls, lc * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return DMK_OK;
+        return h->get(h->L.x, what - DMK_RCCSD_L1, out);
     }
     if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "rccsd_get: no amplitudes yet (init or set first)");
-    const double *src = what == DMK_RCCSD_T1 ? h->x : what == DMK_RCCSD_T2 ? h->x + h->t2off : h->rec + 15;
-    const size_t cnt = what == DMK_RCCSD_T1 ? (size_t)h->o * h->v : what == DMK_RCCSD_T2 ? (size_t)(h->nx - h->t2off) : 1;
-    DMK_HIP(ctx, hipMemcpyAsync(out, src, cnt * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DMK_OK;
+    return h->get(h->T.x, what, out);          // DMK_RCCSD_T1, _T2, _EMP2 = 0, 1, 2: the parts, then E(MP2)
 }
 
 }  // extern "C"

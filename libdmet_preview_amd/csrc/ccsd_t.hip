@@ -223,11 +223,6 @@ long long w_blocks_per_triple(int o) {
     return tiles * tiles * o;
 }
 
-struct DrainOnExit {          // the scoped workspace must not go while launches that use it are queued
-    dmk_ctx *ctx;
-    ~DrainOnExit() { (void)hipStreamSynchronize(ctx->stream); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -264,7 +259,7 @@ int dmk_rccsd_t(dmk_rccsd *h, int64_t max_bytes, double *result_host) {
         (void)hipGetLastError();
         return dmk_fail(ctx, DMK_ERR_NOMEM, "rccsd_t: no device memory for %lld bytes", (long long)(plan[0] + T * plan[1]));
     }
-    DrainOnExit drain{ctx};
+    StreamDrain drain{ctx->stream};          // the scoped workspace must not go while launches that use it are queued
     char *p = ws.get<char>();
     double *t2T = reinterpret_cast<double *>(p);        p += dmk_align256((size_t)o * o * v * v * 8);
     double *part = reinterpret_cast<double *>(p);       p += dmk_align256((size_t)ntr * 8);

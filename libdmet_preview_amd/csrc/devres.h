@@ -1,8 +1,10 @@
 // Scoped owners of device resources (host code only): a device allocation, a stream, an event, and the double-buffered host feed
 // built from them.  Move-only, no policy beyond "released when it goes out of scope".  DESTRUCTORS DO NOT SYNCHRONISE: whoever
-// lets an owner go while work that uses it may still be in flight synchronises the stream first, at the call site.
+// lets an owner go while work that uses it may still be in flight synchronises the stream first, at the call site -- or declares a
+// StreamDrain after the owners.  Carver cuts one allocation into arrays.
 #pragma once
 #include "common.h"
+#include <algorithm>
 #include <utility>
 
 class DevMem {
@@ -29,6 +31,20 @@ public:
     template <class T> T *get() const { return static_cast<T *>(p_); }
     size_t bytes() const { return n_; }
     explicit operator bool() const { return p_ != nullptr; }
+};
+
+// carves 256-byte aligned arrays of doubles out of one allocation (first pass over a null base: the size)
+struct Carver {
+    char *p;
+    explicit Carver(void *base) : p(static_cast<char *>(base)) {}
+    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += dmk_align256((size_t)std::max<long long>(count, 1) * 8); return q; }
+};
+
+// drains a stream when it goes out of scope.  Declared AFTER the owners of the device memory that the queued work uses: destructors
+// run in reverse order, so the stream is drained before they let go
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
 };
 
 // a stream or an event: what DevStream and DevEvent share

@@ -89,12 +89,6 @@ __global__ void mp2_density_kernel(int d, double diag, double c1, int sym1, cons
     }
 }
 
-
-struct StreamDrain {
-    hipStream_t s;
-    ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
-
 // amplitudes t (o1, o2, v1, v2), t' likewise.  The three density products, each as o slabs of K with partials P[slab][d][d]:
 //   OO1  P[j][i][i'] = sum_ab  t[i][j][a][b] t'[i'][j][a][b]            (o2 slabs, d = o1)
 //   OO2  P[i][j][j'] = sum_ab  t[i][j][a][b] t'[i][j'][a][b]            (o1 slabs, d = o2)
@@ -125,13 +119,6 @@ int amp_launch(dmk_ctx *ctx, int o1, int o2, int v1, int v2, const double *V, co
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
-
-// carves 256-byte aligned arrays of doubles out of one allocation (first pass over a null base: the size)
-struct Carver {
-    char *p;
-    explicit Carver(void *base) : p(static_cast<char *>(base)) {}
-    double *take(long long count) { double *q = reinterpret_cast<double *>(p); p += dmk_align256((size_t)std::max<long long>(count, 1) * 8); return q; }
-};
 
 }  // namespace
 

@@ -6,45 +6,31 @@
 // Everything that computes is in cc_engine.h, shared with ccsd.hip (K21): the three O(o^2 v^4) terms are cc_ladder_kernel on the packed
 // (vv|vv), (VV|VV) and (vv|VV) blocks -- the only reader of those blocks --, every other term is a CT / PM line over the contraction
 // engine, whose upper-case letters run over the beta extents.  The iteration is cc_iterate.  Amplitudes: ONE vector of five parts
-// t1a | t1b | t2aa | t2ab | t2bb, each padded with zeros to a multiple of 32 doubles; t2aa and t2bb are stored in full.
+// t1a | t1b | t2aa | t2ab | t2bb, each padded with zeros to a multiple of 32 doubles; t2aa and t2bb are stored in full.  The handle is
+// a Core of cc_engine.h, its layout and ring the Parts and Ring that ccsd.hip's T and Lambda iterations use.
 #include "devres.h"
 #include "cc_engine.h"
 
-struct dmk_uccsd {
-    dmk_ctx *ctx = nullptr;
-    int oa = 0, va = 0, ob = 0, vb = 0, diis = 0;
-    long long nx = 0, off[5] = {0, 0, 0, 0, 0}, cnt[5] = {0, 0, 0, 0, 0};
+struct dmk_uccsd : Core {
+    int oa, va, ob, vb;
     dmk_uccsd_ints I{};
-    DevMem mem, ws;
-    Engine E;
-    double *x = nullptr, *xnew = nullptr, *ring_x = nullptr, *ring_e = nullptr;
     // the intermediates of uc_rod, by the names DESIGN.md K24 gives them
     double *X2aa, *X2ab, *X2bb, *tauaa, *tauab, *taubb, *tataa, *tatab, *tatbb, *Fvva, *Fvvb, *Fooa, *Foob, *Fova, *Fovb, *Wooaa,
            *Wooab, *Woobb, *W_aaaa, *W_abab, *W_abba, *W_baab, *W_baba, *W_bbbb, *n1a, *n1b, *Gvva, *Gvvb, *Gooa, *Goob, *Q_aaaa,
            *Q_abab, *Q_abba, *Q_baab, *Q_baba, *Q_bbbb, *Y_aaaa, *Y_abab, *Y_baab, *Y_bbbb, *Raa, *Rab, *Rbb;
-    // Fock pieces (off-diagonal f_oo / f_vv, f_ov, the diagonals), <ij||ab> as the energy reads it, reduction scratch, records
-    double *fooa, *foob, *fvva, *fvvb, *fova, *fovb, *eoa, *eob, *eva, *evb, *Gaa, *Gab, *Gbb, *part, *rec;
-    bool have_amps = false;
+    // Fock pieces (off-diagonal f_oo / f_vv, f_ov, the diagonals), <ij||ab> as the energy reads it
+    double *fooa, *foob, *fvva, *fvvb, *fova, *fovb, *eoa, *eob, *eva, *evb, *Gaa, *Gab, *Gbb;
 
-    long long ext(const char *t) const {
-        long long n = 1;
-        for (; *t; ++t) n *= *t == 'o' ? oa : *t == 'O' ? ob : *t == 'v' ? va : vb;
-        return n;
-    }
-    void layout() {
-        const char *parts[5] = {"ov", "OV", "oovv", "oOvV", "OOVV"};
-        nx = 0;
-        for (int p = 0; p < 5; ++p) { off[p] = nx; cnt[p] = ext(parts[p]); nx += pad32(cnt[p]); }
+    // the vector: t1a | t1b | t2aa | t2ab | t2bb, every part padded with zeros to a multiple of 32 doubles
+    dmk_uccsd(dmk_ctx *c, int nocc_a, int nvir_a, int nocc_b, int nvir_b, int diis_dim)
+        : Core(c, nocc_a, nvir_a, nocc_b, nvir_b, diis_dim), oa(nocc_a), va(nvir_a), ob(nocc_b), vb(nvir_b) {
+        P = Parts({ext("ov"), ext("OV"), ext("oovv"), ext("oOvV"), ext("OOVV")}, true);
     }
     // what the carve lays out; with a null base: the bytes
     size_t carve(void *base) {
         Carver c(base);
-        x = c.take(nx); xnew = c.take(nx);
-        ring_x = reinterpret_cast<double *>(c.p);
-        for (int q = 0; q < diis; ++q) c.take(nx);
-        ring_e = reinterpret_cast<double *>(c.p);
-        for (int q = 0; q < diis; ++q) c.take(nx);
-        const struct { double **p; const char *t; } tab[] = {
+        T.carve(c, P.nx, diis);
+        const Slot tab[] = {
             {&X2aa, "oovv"}, {&X2ab, "oOvV"}, {&X2bb, "OOVV"}, {&tauaa, "oovv"}, {&tauab, "oOvV"}, {&taubb, "OOVV"},
             {&tataa, "oovv"}, {&tatab, "oOvV"}, {&tatbb, "OOVV"}, {&Fvva, "vv"}, {&Fvvb, "VV"}, {&Fooa, "oo"},
             {&Foob, "OO"}, {&Fova, "ov"}, {&Fovb, "OV"}, {&Wooaa, "oooo"}, {&Wooab, "oOoO"}, {&Woobb, "OOOO"},
@@ -55,11 +41,10 @@ struct dmk_uccsd {
             {&Rab, "oOvV"}, {&Rbb, "OOVV"},
             {&fooa, "oo"}, {&foob, "OO"}, {&fvva, "vv"}, {&fvvb, "VV"}, {&fova, "ov"}, {&fovb, "OV"},
             {&eoa, "o"}, {&eob, "O"}, {&eva, "v"}, {&evb, "V"}, {&Gaa, "oovv"}, {&Gab, "oOvV"}, {&Gbb, "OOVV"}};
-        for (const auto &e : tab) *e.p = c.take(ext(e.t));
+        take(c, tab);
         part = c.take(2048); rec = c.take(16);
         return (size_t)(c.p - static_cast<char *>(base));
     }
-    long long ring_stride() const { return (long long)(dmk_align256((size_t)nx * 8) / 8); }
 };
 
 namespace {
@@ -70,25 +55,13 @@ bool extents_ok(int oa, int va, int ob, int vb) {
     return true;
 }
 
-void plan_bytes(int oa, int va, int ob, int vb, int diis, int64_t *bytes) {
-    dmk_uccsd h;
-    h.oa = oa; h.va = va; h.ob = ob; h.vb = vb; h.diis = diis;
-    h.layout();
-    bytes[0] = (int64_t)h.carve(nullptr);
-    bytes[1] = 3 * (int64_t)dmk_align256((size_t)big_of(oa, va, ob, vb) * 8);
-}
-
-int uc_dot(dmk_uccsd *h, long long n, const double *x, const double *y, double scale, int acc, double *out) {
-    return cc_dot(h->ctx, h->part, n, x, y, scale, acc, out);
-}
-
 // out[i][j][a][b] = c2 t2[i][j][a][b] + c1 t1[i][a] t1'[j][b] of the vector `src`; si, sj: the spins (0 alpha, 1 beta) of (i, a), (j, b)
 int uc_tau(dmk_uccsd *h, double c2, double c1, int si, int sj, const double *src, double *out) {
     dmk_ctx *ctx = h->ctx;
     FamScope fs(ctx, DMK_FAM_MISC);
     const int oi = si ? h->ob : h->oa, vi = si ? h->vb : h->va, oj = sj ? h->ob : h->oa, vj = sj ? h->vb : h->va;
     hipLaunchKernelGGL(cc_tau_kernel, dim3(grid_of((long long)oi * oj * vi * vj)), dim3(NT), 0, ctx->stream, oi, oj, vi, vj, c2, c1,
-                       src + h->off[si], src + h->off[sj], src + h->off[2 + si + sj], out);
+                       src + h->P.off[si], src + h->P.off[sj], src + h->P.off[2 + si + sj], out);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -100,7 +73,7 @@ int uc_div(dmk_uccsd *h, int p, const double *in, double *dst) {
     const Denoms A{h->oa, h->oa, h->va, h->va, h->eoa, h->eoa, h->eva, h->eva}, B{h->ob, h->ob, h->vb, h->vb, h->eob, h->eob, h->evb, h->evb},
         AB{h->oa, h->ob, h->va, h->vb, h->eoa, h->eob, h->eva, h->evb};
     const Denoms &D = (p == 0 || p == 2) ? A : (p == 1 || p == 4) ? B : AB;
-    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(h->cnt[p])), dim3(NT), 0, ctx->stream, D, p >= 2, in, dst + h->off[p]);
+    hipLaunchKernelGGL(cc_div_kernel, dim3(grid_of(h->P.cnt[p])), dim3(NT), 0, ctx->stream, D, p >= 2, in, dst + h->P.off[p]);
     DMK_CHECK_LAUNCH(ctx);
     return DMK_OK;
 }
@@ -128,11 +101,11 @@ int uc_tau_of(dmk_uccsd *h, const double *src) {
 int uc_energy(dmk_uccsd *h, const double *amp, double *e_dev) {
     int rc;
     if ((rc = uc_tau_of(h, amp))) return rc;
-    if ((rc = uc_dot(h, h->cnt[0], h->fova, amp + h->off[0], 1.0, 0, e_dev))) return rc;
-    if ((rc = uc_dot(h, h->cnt[1], h->fovb, amp + h->off[1], 1.0, 1, e_dev))) return rc;
-    if ((rc = uc_dot(h, h->cnt[2], h->Gaa, h->tauaa, 0.25, 1, e_dev))) return rc;
-    if ((rc = uc_dot(h, h->cnt[3], h->Gab, h->tauab, 1.0, 1, e_dev))) return rc;
-    return uc_dot(h, h->cnt[4], h->Gbb, h->taubb, 0.25, 1, e_dev);
+    if ((rc = cc_dot(h, h->P.cnt[0], h->fova, amp + h->P.off[0], 1.0, 0, e_dev))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[1], h->fovb, amp + h->P.off[1], 1.0, 1, e_dev))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[2], h->Gaa, h->tauaa, 0.25, 1, e_dev))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[3], h->Gab, h->tauab, 1.0, 1, e_dev))) return rc;
+    return cc_dot(h, h->P.cnt[4], h->Gbb, h->taubb, 0.25, 1, e_dev);
 }
 
 // the right-hand sides of the amplitude equations (line by line) at the vector `src`, before the division: of t1 into
@@ -141,7 +114,7 @@ int uc_rod(dmk_uccsd *h, const double *src) {
     const Engine &E = h->E;
     const dmk_uccsd_ints &I = h->I;
     const int oa = h->oa, ob = h->ob, va = h->va, vb = h->vb;
-    const double *t1a = src + h->off[0], *t1b = src + h->off[1], *t2aa = src + h->off[2], *t2ab = src + h->off[3], *t2bb = src + h->off[4];
+    const double *t1a = src + h->P.off[0], *t1b = src + h->P.off[1], *t2aa = src + h->P.off[2], *t2ab = src + h->P.off[3], *t2bb = src + h->P.off[4];
     const double *oooo = I.oooo, *ovoo = I.ovoo, *ovov = I.ovov, *oovv = I.oovv, *ovvv = I.ovvv;
     const double *OOOO = I.OOOO, *OVOO = I.OVOO, *OVOV = I.OVOV, *OOVV = I.OOVV, *OVVV = I.OVVV;
     const double *ooOO = I.ooOO, *ovOO = I.ovOO, *ovOV = I.ovOV, *ooVV = I.ooVV, *ovVV = I.ovVV, *OVoo = I.OVoo, *OOvv = I.OOvv, *OVvv = I.OVvv;
@@ -433,11 +406,11 @@ int uc_init(dmk_uccsd *h) {
     int rc;
     const double *rhs[5] = {h->fova, h->fovb, h->Gaa, h->Gab, h->Gbb};
     for (int p = 0; p < 5; ++p)
-        if ((rc = uc_div(h, p, rhs[p], h->x))) return rc;
+        if ((rc = uc_div(h, p, rhs[p], h->T.x))) return rc;
     // E(MP2): the doubles alone, as PySCF's init_amps reports it
-    if ((rc = uc_dot(h, h->cnt[2], h->Gaa, h->x + h->off[2], 0.25, 0, h->rec + 15))) return rc;
-    if ((rc = uc_dot(h, h->cnt[3], h->Gab, h->x + h->off[3], 1.0, 1, h->rec + 15))) return rc;
-    if ((rc = uc_dot(h, h->cnt[4], h->Gbb, h->x + h->off[4], 0.25, 1, h->rec + 15))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[2], h->Gaa, h->T.x + h->P.off[2], 0.25, 0, h->rec + 15))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[3], h->Gab, h->T.x + h->P.off[3], 1.0, 1, h->rec + 15))) return rc;
+    if ((rc = cc_dot(h, h->P.cnt[4], h->Gbb, h->T.x + h->P.off[4], 0.25, 1, h->rec + 15))) return rc;
     h->have_amps = true;
     return DMK_OK;
 }
@@ -457,7 +430,9 @@ int dmk_transpose_f64(dmk_ctx *ctx, int64_t rows, int64_t cols, const double *in
 
 int dmk_uccsd_plan(int nocc_a, int nvir_a, int nocc_b, int nvir_b, int diis_dim, int64_t *bytes_host) {
     if (!bytes_host || !extents_ok(nocc_a, nvir_a, nocc_b, nvir_b) || diis_dim < 0 || diis_dim > DIIS_MAX) return DMK_ERR_INVALID;
-    plan_bytes(nocc_a, nvir_a, nocc_b, nvir_b, diis_dim, bytes_host);
+    dmk_uccsd h(nullptr, nocc_a, nvir_a, nocc_b, nvir_b, diis_dim);
+    bytes_host[0] = (int64_t)h.carve(nullptr);
+    bytes_host[1] = h.ws_bytes();
     return DMK_OK;
 }
 
@@ -473,92 +448,53 @@ int dmk_uccsd_create(dmk_ctx *ctx, int nocc_a, int nvir_a, int nocc_b, int nvir_
     if (I.ld_vvvv < pair_of(nvir_a) || I.ld_VVVV < pair_of(nvir_b) || I.ld_vvVV < pair_of(nvir_b))
         return dmk_fail(ctx, DMK_ERR_INVALID, "uccsd_create: pitch of a packed block below npair of its columns");
     *out = nullptr;
-    dmk_uccsd *h = new dmk_uccsd;
-    h->ctx = ctx; h->oa = nocc_a; h->va = nvir_a; h->ob = nocc_b; h->vb = nvir_b; h->diis = diis_dim;
+    dmk_uccsd *h = new dmk_uccsd(ctx, nocc_a, nvir_a, nocc_b, nvir_b, diis_dim);
     h->I = I;
-    h->layout();
-    int64_t bytes[2];
-    plan_bytes(nocc_a, nvir_a, nocc_b, nvir_b, diis_dim, bytes);
-    if (h->mem.alloc(ctx, (size_t)bytes[0]) != hipSuccess || h->ws.alloc(ctx, (size_t)bytes[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        delete h;
-        return dmk_fail(ctx, DMK_ERR_NOMEM, "uccsd_create: no device memory for %lld + %lld bytes", (long long)bytes[0], (long long)bytes[1]);
-    }
-    h->carve(h->mem.get<void>());
-    const size_t third = (size_t)bytes[1] / 3;
-    h->E.ctx = ctx; h->E.extents(nocc_a, nvir_a, nocc_b, nvir_b);
-    h->E.PA = h->ws.get<double>();
-    h->E.PB = reinterpret_cast<double *>(h->ws.get<char>() + third);
-    h->E.PC = reinterpret_cast<double *>(h->ws.get<char>() + 2 * third);
-    int rc = DMK_OK;
-    auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); delete h; return code; };
-    if (hipMemsetAsync(h->mem.get<void>(), 0, (size_t)bytes[0], ctx->stream) != hipSuccess)
-        return fail(dmk_fail(ctx, DMK_ERR_HIP, "uccsd_create: memset failed"));
-    {
-        FamScope fs(ctx, DMK_FAM_MISC);
-        const int na = nocc_a + nvir_a, nb = nocc_b + nvir_b;
-        hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)na * na)), dim3(NT), 0, ctx->stream, nocc_a, nvir_a, I.fock_a, h->fooa,
-                           h->fvva, h->fova, h->eoa, h->eva);
-        hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)nb * nb)), dim3(NT), 0, ctx->stream, nocc_b, nvir_b, I.fock_b, h->foob,
-                           h->fvvb, h->fovb, h->eob, h->evb);
-        if (hipGetLastError() != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "uccsd_create: kernel launch failed"));
-    }
-    // <ij||ab> = (ia|jb) - (ib|ja) in (i, j, a, b) order for the same-spin blocks, <iJ|aB> = (ia|JB) for the mixed one
-    if ((rc = h->E.perm(1.0, I.ovov, "iajb", 0.0, h->Gaa, "ijab"))) return fail(rc);
-    if ((rc = h->E.perm(-1.0, I.ovov, "ibja", 1.0, h->Gaa, "ijab"))) return fail(rc);
-    if ((rc = h->E.perm(1.0, I.OVOV, "IAJB", 0.0, h->Gbb, "IJAB"))) return fail(rc);
-    if ((rc = h->E.perm(-1.0, I.OVOV, "IBJA", 1.0, h->Gbb, "IJAB"))) return fail(rc);
-    if ((rc = h->E.perm(1.0, I.ovOV, "iaJB", 0.0, h->Gab, "iJaB"))) return fail(rc);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(dmk_fail(ctx, DMK_ERR_HIP, "uccsd_create: the stream failed"));
-    *out = h;
-    return DMK_OK;
+    return cc_create(h, "uccsd_create", [&]() -> int {
+        {
+            FamScope fs(ctx, DMK_FAM_MISC);
+            const int na = nocc_a + nvir_a, nb = nocc_b + nvir_b;
+            hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)na * na)), dim3(NT), 0, ctx->stream, nocc_a, nvir_a, I.fock_a, h->fooa,
+                               h->fvva, h->fova, h->eoa, h->eva);
+            hipLaunchKernelGGL(cc_fock_split_kernel, dim3(grid_of((long long)nb * nb)), dim3(NT), 0, ctx->stream, nocc_b, nvir_b, I.fock_b, h->foob,
+                               h->fvvb, h->fovb, h->eob, h->evb);
+            if (hipGetLastError() != hipSuccess) return dmk_fail(ctx, DMK_ERR_HIP, "uccsd_create: kernel launch failed");
+        }
+        // <ij||ab> = (ia|jb) - (ib|ja) in (i, j, a, b) order for the same-spin blocks, <iJ|aB> = (ia|JB) for the mixed one
+        int rc;
+        if ((rc = h->E.perm(1.0, I.ovov, "iajb", 0.0, h->Gaa, "ijab"))) return rc;
+        if ((rc = h->E.perm(-1.0, I.ovov, "ibja", 1.0, h->Gaa, "ijab"))) return rc;
+        if ((rc = h->E.perm(1.0, I.OVOV, "IAJB", 0.0, h->Gbb, "IJAB"))) return rc;
+        if ((rc = h->E.perm(-1.0, I.OVOV, "IBJA", 1.0, h->Gbb, "IJAB"))) return rc;
+        return h->E.perm(1.0, I.ovOV, "iaJB", 0.0, h->Gab, "iJaB");
+    }, out);
 }
 
-int dmk_uccsd_free(dmk_uccsd *h) {
-    if (!h) return DMK_OK;
-    (void)hipStreamSynchronize(h->ctx->stream);      // work that reads the handle's memory may still be queued
-    delete h;
-    return DMK_OK;
-}
+int dmk_uccsd_free(dmk_uccsd *h) { return cc_free(h); }
 
 int dmk_uccsd_init(dmk_uccsd *h) {
     if (!h) return DMK_ERR_INVALID;
-    const int rc = uc_init(h);
-    if (rc) return rc;
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->synced([h] { return uc_init(h); });
 }
 
 int dmk_uccsd_set(dmk_uccsd *h, const double *t1a, const double *t1b, const double *t2aa, const double *t2ab, const double *t2bb) {
     if (!h) return DMK_ERR_INVALID;
-    dmk_ctx *ctx = h->ctx;
     const double *src[5] = {t1a, t1b, t2aa, t2ab, t2bb};
     for (const double *p : src)
-        if (!p) return dmk_fail(ctx, DMK_ERR_INVALID, "uccsd_set: NULL amplitudes");
-    for (int p = 0; p < 5; ++p)
-        DMK_HIP(ctx, hipMemcpyAsync(h->x + h->off[p], src[p], (size_t)h->cnt[p] * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    h->have_amps = true;
-    return DMK_OK;
+        if (!p) return dmk_fail(h->ctx, DMK_ERR_INVALID, "uccsd_set: NULL amplitudes");
+    return h->set(src, h->T.x, &h->have_amps);
 }
 
 int dmk_uccsd_energy(dmk_uccsd *h, double *e_dev) {
     if (!h) return DMK_ERR_INVALID;
     if (!e_dev || !h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "uccsd_energy: no amplitudes yet (init or set first), or a NULL result");
-    const int rc = uc_energy(h, h->x, e_dev);
-    if (rc) return rc;
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->synced([=] { return uc_energy(h, h->T.x, e_dev); });
 }
 
 int dmk_uccsd_update(dmk_uccsd *h) {
     if (!h) return DMK_ERR_INVALID;
     if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "uccsd_update: no amplitudes yet (init or set first)");
-    const int rc = uc_update(h, h->x, h->xnew);
-    if (rc) return rc;
-    std::swap(h->x, h->xnew);
-    DMK_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-    return DMK_OK;
+    return h->step(h->T, [h](const double *from, double *to) { return uc_update(h, from, to); });
 }
 
 int dmk_uccsd_run(dmk_uccsd *h, int max_iter, double tol_e, double tol_normt, double *result_host) {
@@ -568,22 +504,16 @@ int dmk_uccsd_run(dmk_uccsd *h, int max_iter, double tol_e, double tol_normt, do
     int rc;
     if (!h->have_amps && (rc = uc_init(h))) return rc;
     // without a ring the steps are kept in n1a / n1b / tataa / tatab / tatbb, free between updates
-    Iterate s{&h->x, &h->xnew, h->ring_x, h->ring_e, 5, {}, {}, {h->n1a, h->n1b, h->tataa, h->tatab, h->tatbb}, true, "uccsd_run"};
-    for (int p = 0; p < 5; ++p) { s.off[p] = h->off[p]; s.cnt[p] = h->cnt[p]; }
+    const Iterate s{&h->T, {h->n1a, h->n1b, h->tataa, h->tatab, h->tatbb}, true, "uccsd_run"};
     return cc_iterate(h, s, max_iter, tol_e, tol_normt, [h](const double *from, double *to) { return uc_update(h, from, to); },
                       [h](const double *amp, double *e_dev) { return uc_energy(h, amp, e_dev); }, result_host);
 }
 
 int dmk_uccsd_get(dmk_uccsd *h, int what, double *out) {
     if (!h) return DMK_ERR_INVALID;
-    dmk_ctx *ctx = h->ctx;
-    if (!out || what < DMK_UCCSD_T1A || what > DMK_UCCSD_EMP2) return dmk_fail(ctx, DMK_ERR_INVALID, "uccsd_get: bad arguments");
-    if (!h->have_amps) return dmk_fail(ctx, DMK_ERR_STATE, "uccsd_get: no amplitudes yet (init or set first)");
-    const double *src = what == DMK_UCCSD_EMP2 ? h->rec + 15 : h->x + h->off[what];
-    const size_t cnt = what == DMK_UCCSD_EMP2 ? 1 : (size_t)h->cnt[what];
-    DMK_HIP(ctx, hipMemcpyAsync(out, src, cnt * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    DMK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DMK_OK;
+    if (!out || what < DMK_UCCSD_T1A || what > DMK_UCCSD_EMP2) return dmk_fail(h->ctx, DMK_ERR_INVALID, "uccsd_get: bad arguments");
+    if (!h->have_amps) return dmk_fail(h->ctx, DMK_ERR_STATE, "uccsd_get: no amplitudes yet (init or set first)");
+    return h->get(h->T.x, what, out);          // DMK_UCCSD_T1A .. _T2BB = 0 .. 4: the parts, then DMK_UCCSD_EMP2
 }
 
 }  // extern "C"

@@ -13,11 +13,9 @@ besides the correlation energy.
 solver.cc.RCCSD keeps refusing these (its tests pin that); solver.cc_solver.CCSolver is the reference-shaped front.  make_rdm2 stays
 unbuilt.  The module imports without a GPU.
 """
-import ctypes as C
-
 import numpy as np
 
-from libdmet_preview_amd._lib import lib, c_vp, c_dbl, c_i64
+from libdmet_preview_amd._lib import lib, c_dbl, c_i64
 from libdmet_preview_amd.solver import cc, ccsd_t, scf
 from libdmet_preview_amd.system import integral
 from libdmet_preview_amd.utils import logger as log
@@ -35,6 +33,8 @@ def lambda_plan_bytes(nocc, nvir, diis_space):
 
 
 class RCCSDLambda(cc.RCCSD):
+    _memory_title, _memory_extra = "RCCSD with Lambda,", (("lambda", "Lambda state"),)
+
     def __init__(self, mf, frozen=None, mo_coeff=None, mo_occ=None):
         cc.RCCSD.__init__(self, mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
         self.l1 = self.l2 = None
@@ -49,19 +49,6 @@ class RCCSDLambda(cc.RCCSD):
         plan["lambda"] = lambda_plan_bytes(o, self._scf._n - o, self.diis_space)
         return plan
 
-    def _check_memory(self):
-        plan = self.memory_plan()
-        need = plan["integrals"] + max(plan["transform"], plan["handle"] + plan["workspace"] + plan["lambda"])
-        if self.max_memory is None:
-            have, what = self._scf._ctx.mem_info()[0], "free on the device"
-        else:
-            have, what = int(float(self.max_memory) * (1 << 20)), "allowed by max_memory"
-        if need > have:
-            raise MemoryError("RCCSD with Lambda, nocc = %d, nvir = %d, diis_space = %d plans %d bytes of device memory (integral blocks "
-                              "%d, handle %d, Lambda state %d, contraction workspace %d, transform workspace %d); %d bytes are %s"
-                              % (self._nocc[0], self._scf._n - self._nocc[0], self.diis_space, need, plan["integrals"], plan["handle"],
-                                 plan["lambda"], plan["workspace"], plan["transform"], have, what))
-
     # ---- Lambda ------------------------------------------------------------------------------------------------------------------
     def _need_t(self, t1=None, t2=None):
         if (t1 is None) != (t2 is None):
@@ -73,22 +60,10 @@ class RCCSDLambda(cc.RCCSD):
             self.kernel()
 
     def _set_l(self, l1, l2):
-        ctx = self._scf._ctx
-        s1, s2 = self._shapes()
-        l1, l2 = np.asarray(l1, dtype=np.float64), np.asarray(l2, dtype=np.float64)
-        if l1.shape != s1 or l2.shape != s2:
-            raise ValueError("Lambda amplitudes of shapes %s, %s; expected %s, %s" % (l1.shape, l2.shape, s1, s2))
-        d1, d2 = ctx.to_device(l1), ctx.to_device(l2)
-        ctx.check(lib.dmk_rccsd_lambda_set(self._handle(), d1.ptr, d2.ptr))
+        self._put(lib.dmk_rccsd_lambda_set, self._flatten(l1, l2, "Lambda amplitudes"))
 
     def _get_l(self):
-        ctx = self._scf._ctx
-        out = []
-        for what, shape in zip((_L1, _L2), self._shapes()):
-            d = ctx.empty(shape, np.float64)
-            ctx.check(lib.dmk_rccsd_get(self._handle(), what, d.ptr))
-            out.append(d.get())
-        return out
+        return [self._fetch(what, shape) for what, shape in zip((_L1, _L2), self._shapes())]
 
     def update_lambda(self, l1, l2, t1=None, t2=None):
         """ONE application of the Lambda equations at the amplitudes t (default: the current ones): -> (l1new, l2new)."""
@@ -155,10 +130,9 @@ class RCCSDLambda(cc.RCCSD):
     def residual(self):
         """(r1, r2) = R_od - d t of the current amplitudes: zero at convergence."""
         ctx = self._scf._ctx
-        s1, s2 = self._shapes()
-        d1, d2 = ctx.empty(s1, np.float64), ctx.empty(s2, np.float64)
-        ctx.check(lib.dmk_rccsd_residual(self._handle(), d1.ptr, d2.ptr))
-        return d1.get(), d2.get()
+        dev = [ctx.empty(shape, np.float64) for shape in self._shapes()]
+        ctx.check(lib.dmk_rccsd_residual(self._handle(), *[d.ptr for d in dev]))
+        return self._rebuild([d.get() for d in dev])
 
     # ---- another Hamiltonian -----------------------------------------------------------------------------------------------------
     def expval(self, H0, h1, eri):
@@ -169,8 +143,7 @@ class RCCSDLambda(cc.RCCSD):
         if self.l1 is None:
             self.solve_lambda()
         mf = self._scf
-        ctx, n, o = mf._ctx, mf._n, self._nocc[0]
-        v = n - o
+        ctx, n = mf._ctx, mf._n
         h1 = np.asarray(h1, dtype=np.float64).reshape(n, n)
         eri = np.asarray(eri, dtype=np.float64)
         fmt, spin_dim = integral.get_eri_format(eri, n)
@@ -186,12 +159,10 @@ class RCCSDLambda(cc.RCCSD):
         cs = self._mo()
         e_hf = float(np.sum(dm * (h1 + 0.5 * veff)))
         d_c, d_f = ctx.to_device(cs), ctx.to_device(cs.T @ (h1 + veff) @ cs)
-        rng = {"o": (d_c, 0, o), "v": (d_c, o, v)}
-        blocks = [scf.ao2mo_block_dev(ctx, n, d_blk, [rng[x] for x in name], compact=(name == "vvvv")) for name in cc._BLOCKS]
+        blocks = self._mo_blocks(d_blk, d_c)
         d_t = [ctx.to_device(a) for a in (self.t1, self.t2, self.l1, self.l2)]
         d_e = ctx.empty((1,), np.float64)
-        probe = c_vp()
-        ctx.check(lib.dmk_rccsd_create(ctx.h, o, v, d_f.ptr, *([b.ptr for b in blocks] + [v * (v + 1) // 2, 0, C.byref(probe)])))
+        probe = self._create_over(d_f, blocks, 0)
         try:
             ctx.check(lib.dmk_rccsd_set(probe, d_t[0].ptr, d_t[1].ptr))
             ctx.check(lib.dmk_rccsd_lagrangian(probe, d_t[2].ptr, d_t[3].ptr, d_e.ptr))

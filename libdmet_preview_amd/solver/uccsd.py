@@ -16,12 +16,10 @@ import ctypes as C
 
 import numpy as np
 
-from libdmet_preview_amd._lib import lib, c_vp, c_dbl, c_i64
+from libdmet_preview_amd._lib import lib, c_vp, c_i64
 from libdmet_preview_amd.solver import scf
-from libdmet_preview_amd.solver._posthf import PostHFBase
-from libdmet_preview_amd.utils import logger as log
+from libdmet_preview_amd.solver.cc import _CCSDBase
 
-_T1A, _T1B, _T2AA, _T2AB, _T2BB, _EMP2 = range(6)
 _PACK_BOTH = 3          # DMK_AO2MO_PACK_BRA | DMK_AO2MO_PACK_KET
 
 # what csrc/uccsd.hip reads, in the order of dmk_uccsd_ints: lower case alpha, upper case beta
@@ -56,29 +54,13 @@ class _ERIS(object):
     fock = None
 
 
-class UCCSD(PostHFBase):
+class UCCSD(_CCSDBase):
     _restricted = False
     _method = "UCCSD"
-
-    def __init__(self, mf, frozen=None, mo_coeff=None, mo_occ=None):
-        PostHFBase.__init__(self, mf, frozen=frozen, mo_coeff=mo_coeff, mo_occ=mo_occ)
-        # the reference's defaults (solver/cc.py:569-572)
-        self.conv_tol, self.conv_tol_normt, self.diis_space, self.max_cycle = 1e-7, 1e-5, 8, 200
-        self.level_shift, self.iterative_damping = 0.0, 1.0
-        self.max_memory = None          # MB of device memory the solver may plan with (None: what is free when it starts)
-        self.converged, self.cycles = False, 0
-        self.emp2 = self.t1 = self.t2 = None
-        self._h = self._eris = None
+    _name, _prefix, _memory_title = "UCCSD", "dmk_uccsd_", "UCCSD with"
+    _not_built = staticmethod(_not_built)
 
     # ---- what is not built -------------------------------------------------------------------------------------------------------
-    def _check_options(self):
-        if self.level_shift != 0:
-            _not_built("UCCSD with a level shift (level_shift = %r)" % (self.level_shift,))
-        if self.iterative_damping != 1:
-            _not_built("UCCSD with damping (iterative_damping = %r)" % (self.iterative_damping,))
-        if not 0 <= int(self.diis_space) <= 12:
-            raise ValueError("diis_space = %r outside [0, 12]" % (self.diis_space,))
-
     def solve_lambda(self, *args, **kwargs):
         _not_built("The unrestricted Lambda equations (solve_lambda)")
 
@@ -90,19 +72,6 @@ class UCCSD(PostHFBase):
 
     def ccsd_t(self, *args, **kwargs):
         _not_built("The unrestricted perturbative triples (T) (ccsd_t)")
-
-    # ---- life time ---------------------------------------------------------------------------------------------------------------
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and self._scf._ctx.h:
-            lib.dmk_uccsd_free(h)
-        self._eris = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- memory ------------------------------------------------------------------------------------------------------------------
     def _extents(self):
@@ -128,19 +97,9 @@ class UCCSD(PostHFBase):
             transform = max(transform, int(p[1]))
         return {"handle": handle, "workspace": ws, "integrals": integrals, "transform": transform}
 
-    def _check_memory(self):
-        plan = self.memory_plan()
-        need = plan["integrals"] + max(plan["transform"], plan["handle"] + plan["workspace"])
-        if self.max_memory is None:
-            have, what = self._scf._ctx.mem_info()[0], "free on the device"
-        else:
-            have, what = int(float(self.max_memory) * (1 << 20)), "allowed by max_memory"
-        if need > have:
-            e = self._extents()
-            raise MemoryError("UCCSD with nocc = (%d, %d), nvir = (%d, %d), diis_space = %d plans %d bytes of device memory (integral "
-                              "blocks %d, handle %d, contraction workspace %d, transform workspace %d); %d bytes are %s"
-                              % (e["o"], e["O"], e["v"], e["V"], self.diis_space, need, plan["integrals"], plan["handle"],
-                                 plan["workspace"], plan["transform"], have, what))
+    def _extents_text(self):
+        e = self._extents()
+        return "nocc = (%d, %d), nvir = (%d, %d)" % (e["o"], e["O"], e["v"], e["V"])
 
     # ---- the integrals -----------------------------------------------------------------------------------------------------------
     def ao2mo(self, mo_coeff=None):
@@ -171,20 +130,15 @@ class UCCSD(PostHFBase):
         eris.fock = [cs[s].T @ fock[s] @ cs[s] for s in range(2)]
         return eris
 
-    def _handle(self):
-        if self._h is None:
-            self._check_options()
-            self._check_memory()
-            ctx, e = self._scf._ctx, self._extents()
-            eris = self.ao2mo()
-            eris.d_fock = [ctx.to_device(f) for f in eris.fock]
-            pair = lambda k: k * (k + 1) // 2
-            ints = _Ints(fock_a=eris.d_fock[0].ptr, fock_b=eris.d_fock[1].ptr, ld_vvvv=pair(e["v"]), ld_VVVV=pair(e["V"]), ld_vvVV=pair(e["V"]),
-                         **{name: getattr(eris, name).ptr for name in _BLOCKS})
-            h = c_vp()
-            ctx.check(lib.dmk_uccsd_create(ctx.h, e["o"], e["v"], e["O"], e["V"], C.byref(ints), int(self.diis_space), C.byref(h)))
-            self._h, self._eris = h, eris          # the blocks are borrowed by the handle: kept alive here
-        return self._h
+    def _create(self, eris, diis_space):
+        ctx, e = self._scf._ctx, self._extents()
+        eris.d_fock = [ctx.to_device(f) for f in eris.fock]
+        pair = lambda k: k * (k + 1) // 2
+        ints = _Ints(fock_a=eris.d_fock[0].ptr, fock_b=eris.d_fock[1].ptr, ld_vvvv=pair(e["v"]), ld_VVVV=pair(e["V"]), ld_vvVV=pair(e["V"]),
+                     **{name: getattr(eris, name).ptr for name in _BLOCKS})
+        h = c_vp()
+        ctx.check(lib.dmk_uccsd_create(ctx.h, e["o"], e["v"], e["O"], e["V"], C.byref(ints), int(diis_space), C.byref(h)))
+        return h
 
     # ---- amplitudes --------------------------------------------------------------------------------------------------------------
     def _shapes(self):
@@ -192,60 +146,14 @@ class UCCSD(PostHFBase):
         oa, va, ob, vb = e["o"], e["v"], e["O"], e["V"]
         return (oa, va), (ob, vb), (oa, oa, va, va), (oa, ob, va, vb), (ob, ob, vb, vb)
 
-    def _set(self, t1, t2):
-        ctx = self._scf._ctx
+    def _flatten(self, t1, t2):
         if t1 is None or t2 is None or len(t1) != 2 or len(t2) != 3:
             raise ValueError("unrestricted amplitudes are t1 = (t1a, t1b) and t2 = (t2aa, t2ab, t2bb)")
         amps = [np.ascontiguousarray(a, dtype=np.float64) for a in tuple(t1) + tuple(t2)]
         shapes = self._shapes()
         if any(a.shape != s for a, s in zip(amps, shapes)):
             raise ValueError("amplitudes of shapes %s; expected %s" % ([a.shape for a in amps], list(shapes)))
-        dev = [ctx.to_device(a) for a in amps]
-        ctx.check(lib.dmk_uccsd_set(self._handle(), *[d.ptr for d in dev]))
+        return amps
 
-    def _get(self, what):
-        ctx = self._scf._ctx
-        d = ctx.empty((self._shapes() + ((1,),))[what], np.float64)
-        ctx.check(lib.dmk_uccsd_get(self._handle(), what, d.ptr))
-        return d.get()
-
-    def _amps(self):
-        return (self._get(_T1A), self._get(_T1B)), (self._get(_T2AA), self._get(_T2AB), self._get(_T2BB))
-
-    def energy(self, t1=None, t2=None):
-        """e_corr of the given amplitudes (default: the current ones)."""
-        ctx = self._scf._ctx
-        if t1 is not None or t2 is not None:
-            self._set(t1, t2)
-        d_e = ctx.empty((1,), np.float64)
-        ctx.check(lib.dmk_uccsd_energy(self._handle(), d_e.ptr))
-        return float(d_e.get()[0])
-
-    def update_amps(self, t1, t2):
-        """ONE application of the amplitude equations: -> ((t1a, t1b), (t2aa, t2ab, t2bb))."""
-        self._set(t1, t2)
-        self._scf._ctx.check(lib.dmk_uccsd_update(self._handle()))
-        return self._amps()
-
-    def kernel(self, t1=None, t2=None, mo_coeff=None):
-        """-> (e_corr, (t1a, t1b), (t2aa, t2ab, t2bb)), the amplitudes on the host; starts from t1 / t2 when both are given, else from the
-        MP2 guess."""
-        if (t1 is None) != (t2 is None):
-            raise ValueError("a restart needs both t1 and t2")
-        if mo_coeff is not None:
-            self.close()
-            self.mo_coeff = mo_coeff
-            self._set_orbitals(mo_coeff)
-        ctx = self._scf._ctx
-        h = self._handle()
-        ctx.check(lib.dmk_uccsd_init(h))
-        self.emp2 = float(self._get(_EMP2)[0])
-        if t1 is not None:
-            self._set(t1, t2)
-        res = (c_dbl * 5)()
-        ctx.check(lib.dmk_uccsd_run(h, int(self.max_cycle), float(self.conv_tol), float(self.conv_tol_normt), res))
-        self.e_corr, self.converged, self.cycles = float(res[0]), bool(res[1]), int(res[2])
-        self.t1, self.t2 = self._amps()
-        log.debug(0, "UCCSD: e_corr = %.12f after %d iterations (|dt| = %.2e, dE = %.2e)%s", self.e_corr, self.cycles, res[3], res[4],
-                  "" if self.converged else ", NOT converged")
-        return self.e_corr, self.t1, self.t2
+    def _rebuild(self, parts):
+        return tuple(parts[:2]), tuple(parts[2:])
