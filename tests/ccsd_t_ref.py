@@ -1,6 +1,6 @@
 """
 Numpy restatements of the perturbative triples (T) for the tests of DESIGN.md K22 (tests/test_host_ccsd_t.py,
-tests/test_gpu_ccsd_t.py), in two formulations that share nothing with the device code (csrc/ccsd_t.hip) and little with each other.
+tests/test_gpu_ccsd_t.py, tests/test_gpu_ccsd_t_shapes.py), in two formulations that share nothing with the device code (csrc/ccsd_t.hip) and little with each other.
 
   t_spin_orbital(so, t1, t2)      (a) the spin-orbital formula on ccsd_ref.spin_orbital / to_so, with 6-index arrays (small shapes only):
                                       E_(T) = 1/36 sum c (c + d) / D,
@@ -11,6 +11,9 @@ tests/test_gpu_ccsd_t.py), in two formulations that share nothing with the devic
                                   (b) the closed-shell formula of DESIGN.md K22 over the blocks of ccsd_ref.restricted_blocks, evaluated
                                       triple by triple over a >= b >= c, in float64 or np.longdouble: -> (E_(T), S), S the same expression
                                       with the absolute value taken at every product (the scale rounding errors are measured against)
+  t_closed_shell_streamed(f, blocks, t1, t2, dtype)
+                                  (b) again with the six w of one unique triple at a time from matrix products: O(o^3) memory where
+                                      t_closed_shell holds v^3 o^3 numbers twice (tests/test_gpu_ccsd_t_shapes.py: o up to 129, v up to 17)
   fci_energy(sysm, nelec_pair)    the exact ground-state energy of a small closed-shell system (all determinants, plain numpy)
 
 Notation of (b): i j k m occupied, a b c f virtual, integrals in chemists' order, t2[i, j, a, b] = t_ij^ab.
@@ -20,7 +23,9 @@ Notation of (b): i j k m occupied, a b c f virtual, integrals in chemists' order
     r3(X)_ijk = 4 X_ijk + X_jki + X_kij - 2 X_kji - 2 X_ikj - 2 X_jik
     Y^abc = sum_ijk W_ijk r3(V)_ijk / D_ijk,     E_(T) = sum_{a >= b >= c} mult(abc) Y^abc,  mult = 2 / 1 / 1/3
 """
+import concurrent.futures
 import itertools
+import os
 
 import numpy as np
 
@@ -97,6 +102,92 @@ def t_closed_shell(fock_mo, blocks, t1, t2, dtype=np.float64):
                 mult = third if a == c else (dtype(1) if (a == b or b == c) else dtype(2))
                 e_t += mult * np.sum(W * _r3(W + X / 2, -1) / D)
                 s_t += mult * np.sum(Wa * _r3(Wa + Xa / 2, +1) / abs(D))
+    return float(e_t), float(s_t)
+
+
+def t_closed_shell_streamed(fock_mo, blocks, t1, t2, dtype=np.float64, threads=None, chunk_elements=1 << 21):
+    """(b) again -> (E_(T), S), for the shapes at which v^3 o^3 numbers do not fit: the six w of a unique triple from matrix products,
+
+        particle part of w^{xyz}   ovvv[:, x, y, :] @ t2[:, :, z, :].reshape(o o, v).T     viewed as (i, k, j)
+        hole part of w^{xyz}       ovoo[:, x, :, :].reshape(o o, o) @ t2[:, :, y, z]       viewed as (i, j, k)
+
+    and nothing kept between triples.  The elementwise work of a pair (a, b) runs over a chunk of its c <= b at once (a leading axis
+    of at most chunk_elements / o^3 triples, so the memory stays O(o^3)), and the triples are added up one by one in the order of
+    t_closed_shell.  The chunks run on `threads` Python threads (default: the CPUs of the process, 16 at the most); the result does
+    not depend on their number."""
+    o, v = t1.shape
+    cast = lambda x: np.asarray(x, dtype=dtype)
+    f = cast(fock_mo)
+    ovvv, ovoo, ovov = cast(blocks["ovvv"]), cast(blocks["ovoo"]), cast(blocks["ovov"])
+    t1, t2 = cast(t1), cast(t2)
+    fov, eo, ev = f[:o, o:], np.diag(f)[:o], np.diag(f)[o:]
+    sets = ((ovvv, ovoo, ovov, t1, t2, fov, -1), (abs(ovvv), abs(ovoo), abs(ovov), abs(t1), abs(t2), abs(fov), +1))
+    eijk = eo[:, None, None] + eo[None, :, None] + eo[None, None, :]
+    third = dtype(1) / dtype(3)
+    step = max(1, int(chunk_elements) // o ** 3)
+
+    def six(arrays, a, b, cs):
+        """(W, X) of the triples (a, b, c), c in the slice cs, as (c, i, j, k), from one set of arrays: the signed one, or the
+        absolute values with every term added.  All three virtual indices are index VECTORS of the chunk's length (a and b
+        repeated), so every array below has the same shape whichever place c takes in the permutation."""
+        vvv, voo, vov, s1, s2, sf, sign = arrays
+        nc = cs.stop - cs.start
+        W = np.zeros((nc, o, o, o), dtype=dtype)
+        X = np.zeros((nc, o, o, o), dtype=dtype)
+        x = (np.full(nc, a), np.full(nc, b), np.arange(cs.start, cs.stop))
+        for p in _PERMS:
+            X0, X1, X2 = x[p[0]], x[p[1]], x[p[2]]                       # the pairs of this w, in its own order (first, second, third)
+            # particle: sum_f (first X0 | X1 f) t_{third second}^{X2 f}
+            A = vvv[:, X0, X1, :].transpose(1, 0, 2)                     # (c, first, f)
+            B = s2[:, :, X2, :].transpose(2, 0, 1, 3).reshape(nc, o * o, v)          # (c, (third second), f)
+            part = np.matmul(A, B.transpose(0, 2, 1)).reshape(nc, o, o, o).transpose(0, 1, 3, 2)     # (c, first, second, third)
+            # hole: sum_m (first X0 | second m) t_{m third}^{X1 X2}
+            A = voo[:, X0, :, :].transpose(1, 0, 2, 3).reshape(nc, o * o, o)         # (c, (first second), m)
+            B = s2[:, :, X1, X2].transpose(2, 0, 1)                      # (c, m, third)
+            hole = np.matmul(A, B).reshape(nc, o, o, o)                  # (c, first, second, third)
+            w = part + sign * hole
+            # (first X0 | second X1) t1[third, X2] + t2[first, second, X0, X1] f_ov[third, X2]
+            g = vov[:, X0, :, X1]                                        # (c, first, second): index vectors around a slice lead
+            t = s2[:, :, X0, X1].transpose(2, 0, 1)                      # (c, first, second)
+            u, h = s1[:, X2].T, sf[:, X2].T                              # (c, third)
+            term = g[:, :, :, None] * u[:, None, None, :] + t[:, :, :, None] * h[:, None, None, :]
+            # the occupied axes from the order of this w to (i, j, k) of the triple (a, b, c): t_closed_shell's transposition
+            inv = [0] + [1 + q for q in np.argsort(p)]
+            W += w.transpose(*inv)
+            X += term.transpose(*inv)
+        return W, X
+
+    def r3(xx, sign):
+        return (4 * xx + xx.transpose(0, 2, 3, 1) + xx.transpose(0, 3, 1, 2)
+                + sign * 2 * (xx.transpose(0, 3, 2, 1) + xx.transpose(0, 1, 3, 2) + xx.transpose(0, 2, 1, 3)))
+
+    def chunk(item):
+        """The sums over i j k of the triples (a, b, c in cs): one (signed, absolute) pair of numbers per c."""
+        a, b, cs = item
+        W, X = six(sets[0], a, b, cs)
+        Wa, Xa = six(sets[1], a, b, cs)
+        D = eijk[None] - (ev[a] + ev[b] + ev[cs])[:, None, None, None]
+        ye = W * r3(W + X / 2, -1) / D
+        ys = Wa * r3(Wa + Xa / 2, +1) / abs(D)
+        return [(np.sum(ye[n]), np.sum(ys[n])) for n in range(cs.stop - cs.start)]
+
+    # the chunks share nothing, so they may run side by side (numpy drops the interpreter lock in its loops); the sum over the
+    # triples below is taken in the fixed order of the list whatever the number of threads
+    items = [(a, b, slice(c0, min(b + 1, c0 + step))) for a in range(v) for b in range(a + 1) for c0 in range(0, b + 1, step)]
+    if threads is None:
+        threads = min(16, len(os.sched_getaffinity(0)))
+    threads = max(1, min(int(threads), len(items)))
+    if threads == 1:
+        sums = [chunk(item) for item in items]
+    else:
+        with concurrent.futures.ThreadPoolExecutor(threads) as pool:
+            sums = list(pool.map(chunk, items))
+    e_t = s_t = dtype(0)
+    for (a, b, cs), per_c in zip(items, sums):
+        for c, (ye, ys) in zip(range(cs.start, cs.stop), per_c):
+            mult = third if a == c else (dtype(1) if (a == b or b == c) else dtype(2))
+            e_t += mult * ye
+            s_t += mult * ys
     return float(e_t), float(s_t)
 
 

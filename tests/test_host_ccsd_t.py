@@ -9,7 +9,9 @@ Normalisation   CCSD is exact through third order of perturbation theory and (T)
 Measured        the references agree within 7.6e-16 relative (bound 1e-12); at (1, 4) and (4, 1) the closed-shell form gives
                 |E| <= 5.3e-19 (S = 0.04 ... 0.08); rho(1) = 0.0946, rho(1/2) = 0.0479 (and 0.0242 at 1/4: it halves with lam) on the 4-electron,
                 n = 6 system of seed NORM_SEED; seeds 1, 2, 3 give 0.039 / 0.020, 0.130 / 0.064, 0.161 / 0.081
-                (profiles/ccsd_t_notes.txt).
+                (profiles/ccsd_t_notes.txt).  The streamed closed-shell form (the reference of tests/test_gpu_ccsd_t_shapes.py)
+                agrees with the closed-shell form within 3.6e-16 relative in E and bit for bit in S (bound 1e-13) at (2, 2), (3, 4),
+                (4, 3), (5, 17), canonical and rotated, and gives |E| <= 4.5e-19 at (1, 4) and (4, 1).
 """
 import ctypes as C
 
@@ -58,6 +60,39 @@ def test_triples_vanish_with_one_occupied_or_one_virtual(o, v):
         f, blocks = CR.restricted_blocks(sysm, Cm, o)
         e, s = TR.t_closed_shell(f, blocks, t1, t2)
         print("(o, v) = (%d, %d)%s: E_(T) = %.3e, S = %.3e, |E| / (64 eps S) = %.3f" % (o, v, " rotated" if rotated else "", e, s, abs(e) / (64 * EPS * s)))
+        assert s > 0.0 and abs(e) <= 64 * EPS * s
+
+
+STREAMED = [(2, 2, np.float64), (3, 4, np.float64), (4, 3, np.float64), (5, 17, np.float64),
+            (2, 2, np.longdouble), (3, 4, np.longdouble), (4, 3, np.longdouble)]
+
+
+@pytest.mark.parametrize("rotated", [False, True])
+@pytest.mark.parametrize("o,v,dtype", STREAMED, ids=lambda x: x.__name__ if isinstance(x, type) else str(x))
+def test_the_streamed_form_is_the_closed_shell_form(o, v, dtype, rotated):
+    """t_closed_shell_streamed (matrix products, O(o^3) memory: the reference of tests/test_gpu_ccsd_t_shapes.py) against
+    t_closed_shell, E relative to |E| and S relative to S.  The two differ in the order of the K sums only (einsum against a matrix
+    product), which is a few eps of S spread over the elements; |E| / S is 3e-4 .. 9e-3 here.  With the c of a pair in chunks of two
+    (the path the large shapes take) the numbers are the same within the same bound, and they do not depend on the thread count."""
+    sysm, Cm, t1, t2 = _case(o, v, rotated)
+    f, blocks = CR.restricted_blocks(sysm, Cm, o)
+    e, s = TR.t_closed_shell(f, blocks, t1, t2, dtype)
+    es, ss = TR.t_closed_shell_streamed(f, blocks, t1, t2, dtype)
+    print("(o, v) = (%d, %d)%s %s: closed-shell %.16e, streamed %.16e, relative difference %.2e; S %.2e"
+          % (o, v, " rotated" if rotated else "", dtype.__name__, e, es, abs(e - es) / abs(e), abs(s - ss) / s))
+    assert e != 0.0 and abs(es - e) <= 1e-13 * abs(e) and abs(ss - s) <= 1e-13 * s
+    assert TR.t_closed_shell_streamed(f, blocks, t1, t2, dtype, threads=1) == (es, ss)
+    ec, sc = TR.t_closed_shell_streamed(f, blocks, t1, t2, dtype, chunk_elements=2 * o ** 3)
+    assert abs(ec - e) <= 1e-13 * abs(e) and abs(sc - s) <= 1e-13 * s
+
+
+@pytest.mark.parametrize("o,v", [(1, 4), (4, 1)])
+def test_the_streamed_form_vanishes_with_one_occupied_or_one_virtual(o, v):
+    for rotated in (False, True):
+        sysm, Cm, t1, t2 = _case(o, v, rotated)
+        f, blocks = CR.restricted_blocks(sysm, Cm, o)
+        e, s = TR.t_closed_shell_streamed(f, blocks, t1, t2)
+        print("(o, v) = (%d, %d)%s: streamed E_(T) = %.3e, S = %.3e, |E| / (64 eps S) = %.3f" % (o, v, " rotated" if rotated else "", e, s, abs(e) / (64 * EPS * s)))
         assert s > 0.0 and abs(e) <= 64 * EPS * s
 
 
